@@ -13,9 +13,12 @@ N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in t
 process is one rank; started plainly with --gpus N > 1 it launches `python -m torch.distributed.run --nproc-per-node N bench.py ...`
 as a child BEFORE touching the GPU, relays rank 0's JSON line and exits with the child's code.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (icnn_step_kernel): algorithmic FLOPs per launch
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K fits, writes the last fit's outputs (--dump-outputs DIR)
+and prints the line: `value` (fits/s), `ms_per_step` (one timed fit), the quality and determinism fields of the timed fits.
+--full adds what takes runs of its own: `roofline` for the dominant kernel (icnn_step_kernel): algorithmic FLOPs per launch
 (105,312 flop/point/step x 65,536 points x images) / its average launch duration measured live with events on the launch
-stream.  `cpu_baseline` times the CPU oracle (torch, all host threads) on a bounded sample (rank 0, N = 1 only).
+stream; the throughput and strong-scaling entries; parity with the reference fixtures; the other priors (`variants`); and
+`cpu_baseline`, which times the CPU oracle (torch, all host threads) on a bounded sample (rank 0, N = 1 only).
 """
 import argparse
 import contextlib
@@ -36,8 +39,12 @@ PEAK_FP32_MATRIX_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3, help="timed fits per GPU")
+    ap.add_argument("--steps", type=int, default=3, help="timed fits per GPU (at least 1)")
     ap.add_argument("--warmup", type=int, default=1, help="untimed fits per GPU")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline figure: roofline, throughput "
+                    "and strong-scaling entries, parity with the reference fixtures, variants, CPU baseline (the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed fits, write what the last one returned (rank 0's images) as DIR/<name>.npy, float32")
     ap.add_argument("--epochs", type=int, default=2000, help="optimizer steps per fit (E)")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--images-per-gpu", type=int, default=1)
@@ -55,7 +62,10 @@ def parse_args():
     ap.add_argument("--throughput-images", type=int, default=64,
                     help="also time ONE full fit of this many images per GPU (BASELINE configs[2] = 512/8) and report it "
                          "under 'throughput_mode' (0 = skip); never part of `value`")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -115,6 +125,8 @@ def main():
     rehearsal = os.environ.get("BENCH_REHEARSAL", "0") == "1"
     if rehearsal and backend != "gloo":
         raise SystemExit("[bench] BENCH_REHEARSAL=1 needs BENCH_BACKEND=gloo")
+    if rehearsal and args.dump_outputs:
+        raise SystemExit("[bench] --dump-outputs: the rehearsal runs no fit, it has no outputs")
     if args.gpus != world:
         raise SystemExit(f"[bench] --gpus {args.gpus} but WORLD_SIZE {world}: start it as "
                          f"`python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus} ...` "
@@ -241,68 +253,74 @@ def main():
     iou_all = gather_cat(iou)
     miou = float(iou_all.mean().item())
 
-    # ---- roofline of the dominant kernel: average launch duration by HIP events on the launch stream ------------------------
-    # In the timed region every optimizer step is two back-to-back launches (step kernel, update kernel; rocprofv3's kernel
-    # trace of this command shows no gap between them).  One more fit of the same workload brackets every launch of both
-    # kernels with its own pair of events (inrfit_timing_*); the event packets stretch the sequence a little, and that excess -
-    # (step bracket + update bracket) minus the un-instrumented time per optimizer step measured above - is taken off the two
-    # brackets in equal parts.  -> `kernel_us`, the step kernel's duration IN the optimisation sequence (parameter image just
-    # rewritten by the update), which `frac` is quoted on.  A plain train of identical step-kernel launches between one pair of
-    # events is ~3 us faster per launch (`kernel_us_back_to_back`).
-    params = res.params
-    ws = A.icnn.step_only(spec, params, grid, unaries, 5)           # warm
-    torch.cuda.synchronize(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    A.icnn.step_only(spec, params, grid, unaries, args.kernel_iters, workspace=ws)
-    e1.record()
-    torch.cuda.synchronize(dev)
-    kernel_b2b_ms = e0.elapsed_time(e1) / args.kernel_iters
-    n_seq = min(E, 500)
-    with A.icnn.step_kernel_brackets(n_seq) as seq:
-        A.fit(spec, init.clone(), grid, unaries, n_seq, lr=2e-3, loss="se", optimizer="adam", clamp=True, record_loss=False,
-              want_logits=False)
-    us_per_step = elapsed / args.steps / E * 1e6
-    excess = max(seq.avg_us + seq.update_avg_us - us_per_step, 0.0)
-    kernel_ms = (seq.avg_us - 0.5 * excess) * 1e-3
-    update_us = seq.update_avg_us - 0.5 * excess
-    flop_per_launch = STEP_FLOP_PER_POINT * N * B
-    achieved = flop_per_launch / (kernel_ms * 1e-3) / 1e12
-    # HBM bytes per launch of this kernel from the PMC counters (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 --pmc passes of
-    # this same command: tools/profile_round.sh).  A --pmc pass cannot run inside this process, so the figure is read from the
-    # committed summary of the newest round that has one and only quoted for the configuration it was measured on;
-    # `traffic_source` names the file.  `algorithmic_bytes`: SURVEY 8(d)'s 4-12 B per point (targets [+ grid + logits]) PLUS what
-    # this design adds on purpose - one gradient slab per workgroup (wgs x PS x 4 B written here, read by the update kernel) and
-    # the parameter image every workgroup copies into LDS - so `traffic_over_algorithmic` separates "wasted re-reads" (none: ~1.0)
-    # from the slab round trip the design pays for (`traffic_over_survey_bytes`).
-    traffic, traffic_source = None, None
-    for tag in ("r04_b", "r03_f", "r03_e", "r02_e"):
-        tf = os.path.join(ROOT, "profiles", f"{tag}_pmc_step_kernel.json")
-        if B == 1 and S == 256 and os.path.exists(tf):
-            with open(tf) as f:
-                traffic = json.load(f).get("traffic_bytes_per_launch")
-            traffic_source = os.path.relpath(tf, ROOT)
-            break
-    lib0 = A._lib.load()
-    wgs = int(lib0.inrfit_slabs_per_image(N, B))
-    slab_cols = (19222 + 31) // 32 * 32 if spec.n_hidden == 130 and spec.in_features == 2 else None   # Cfg<130,2>::SL_COLS (icnn_step.h), rows on 128-byte lines
-    survey_bytes = 12 * N * B                                   # <= 8 B grid + 4 B target per point
-    design_bytes = None
-    if slab_cols is not None:
-        design_bytes = 4 * N * B + B * wgs * slab_cols * 4 + 8 * 77 * 1024   # targets + slabs + the parameter image once per XCD
-    # what a launch of nothing but independent fp32 MFMAs on all 1024 SIMDs reaches on THIS box (~2.1 GHz under that load instead
-    # of the 2.4 GHz the nominal peak assumes): the practical ceiling, reported next to `peak`, never instead of it
-    mfma_stream = A.icnn.mfma_stream_tflops(dev)
-    roofline = {"bound": "mfma", "achieved": round(achieved, 3), "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved / PEAK_FP32_MATRIX_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "algorithmic_bytes": design_bytes, "survey_bytes_per_launch": survey_bytes,
-                "traffic_over_algorithmic": round(traffic / design_bytes, 3) if traffic and design_bytes else None,
-                "traffic_over_survey_bytes": round(traffic / survey_bytes, 1) if traffic else None,
-                "kernel": "icnn_step_kernel<130,2,train>", "kernel_us": round(kernel_ms * 1e3, 2),
-                "kernel_samples": seq.samples, "kernel_us_back_to_back": round(kernel_b2b_ms * 1e3, 2),
-                "update_kernel_us": round(update_us, 2), "event_bracket_excess_us": round(excess, 2),
-                "flop_per_launch": flop_per_launch, "mfma_only_stream_tflops": round(mfma_stream, 1),
-                "frac_of_mfma_only_stream": round(achieved / mfma_stream, 4)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, seeds)
+
+    # ---- everything below the headline figure runs with --full only ------------------------------------------------------------
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel: average launch duration by HIP events on the launch stream ------------------------
+        # In the timed region every optimizer step is two back-to-back launches (step kernel, update kernel; rocprofv3's kernel
+        # trace of this command shows no gap between them).  One more fit of the same workload brackets every launch of both
+        # kernels with its own pair of events (inrfit_timing_*); the event packets stretch the sequence a little, and that excess -
+        # (step bracket + update bracket) minus the un-instrumented time per optimizer step measured above - is taken off the two
+        # brackets in equal parts.  -> `kernel_us`, the step kernel's duration IN the optimisation sequence (parameter image just
+        # rewritten by the update), which `frac` is quoted on.  A plain train of identical step-kernel launches between one pair of
+        # events is ~3 us faster per launch (`kernel_us_back_to_back`).
+        params = res.params
+        ws = A.icnn.step_only(spec, params, grid, unaries, 5)           # warm
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        A.icnn.step_only(spec, params, grid, unaries, args.kernel_iters, workspace=ws)
+        e1.record()
+        torch.cuda.synchronize(dev)
+        kernel_b2b_ms = e0.elapsed_time(e1) / args.kernel_iters
+        n_seq = min(E, 500)
+        with A.icnn.step_kernel_brackets(n_seq) as seq:
+            A.fit(spec, init.clone(), grid, unaries, n_seq, lr=2e-3, loss="se", optimizer="adam", clamp=True, record_loss=False,
+                  want_logits=False)
+        us_per_step = elapsed / args.steps / E * 1e6
+        excess = max(seq.avg_us + seq.update_avg_us - us_per_step, 0.0)
+        kernel_ms = (seq.avg_us - 0.5 * excess) * 1e-3
+        update_us = seq.update_avg_us - 0.5 * excess
+        flop_per_launch = STEP_FLOP_PER_POINT * N * B
+        achieved = flop_per_launch / (kernel_ms * 1e-3) / 1e12
+        # HBM bytes per launch of this kernel from the PMC counters (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 --pmc passes of
+        # this same command: tools/profile_round.sh).  A --pmc pass cannot run inside this process, so the figure is read from the
+        # committed summary of the newest round that has one and only quoted for the configuration it was measured on;
+        # `traffic_source` names the file.  `algorithmic_bytes`: SURVEY 8(d)'s 4-12 B per point (targets [+ grid + logits]) PLUS what
+        # this design adds on purpose - one gradient slab per workgroup (wgs x PS x 4 B written here, read by the update kernel) and
+        # the parameter image every workgroup copies into LDS - so `traffic_over_algorithmic` separates "wasted re-reads" (none: ~1.0)
+        # from the slab round trip the design pays for (`traffic_over_survey_bytes`).
+        traffic, traffic_source = None, None
+        for tag in ("r04_b", "r03_f", "r03_e", "r02_e"):
+            tf = os.path.join(ROOT, "profiles", f"{tag}_pmc_step_kernel.json")
+            if B == 1 and S == 256 and os.path.exists(tf):
+                with open(tf) as f:
+                    traffic = json.load(f).get("traffic_bytes_per_launch")
+                traffic_source = os.path.relpath(tf, ROOT)
+                break
+        lib0 = A._lib.load()
+        wgs = int(lib0.inrfit_slabs_per_image(N, B))
+        slab_cols = (19222 + 31) // 32 * 32 if spec.n_hidden == 130 and spec.in_features == 2 else None   # Cfg<130,2>::SL_COLS (icnn_step.h), rows on 128-byte lines
+        survey_bytes = 12 * N * B                                   # <= 8 B grid + 4 B target per point
+        design_bytes = None
+        if slab_cols is not None:
+            design_bytes = 4 * N * B + B * wgs * slab_cols * 4 + 8 * 77 * 1024   # targets + slabs + the parameter image once per XCD
+        # what a launch of nothing but independent fp32 MFMAs on all 1024 SIMDs reaches on the GPU in use (~2.1 GHz under that load instead
+        # of the 2.4 GHz the nominal peak assumes): the practical ceiling, reported next to `peak`, never instead of it
+        mfma_stream = A.icnn.mfma_stream_tflops(dev)
+        roofline = {"bound": "mfma", "achieved": round(achieved, 3), "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(achieved / PEAK_FP32_MATRIX_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                    "algorithmic_bytes": design_bytes, "survey_bytes_per_launch": survey_bytes,
+                    "traffic_over_algorithmic": round(traffic / design_bytes, 3) if traffic and design_bytes else None,
+                    "traffic_over_survey_bytes": round(traffic / survey_bytes, 1) if traffic else None,
+                    "kernel": "icnn_step_kernel<130,2,train>", "kernel_us": round(kernel_ms * 1e3, 2),
+                    "kernel_samples": seq.samples, "kernel_us_back_to_back": round(kernel_b2b_ms * 1e3, 2),
+                    "update_kernel_us": round(update_us, 2), "event_bracket_excess_us": round(excess, 2),
+                    "flop_per_launch": flop_per_launch, "mfma_only_stream_tflops": round(mfma_stream, 1),
+                    "frac_of_mfma_only_stream": round(achieved / mfma_stream, 4)}
 
     # ---- which devices the ranks sat on: (rank, local rank, PCI bus id / uuid, the backend's world size), gathered so that the
     # driver's record can show that the N-rank line came from N distinct GPUs over RCCL -------------------------------------
@@ -322,7 +340,7 @@ def main():
     # image i of rank r = configs[2]'s image r*TB + i: blob seed s, initial weights torch.manual_seed(s) + the reference's default
     # init - so that the first images coincide with the reference classes' own fits in tests/golden/fits_blob256_multi_{a,b}.npz
     thr = None
-    if args.throughput_images > 0:
+    if args.full and args.throughput_images > 0:
         TB = args.throughput_images
         tseeds = [rank * TB + i for i in range(TB)]
         tun = torch.stack([convex_blob_unaries(S, s).reshape(-1) for s in tseeds]).to(dev)
@@ -353,7 +371,7 @@ def main():
     # the last rank's remainder batch, the per-batch launch shapes (fewer images per launch = more gradient slabs per image) and
     # the barrier show up in it.
     strong = None
-    if args.strong_images > 0:
+    if args.full and args.strong_images > 0:
         from awesome_amd import parallel as PAR
         total, DB = args.strong_images, max(1, args.throughput_images or 64)
         mine = list(PAR.shard_range(total, rank, world))
@@ -393,7 +411,7 @@ def main():
     # fixture tests/golden/fit_blob256_reference.npz (tools/gen_golden.py gen_fit_blob256: same seeds, E = 2000, 256x256)
     reference_parity = {}
     fx = os.path.join(ROOT, "tests", "golden", "fit_blob256_reference.npz")
-    if rank == 0 and S == 256 and E == 2000 and os.path.exists(fx):
+    if args.full and rank == 0 and S == 256 and E == 2000 and os.path.exists(fx):
         import numpy as np
         z = np.load(fx)
         mask0 = (prob[0] > 0.5).cpu().numpy().reshape(-1)
@@ -422,23 +440,51 @@ def main():
                                    f"SE(sigmoid) mean, Adam lr 2e-3, clamp, E={E} full-batch steps (BASELINE configs[1])",
                        "images_per_gpu": B, "grid": f"{S}x{S}", "epochs_per_fit": E, "parallelism": f"dp{world} (independent fits)"},
             "miou_vs_unaries": round(miou, 5), "nonfinite_fits": status_bad, **reference_parity, **determinism,
-            "us_per_optimizer_step": round(elapsed / args.steps / E * 1e6, 2),
-            "roofline": roofline,
+            "us_per_optimizer_step": round(elapsed / args.steps / E * 1e6, 2), "full": args.full,
             "placements": placements,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if thr is not None:
             out["throughput_mode"] = thr
         if strong is not None:
             out["strong_scaling_configs2"] = strong
-        if world == 1 and not args.no_variants:
+        if args.full and world == 1 and not args.no_variants:
             out["variants"] = path_variants(dev, S, cpu_legs=not args.no_variant_cpu)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, init[0].cpu(), unaries[0].cpu(), spec)
             out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)
     if dist is not None:
         barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, seeds):
+    """--dump-outputs: what a caller of the timed path receives from its last fit (A.fit's FitResult: final parameters, logits at the
+    final parameters, status, and the computed part of the optimizer state - Adam's two moment vectors and the last loss), one
+    float32 .npy per array with one row per image, and the blob seed of every row (image_seeds.npy, float64).  The rest of the
+    state header (include/inrfit.h: lr double buffer, flags, the plateau sentinel, +inf while no plateau schedule runs) is
+    bookkeeping, not a result.  Inputs are seeded, so two builds run with the same arguments can be compared file by file.
+    Above 64 MB in all, a fixed (seed 0) sample of the images is written, in ascending order."""
+    import numpy as np
+    P = res.params.shape[1]
+    st = res.opt_state
+    arrays = {"params": res.params, "logits": res.logits, "status": res.status, "adam_exp_avg": st[:, :P],
+              "adam_exp_avg_sq": st[:, P:2 * P], "last_loss": st[:, 2 * P + 5]}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}      # status: int32 0 / 1, exact in float32
+    arrays["image_seeds"] = np.asarray(seeds, dtype=np.float64)
+    n = len(seeds)
+    rows = np.arange(n)
+    per_image = sum(a[:1].nbytes for a in arrays.values())
+    if per_image * n > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, max(1, DUMP_LIMIT_BYTES // per_image), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a[rows]))
 
 
 def miou_delta_vs_reference(seeds, iou, masks):

@@ -89,15 +89,21 @@ def test_fbms_joint_loss_matches_reference(golden_dir):
 
 @pytest.mark.parametrize("tag", ["l2_w130_k6", "l1_w24_k4"])
 def test_cdn_translate_matches_reference(golden_dir, tag):
-    """ConvexDiffeomorphismNet.translate_only_point (the centre-of-mass warm start): same new linear layer as the class."""
+    """ConvexDiffeomorphismNet.translate_only_point (the centre-of-mass warm start): same new linear layer as the class.  Compared
+    in float64 (the class's own solve in float64: cdn_class_translate_f64.npz): the fp32 least-squares solve of three points
+    (condition number ~900) ends ~1e-4 apart on two BLAS builds, in float64 ~1e-13."""
     from awesome_amd.model.diffeomorphism_net import translate_linear, translate_only_point_args
     z = _z(golden_dir, f"cdn_class_{tag}.npz")
-    w0, b0 = torch.from_numpy(z["sd.linear.weight"]), torch.from_numpy(z["sd.linear.bias"])
-    grid = torch.from_numpy(z["grid"])
+    zf = _z(golden_dir, "cdn_class_translate_f64.npz")
+    np.testing.assert_array_equal(zf[f"{tag}.sd.linear.weight"], z["sd.linear.weight"].astype(np.float64))   # same net
+    np.testing.assert_array_equal(zf[f"{tag}.sd.linear.bias"], z["sd.linear.bias"].astype(np.float64))
+    w0, b0 = torch.from_numpy(z["sd.linear.weight"]).double(), torch.from_numpy(z["sd.linear.bias"]).double()
+    grid = torch.from_numpy(z["grid"]).double()
     pts = translate_only_point_args(torch.from_numpy(z["tr_src"]), torch.from_numpy(z["tr_dst"]), grid.squeeze(), 2)
     w1, b1 = translate_linear(w0, b0, *pts)
-    np.testing.assert_allclose(w1.numpy(), z["sd_tr.linear.weight"], rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(b1.numpy(), z["sd_tr.linear.bias"], rtol=1e-5, atol=1e-6)
+    assert w1.dtype == b1.dtype == torch.float64
+    np.testing.assert_allclose(w1.numpy(), zf[f"{tag}.sd_tr.linear.weight"], rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(b1.numpy(), zf[f"{tag}.sd_tr.linear.bias"], rtol=1e-9, atol=1e-12)
     # and nothing else moved
     for k in z.files:
         if k.startswith("sd_tr.") and not k.startswith("sd_tr.linear."):
@@ -144,14 +150,16 @@ def test_oracle_encode_stage_matches_the_notebook_classes(golden_dir):
                 name = k[len(tag) + 6:]
                 np.testing.assert_allclose(sd[name].grad.numpy(), z[k], rtol=1e-4, atol=1e-8, err_msg=k)
     # the generic form the kernels are checked against (icnn_forward with act0) IS that arithmetic: same features, same first layer
-    sd = {k[11:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("fourier.sd.")}
-    x = torch.from_numpy(z["fourier.x"])
+    # (in float64: x @ A + b and linear(x, A^T, b) are two BLAS calls whose fp32 roundings of the arguments (~1e2) differ by an ulp
+    # on some BLAS builds, ~4e-6 after the cosine)
+    sd = {k[11:]: torch.from_numpy(z[k]).double() for k in z.files if k.startswith("fourier.sd.")}
+    x = torch.from_numpy(z["fourier.x"]).double()
     feats = torch.cos(x @ sd["A"] + sd["b"])
     np.testing.assert_allclose(O.encode_layer(torch.nn.functional.linear(x, sd["A"].t(), sd["b"]), "cos").numpy(), feats.numpy(), rtol=1e-6, atol=1e-6)
     p = {"input.weight": sd["A"].t().contiguous(), "input.bias": sd["b"],
          "skip.0.ln.weight": torch.nn.functional.pad(sd["fc1.weight"], (0, 0, 0, 0))[:20, :], "skip.0.ln.bias": sd["fc1.bias"][:20],
-         "skip.0.skp.weight": torch.zeros(20, 2), "out.ln.weight": torch.ones(1, 20), "out.ln.bias": torch.zeros(1),
-         "out.skp.weight": torch.zeros(1, 2)}
+         "skip.0.skp.weight": torch.zeros(20, 2, dtype=x.dtype), "out.ln.weight": torch.ones(1, 20, dtype=x.dtype),
+         "out.ln.bias": torch.zeros(1, dtype=x.dtype), "out.skp.weight": torch.zeros(1, 2, dtype=x.dtype)}
     ref = torch.relu(torch.nn.functional.linear(feats, sd["fc1.weight"][:20], sd["fc1.bias"][:20])).sum(1, keepdim=True)
     np.testing.assert_allclose(O.icnn_forward(p, x, act0="cos").numpy(), ref.numpy(), rtol=1e-5, atol=1e-5)
     sds = {k[8:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sine.sd.")}

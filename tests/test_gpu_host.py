@@ -329,3 +329,43 @@ def test_prior_bank_joint_step_and_prefit(golden_dir):
     expect = A.fit(model.spec, bank.rows([1, 2]).contiguous(), grid, un, 50, lr=2e-3).params
     bank.fit([1, 2], grid, un, 50, lr=2e-3)
     assert torch.equal(bank.rows([1, 2]), expect)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_fit(dev, tmp_path):
+    """`bench.py` without --full: the headline line only (`--steps` timed fits, `ms_per_step` one of them, nothing of --full's
+    entries), and --dump-outputs writes what the timed path returned in its last fit - the same bits as a direct call of that
+    path on the same seeded inputs."""
+    import awesome_amd as A
+    from awesome_amd.dataset import convex_blob_unaries
+    from awesome_amd.model import ConvexNextNet
+    S, E, seeds = 64, 50, [0, 1]
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", str(S),
+                        "--epochs", str(E), "--images-per-gpu", str(len(seeds)), "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["unit"] == "fits/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["value"] > 0
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["ms_per_step"] == pytest.approx(1e3 * len(seeds) / line["value"], rel=2e-3)
+    assert not {"roofline", "variants", "cpu_baseline", "throughput_mode", "strong_scaling_configs2"} & set(line)
+    names = ("params", "logits", "status", "adam_exp_avg", "adam_exp_avg_sq", "last_loss", "image_seeds")
+    assert sorted(os.listdir(out_dir)) == sorted(f"{k}.npy" for k in names)
+    got = {k: np.load(out_dir / f"{k}.npy") for k in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    np.testing.assert_array_equal(got["image_seeds"], np.asarray(seeds, np.float64))
+    spec = A.IcnnSpec(130, 2, 1)
+    un = torch.stack([convex_blob_unaries(S, s).reshape(-1) for s in seeds]).to(dev)
+    init = []
+    for s in seeds:
+        torch.manual_seed(s)
+        init.append(ConvexNextNet(n_hidden=130, in_features=2, n_hidden_layers=1).flat_parameters())
+    res = A.fit(spec, torch.stack(init).to(dev), A.Grid.linspace(S, S, dev), un, E, lr=2e-3, loss="se", optimizer="adam", clamp=True,
+                record_loss=False, want_logits=True)
+    P = spec.n_params
+    want = {"params": res.params, "logits": res.logits, "status": res.status, "adam_exp_avg": res.opt_state[:, :P],
+            "adam_exp_avg_sq": res.opt_state[:, P:2 * P], "last_loss": res.opt_state[:, 2 * P + 5]}
+    for k, v in want.items():
+        np.testing.assert_array_equal(got[k], v.float().cpu().numpy(), err_msg=k)

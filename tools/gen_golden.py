@@ -299,12 +299,13 @@ def gen_fit_blob256(ref, out, layers=1, name="fit_blob256_reference"):
     print("wrote", name, ": loss", losses[0], "->", losses[-1], "miou", rec["final_miou"])
 
 
-def gen_cdn_fit(ref, out):
+def gen_cdn_fit(ref, out, dtype=torch.float32, name="cdn_fit48"):
     """The path-connected prior end to end with the reference's own modules: ConvexNextNet(130, L=2) behind
     NormalizingFlow1D(6 couplings, width 130, normal_block) behind nn.Linear(2, 2) - composed exactly as
     ConvexDiffeomorphismNet.forward does (convex_diffeomorphism_net.py:173-178; the class itself needs `toml` to import) - and
     trained like its pretrain loop (:405-430): Adam over get_weight_normalized_param_groups(5e-5), lr 3e-3, BCE on the sigmoid,
-    enforce_convexity; 300 steps on a 48x48 two-disc shape."""
+    enforce_convexity; 300 steps on a 48x48 two-disc shape.  dtype=torch.float64 (cdn_fit48_f64.npz): the same initial
+    parameters and problem in double precision, a trajectory that does not depend on the host's BLAS kernels."""
     T = ref.transformator.Transformator
     seed_all(4)
     convex_net = ref.convex_net.ConvexNextNet(n_hidden=130, in_features=2, n_hidden_layers=2)
@@ -312,13 +313,13 @@ def gen_cdn_fit(ref, out):
     linear = torch.nn.Linear(2, 2)
     linear.weight.data.normal_(0.0, 1 / np.sqrt(2))
     linear.bias.data.fill_(0)
-    net = torch.nn.ModuleDict(dict(convex_net=convex_net, diffeo_net=diffeo_net, linear=linear))
+    net = torch.nn.ModuleDict(dict(convex_net=convex_net, diffeo_net=diffeo_net, linear=linear)).to(dtype)
     S = 48
     yy, xx = np.mgrid[0:S, 0:S]
     mask = (((yy - 16) ** 2 + (xx - 14) ** 2) < 60) | (((yy - 32) ** 2 + (xx - 32) ** 2) < 60) | \
            ((np.abs(yy - 16) < 3) & (xx >= 14) & (xx <= 32)) | ((np.abs(xx - 32) < 3) & (yy >= 16) & (yy <= 32))
-    unaries = torch.from_numpy(1.0 - mask.astype(np.float32))[None, None]
-    grid = T.get_positional_matrices(S, S)[None]
+    unaries = torch.from_numpy(1.0 - mask.astype(np.float32))[None, None].to(dtype)
+    grid = T.get_positional_matrices(S, S)[None].to(dtype)
     rows = grid.permute(0, 2, 3, 1).reshape(-1, 2)
 
     def forward():
@@ -338,11 +339,12 @@ def gen_cdn_fit(ref, out):
         losses.append(loss.item())
     with torch.no_grad():
         logits = forward()
-    rec["losses"] = np.asarray(losses, dtype=np.float32)
-    rec["final_logits"] = logits.numpy().astype(np.float32)
+    np_dtype = np.float64 if dtype == torch.float64 else np.float32
+    rec["losses"] = np.asarray(losses, dtype=np_dtype)
+    rec["final_logits"] = logits.numpy().astype(np_dtype)
     rec.update(sd_np(net, "final."))
-    np.savez_compressed(os.path.join(out, "cdn_fit48.npz"), **rec)
-    print("wrote cdn_fit48: loss", losses[0], "->", losses[-1])
+    np.savez_compressed(os.path.join(out, name + ".npz"), **rec)
+    print("wrote", name, ": loss", losses[0], "->", losses[-1])
 
 
 def gen_flow(ref, out):
@@ -454,6 +456,8 @@ def main():
     ref = _import_reference()
     if args.only == "fit_blob256_l2":
         return gen_fit_blob256(ref, out, layers=2, name="fit_blob256_l2_reference")
+    if args.only == "cdn_fit_f64":
+        return gen_cdn_fit(ref, out, dtype=torch.float64, name="cdn_fit48_f64")
     gen_grid(ref, out)
     gen_miou(ref, out)
     gen_losses(ref, out)
@@ -464,6 +468,7 @@ def main():
     gen_fit_blob256(ref, out)
     gen_fit_blob256(ref, out, layers=2, name="fit_blob256_l2_reference")
     gen_cdn_fit(ref, out)
+    gen_cdn_fit(ref, out, dtype=torch.float64, name="cdn_fit48_f64")
     gen_minmax(ref, out)
     gen_pixel_losses(ref, out)
     gen_fcnet(ref, out)

@@ -107,6 +107,29 @@ def gen_cdn_class(ref, out):
         print("cdn_class", tag, float(loss))
 
 
+def gen_cdn_translate_f64(ref, out):
+    """translate_only_point of gen_cdn_class's two nets in double precision (cdn_class_translate_f64.npz): the same initial
+    parameters, points and grid, the class's least-squares solve in float64.  The fp32 solve (X^T X of three points, condition
+    number ~900) rounds differently with every BLAS kernel; in float64 the result does not depend on the host."""
+    import copy
+    rec = {}
+    for tag, kw, hw in (("l2_w130_k6", dict(n_hidden=130, n_hidden_layers=2, nf_layers=6, nf_hidden=130,
+                                            diffeo_args=dict(backbone="normal_block")), (24, 20)),
+                        ("l1_w24_k4", dict(n_hidden=64, n_hidden_layers=1, nf_layers=4, nf_hidden=24), (16, 16))):
+        seed_all(21)
+        m = ref.cdn.ConvexDiffeomorphismNet(**copy.deepcopy(kw)).double()
+        grid = linspace_grid(*hw).double()
+        rec.update({f"{tag}.sd.linear.weight": m.linear.weight.detach().numpy().copy(),
+                    f"{tag}.sd.linear.bias": m.linear.bias.detach().numpy().copy()})
+        src = torch.tensor([7, 9], dtype=torch.long)     # = gen_cdn_class
+        dst = torch.tensor([10, 6], dtype=torch.long)
+        m.translate_only_point(src, dst, grid=grid.squeeze())
+        rec.update({f"{tag}.sd_tr.linear.weight": m.linear.weight.detach().numpy().copy(),
+                    f"{tag}.sd_tr.linear.bias": m.linear.bias.detach().numpy().copy()})
+        print("cdn_translate_f64", tag, rec[f"{tag}.sd_tr.linear.bias"])
+    np.savez_compressed(os.path.join(out, "cdn_class_translate_f64.npz"), **rec)
+
+
 def gen_cdn_class_resnet(ref, out):
     """ConvexDiffeomorphismNet with NormalizingFlow1D's 'resnet' backbone (SimpleResnet: diffeomorphism_net.py:107-166, 256-260; no
     config selects it): forward on a (1,2,H,W) grid, the deformation, BCE(sigmoid) loss gradients w.r.t. every parameter."""
@@ -443,6 +466,8 @@ def main():
         return gen_weighted_loss_noneclass(ref, args.out)
     if args.only == "cdn_resnet":
         return gen_cdn_class_resnet(ref, args.out)
+    if args.only == "cdn_translate_f64":
+        return gen_cdn_translate_f64(ref, args.out)
     gen_weighted_loss_noneclass(ref, args.out)
     gen_wrapper_pixel(ref, args.out)
     gen_encode_notebooks(args.out)
@@ -452,6 +477,7 @@ def main():
     gen_wrapper(ref, args.out)
     gen_prior_cache(ref, args.out)
     gen_cdn_class(ref, args.out)
+    gen_cdn_translate_f64(ref, args.out)
     gen_cdn_class_resnet(ref, args.out)
 
 

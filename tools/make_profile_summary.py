@@ -46,7 +46,7 @@ def main():
     R = f"r{rnd:02d}"
     if os.path.exists(os.path.join(SRC, "bench_line.json")):
         shutil.copy(os.path.join(SRC, "bench_line.json"), os.path.join(DST, f"{R}_{tag}_bench_line.json"))
-    for src, name, cmd in (("bench", "bench", "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --strong-images 0 --no-variants --throughput-images 0"),
+    for src, name, cmd in (("bench", "bench", "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --strong-images 0 --no-variants --throughput-images 0"),
                            ("pcn", "pcn_fit", "python3 tools/kbench_pcn.py --steps 200"), ("cdn", "cdn_fit", "python3 tools/kbench_cdn.py"),
                            ("joint", "joint_step", "python3 tools/kbench_joint.py")):
         if not os.path.exists(os.path.join(SRC, f"{src}_kernel_stats.csv")):
@@ -76,7 +76,7 @@ def step_kernel_summary(tag, rnd, R):
     life = 4 * s["SQ_WAVE_CYCLES"] / waves_per_se
     rec = {
         "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE | --pmc SQ_* (three separate passes, no trace domain besides the counters) -- "
-                   "python3 bench.py --steps 1 --warmup 0 --epochs 50 --kernel-iters 20 --no-cpu-baseline --throughput-images 0 --no-variants",
+                   "python3 bench.py --full --steps 1 --warmup 0 --epochs 50 --kernel-iters 20 --no-cpu-baseline --throughput-images 0 --no-variants",
         "round": rnd, "kernel": "icnn_step_kernel<130,2,train,relu>", "workload": "1 x 256x256, 256 workgroups x 4 waves",
         "kernel_avg_us_rocprofv3_kernel_trace": round(avg_ns / 1e3, 2),
         "FETCH_SIZE_KB_mean": f_kb, "WRITE_SIZE_KB_mean": w_kb,

@@ -19,7 +19,7 @@ summ_pmc() {   # dir tag
   if [ -n "$csv" ]; then python3 tools/pmc_summary.py "$csv" > $O/$2.txt; else python3 tools/pmc_summary_db.py "$db" > $O/$2.txt; fi
   rm -rf $1
 }
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 if [ "$1" != "pmc" ]; then
 echo "== bench line $(date +%T)"; timeout -k 10 300 $B > $O/bench_line.json 2> $O/bench_line.err || exit 1
 echo "== kernel stats of the bench command $(date +%T)"
@@ -32,7 +32,7 @@ echo "== kernel stats of the CDN fit $(date +%T)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_cdn -o cdn -- python3 tools/kbench_cdn.py > $O/stats_cdn.log 2>&1 || exit 1
 summ_stats $O/stats_cdn cdn
 fi
-S="python3 bench.py --steps 1 --warmup 0 --epochs 50 --kernel-iters 20 --no-cpu-baseline --throughput-images 0 --no-variants"
+S="python3 bench.py --full --steps 1 --warmup 0 --epochs 50 --kernel-iters 20 --no-cpu-baseline --throughput-images 0 --no-variants"
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $c (bench) $(date +%T)"; timeout -k 10 300 rocprofv3 --pmc $c -d $O/pmc_$c -o p -- $S > $O/pmc_$c.log 2>&1 || exit 1
   ls -R $O/pmc_$c | head; summ_pmc $O/pmc_$c bench_pmc_$c

@@ -19,7 +19,7 @@ summ_pmc() {   # dir tag
   if [ -n "$csv" ]; then python3 tools/pmc_summary.py "$csv" > $O/$2.txt; else python3 tools/pmc_summary_db.py "$db" > $O/$2.txt; fi
   rm -rf $1
 }
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --strong-images 0"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --strong-images 0"
 if [ "$MODE" = "stats" ] || [ "$MODE" = "all" ]; then
 echo "== kernel stats of the bench command $(date +%T)"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats_bench -o bench -- $B --no-variants --throughput-images 0 > $O/stats_bench.log 2>&1 || exit 1
@@ -41,7 +41,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_cdn -o cdn -- pyt
 summ_stats $O/stats_cdn cdn
 fi
 if [ "$MODE" = "pmc" ] || [ "$MODE" = "all" ]; then
-S="python3 bench.py --steps 1 --warmup 0 --epochs 50 --kernel-iters 20 --no-cpu-baseline --throughput-images 0 --no-variants --strong-images 0"
+S="python3 bench.py --full --steps 1 --warmup 0 --epochs 50 --kernel-iters 20 --no-cpu-baseline --throughput-images 0 --no-variants --strong-images 0"
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $c (bench) $(date +%T)"; timeout -k 10 300 rocprofv3 --pmc $c -d $O/pmc_$c -o p -- $S > $O/pmc_$c.log 2>&1 || exit 1
   summ_pmc $O/pmc_$c bench_pmc_$c
