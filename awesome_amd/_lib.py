@@ -15,7 +15,7 @@ INR_LOSS_SE, INR_LOSS_BCE = 0, 1
 INR_WEIGHT_NONE, INR_WEIGHT_EQUAL, INR_WEIGHT_RATIO, INR_WEIGHT_SSSDMS, INR_WEIGHT_EXPLICIT = 0, 1, 2, 3, 4
 INR_OPT_ADAM, INR_OPT_ADAMAX = 0, 1
 INR_OPT_HEADER_FLOATS = 8
-INRFIT_ABI_VERSION = 7
+INRFIT_ABI_VERSION = 8
 INR_ACT_RELU, INR_ACT_COS, INR_ACT_SIN = 0, 1, 2
 ACT_KINDS = {"relu": INR_ACT_RELU, "cos": INR_ACT_COS, "sin": INR_ACT_SIN}
 INR_FLOW_NORMAL_BLOCK, INR_FLOW_SIMPLE = 0, 1
@@ -29,7 +29,8 @@ OPT_KINDS = {"adam": INR_OPT_ADAM, "adamax": INR_OPT_ADAMAX}
 
 class InrModelDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_hidden", C.c_int32), ("in_features", C.c_int32), ("n_layers", C.c_int32),
-                ("act0", C.c_int32), ("act_omega", C.c_float)]
+                ("act0", C.c_int32), ("act_omega", C.c_float),
+                ("n_features", C.c_int32), ("n_out", C.c_int32)]   # ABI v8 (zero tail = v7 meaning: n_features = n_hidden, one output)
 
 
 class InrGridDesc(C.Structure):

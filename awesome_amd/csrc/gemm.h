@@ -62,7 +62,8 @@ struct GemmArgs {
     const float* skip;     // HIDDEN: S [N][C]
     const float* ext;      // HIDDEN: x_c of row m = ext[m * ext_ld + 1 + c] (the ext columns (1, x) of the previous layer's activations)
     int ext_ld, C_in;
-    int ext_copy;          // HIDDEN: also C[m][N .. N + ext_copy) = ext[m][0 .. ext_copy) (the ext columns and padding of the activation rows travel along)
+    int ext_copy;          // HIDDEN: also C[m][N .. N + ext_copy) = ext[m][0 .. 1 + C_in), then zeros (the ext columns of the activation rows
+                           // travel along; the row's padding is written as zeros whatever the padding of the row below is)
     const float* mask;     // MASK: multiply by [mask[m * mask_ld + n] > 0] (mask_act == relu) or by the activation's derivative at it
     int mask_ld, mask_act;
     float omega;
@@ -402,7 +403,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE ? GM_W
     if (EPI == GEMM_EPI_HIDDEN && a.ext_copy > 0 && bx == (int)gridDim.x - 1 && tid < GM_BM && m0 + tid < a.M) {
         const float* src = a.ext + (size_t)(m0 + tid) * a.ext_ld;
         float* dst = Cz + (size_t)(m0 + tid) * a.ldc + a.N;
-        for (int c = 0; c < a.ext_copy; ++c) dst[c] = src[c];
+        for (int c = 0; c < a.ext_copy; ++c) dst[c] = c <= a.C_in ? src[c] : 0.f;   // (1, x), then zeros: the padding of this row
     }
     if (!TA && !TB && a.extsum) {
         // the column sums of the tile: lanes that share a column (4 row groups g, 2 waves wm) through LDS, added in a fixed order

@@ -513,6 +513,7 @@ const KernelEntry kEntries[] = {
 // the kernel a model runs on: its own shape if compiled, else the smallest compiled width above it (zero-padded, user_param_index)
 const KernelEntry* find_entry(const InrModelDesc* m) {
     if (!m || m->kind != INR_MODEL_ICNN || m->n_hidden < 1) return nullptr;
+    if (m->n_features < 0 || m->n_out < 0 || wide_desc_general(m)) return nullptr;   // own feature width / several outputs / no hidden layer
     const KernelEntry* best = nullptr;
     for (const auto& e : kEntries)
         if (e.c == m->in_features && e.l == m->n_layers && e.h >= m->n_hidden && (!best || e.h < best->h)) best = &e;
@@ -646,11 +647,13 @@ int inrfit_query(int* abi_version, int* max_hidden, int* lds_bytes) {
     return INR_OK;
 }
 
+#define INRFIT_STR_(x) #x
+#define INRFIT_STR(x) INRFIT_STR_(x)
 #ifndef INRFIT_BUILD_FLAGS
 #define INRFIT_BUILD_FLAGS "unknown (not built by awesome_amd/build.py)"
 #endif
 const char* inrfit_build_info(void) {
-    return "libinrfit abi " "6" "; gfx950; slab_base 256; " __VERSION__ "; flags: " INRFIT_BUILD_FLAGS;
+    return "libinrfit abi " INRFIT_STR(INRFIT_ABI_VERSION) "; gfx950; slab_base 256; " __VERSION__ "; flags: " INRFIT_BUILD_FLAGS;
 }
 
 int inrfit_debug_set_slab_base(int slab_base) {
@@ -668,8 +671,11 @@ int inrfit_supported(const InrModelDesc* model) { return (find_entry(model) || w
 
 int64_t inrfit_param_count(const InrModelDesc* m) {
     if (!m || m->kind != INR_MODEL_ICNN || m->n_hidden <= 0 || m->in_features <= 0 || m->n_layers < 0) return INR_EINVAL;
-    const int64_t h = m->n_hidden, c = m->in_features, l = m->n_layers;
-    return h * c + h + l * (h * h + h + h * c) + h + 1 + c;
+    if (m->n_features < 0 || m->n_features > WIDE_MAX_HIDDEN || m->n_out < 0 || m->n_out > 4) return INR_EINVAL;
+    // W_in [F][C], b_in [F] | W_0 [h][F], b_0, S_0 | W_k [h][h], b_k, S_k (k >= 1) | W_o [O][h or F], b_o [O], S_o [O][C]
+    const int64_t h = m->n_hidden, c = m->in_features, l = m->n_layers, f = wide_desc_F(m), o = wide_desc_O(m);
+    const int64_t hidden = l > 0 ? (h * f + h + h * c) + (l - 1) * (h * h + h + h * c) : 0;
+    return f * c + f + hidden + o * (l > 0 ? h : f) + o + o * c;
 }
 
 int64_t inrfit_opt_state_floats(const InrModelDesc* m) {
@@ -681,8 +687,7 @@ int64_t inrfit_workspace_bytes(const InrModelDesc* model, const InrGridDesc* gri
     const KernelEntry* e = find_entry(model);
     if (!e && wide_shape_ok(model)) {
         if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
-        return wide_total_bytes(make_wide_map(model->n_hidden, model->in_features, model->n_layers), grid->n_points,
-                                model->act0 != INR_ACT_RELU, n_images);
+        return wide_total_bytes(make_wide_map(model), grid->n_points, model->act0 != INR_ACT_RELU, n_images);
     }
     if (!e) return INR_EUNSUPPORTED;
     if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
@@ -824,7 +829,8 @@ static void launch_reduce(const KernelEntry* e, const Workspace& w, int n_images
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the layer-by-layer path (wide.h): shapes without a fused kernel - n_hidden > 130 or more than two hidden layers
+// the layer-by-layer path (wide.h): shapes without a fused kernel - n_hidden > 130, more than two hidden layers, or a general shape
+// (n_features != n_hidden, n_out > 1, no hidden layer)
 // ---------------------------------------------------------------------------------------------------------------------
 static bool use_wide(const InrModelDesc* m) { return find_entry(m) == nullptr && wide_shape_ok(m); }
 
@@ -837,7 +843,7 @@ static int wide_prepare(const InrModelDesc* model, const InrGridDesc* grid, int 
         return INR_EINVAL;
     }
     if (model->act0 < INR_ACT_RELU || model->act0 > INR_ACT_SIN) return INR_EINVAL;
-    *m = make_wide_map(model->n_hidden, model->in_features, model->n_layers);
+    *m = make_wide_map(model);
     const bool pre0 = model->act0 != INR_ACT_RELU;
     if (workspace_bytes < wide_total_bytes(*m, grid->n_points, pre0, n_images)) return INR_EWORKSPACE;
     *w = carve_wide(*m, grid->n_points, pre0, workspace);
@@ -854,7 +860,7 @@ static int wide_forward_all(const InrModelDesc* model, const float* params, cons
     int rc = wide_prepare(model, grid, n_images, workspace, workspace_bytes, &m, &w, &coef, s);
     if (rc) return rc;
     for (int img = 0; img < n_images; ++img)
-        if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, logits + (size_t)img * grid->n_points, s)))
+        if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, logits + (size_t)img * m.O * grid->n_points, s)))
             return rc;
     return INR_OK;
 }
@@ -868,14 +874,15 @@ static int wide_loss_grad_all(const InrModelDesc* model, const float* params, co
     float* coef;
     int rc = wide_prepare(model, grid, n_images, workspace, workspace_bytes, &m, &w, &coef, s);
     if (rc) return rc;
-    const long long N = grid->n_points;
-    if (loss->kind != INR_LOSS_EXTERNAL)
-        hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, coef);
+    const long long N = grid->n_points, ON = (long long)m.O * N;   // targets / dlogits: [n_images][O][N]
+    if (m.O > 1 && loss->weight_mode != INR_WEIGHT_NONE && loss->weight_mode != INR_WEIGHT_EXPLICIT) return INR_EINVAL;
+    if (loss->kind != INR_LOSS_EXTERNAL)   // ('mean' over the O x N elements: torch's MSELoss on (N, O))
+        hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef);
     for (int img = 0; img < n_images; ++img) {
         w.coef = coef + 2 * img;
         const float* p = params + (size_t)img * m.P;
-        if ((rc = wide_forward(m, w, model, p, grid, img, targets + (size_t)img * N, loss->kind, true, nullptr, s))) return rc;
-        if ((rc = wide_backward(m, w, model, p, N, s, targets + (size_t)img * N, dcoords ? dcoords + (size_t)img * m.C * N : nullptr))) return rc;
+        if ((rc = wide_forward(m, w, model, p, grid, img, targets + (size_t)img * ON, loss->kind, true, nullptr, s))) return rc;
+        if ((rc = wide_backward(m, w, model, p, N, s, targets + (size_t)img * ON, dcoords ? dcoords + (size_t)img * m.C * N : nullptr))) return rc;
         if (hipMemcpyAsync(grads_out + (size_t)img * m.P, w.grads, sizeof(float) * m.P, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
         if (loss_out && hipMemcpyAsync(loss_out + img, w.grads + m.P, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
     }
@@ -890,8 +897,9 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
     float* coef;
     int rc = wide_prepare(model, grid, n_images, workspace, workspace_bytes, &m, &w, &coef, s);
     if (rc) return rc;
-    const long long N = grid->n_points;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, coef);
+    const long long N = grid->n_points, ON = (long long)m.O * N;   // targets / logits: [n_images][O][N]
+    if (m.O > 1 && loss->weight_mode != INR_WEIGHT_NONE && loss->weight_mode != INR_WEIGHT_EXPLICIT) return INR_EINVAL;
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, m.P, *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
     // the optimizer step = icnn_update_kernel on a one-"slab" view of the gradient vector (column = parameter, column P = the loss)
@@ -910,12 +918,13 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
     u.slabs = w.grads;
     for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = u.freeze_lo[k] = u.freeze_hi[k] = 0;
     for (int k = 0; k < m.L; ++k) {
-        u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.h;
+        u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.kin(k);
         u.freeze_lo[k] = m.p_s(k); u.freeze_hi[k] = m.p_s(k) + m.h * m.C;
     }
-    u.clamp_lo[UPD_RANGES - 1] = m.p_wo(); u.clamp_hi[UPD_RANGES - 1] = m.p_wo() + m.h;
-    u.freeze_lo[UPD_RANGES - 1] = m.p_so(); u.freeze_hi[UPD_RANGES - 1] = m.p_so() + m.C;
-    u.input_hi = m.p_w(0);
+    u.clamp_lo[UPD_RANGES - 1] = m.p_wo(); u.clamp_hi[UPD_RANGES - 1] = m.p_wo() + m.O * m.hl();
+    u.freeze_lo[UPD_RANGES - 1] = m.p_so(); u.freeze_hi[UPD_RANGES - 1] = m.p_so() + m.O * m.C;
+    u.input_hi = m.p_w(0);   // input.weight | input.bias (L = 0: everything in front of the output layer)
+    const bool need_dz0 = !(m.general() && opt->freeze_input);   // frozen features: dZ_0 has no use
     const dim3 ugrid = upd_grid(m.P + 1, 1), ublock = upd_block(m.P + 1);
     const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
     for (int it = 0; it < steps; ++it) {
@@ -926,9 +935,9 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
         for (int img = 0; img < n_images; ++img) {
             float* p = params + (size_t)img * m.P;
             w.coef = coef + 2 * img;
-            if ((rc = wide_forward(m, w, model, p, grid, img, targets + (size_t)img * N, loss->kind, true,
-                                   gate_logits && it == steps - 1 ? final_logits + (size_t)img * N : nullptr, s))) return rc;
-            if ((rc = wide_backward(m, w, model, p, N, s))) return rc;
+            if ((rc = wide_forward(m, w, model, p, grid, img, targets + (size_t)img * ON, loss->kind, true,
+                                   gate_logits && it == steps - 1 ? final_logits + (size_t)img * ON : nullptr, s))) return rc;
+            if ((rc = wide_backward(m, w, model, p, N, s, nullptr, nullptr, need_dz0))) return rc;
             u.params = p;
             u.opt_state = opt_state + (size_t)img * (2 * (size_t)m.P + INR_OPT_HEADER_FLOATS);
             u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps : nullptr;
@@ -939,7 +948,7 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
     if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
     if (final_logits && !gate_logits)
         for (int img = 0; img < n_images; ++img)
-            if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, final_logits + (size_t)img * N, s))) return rc;
+            if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, final_logits + (size_t)img * ON, s))) return rc;
     return INR_OK;
 }
 

@@ -39,22 +39,39 @@ inline int wide_chunk(int h) {
 inline int splitk_parts(long long N, int h) { return (int)((N + wide_chunk(h) - 1) / wide_chunk(h)); }
 inline int out_parts(long long N) { return (int)((N + WIDE_OUT_CHUNK - 1) / WIDE_OUT_CHUNK); }
 
-// ---- flat parameter offsets for any (h, C, L) ---------------------------------------------------------------------------------------------
+// ---- flat parameter offsets for any (h, C, L, F, O) ----------------------------------------------------------------------------------------
+// F = n_features (the width of layer 0, the encode stage; h by default), O = n_out (output channels; 1 by default).  Layer k >= 1 and the
+// output layer read h units, hidden layer 0 reads the F features; with L = 0 the output layer reads the features directly.  F = h, O = 1
+// is the ICNN layout of include/inrfit.h.
 struct WideMap {
-    int h, C, L, P;
+    int h, C, L, P, F, O;
+    __host__ __device__ int kin(int k) const { return k == 0 ? F : h; }      // input width of hidden layer k
+    __host__ __device__ int hl() const { return L > 0 ? h : F; }             // width of the last activation (what the output layer reads)
     __host__ __device__ int p_win() const { return 0; }
-    __host__ __device__ int p_bin() const { return h * C; }
-    __host__ __device__ int p_w(int k) const { return h * C + h + k * (h * h + h + h * C); }
-    __host__ __device__ int p_b(int k) const { return p_w(k) + h * h; }
+    __host__ __device__ int p_bin() const { return F * C; }
+    __host__ __device__ int p_w(int k) const { return F * C + F + (k > 0 ? (h * F + h + h * C) + (k - 1) * (h * h + h + h * C) : 0); }
+    __host__ __device__ int p_b(int k) const { return p_w(k) + h * kin(k); }
     __host__ __device__ int p_s(int k) const { return p_b(k) + h; }
     __host__ __device__ int p_wo() const { return p_w(L); }
-    __host__ __device__ int p_bo() const { return p_wo() + h; }
-    __host__ __device__ int p_so() const { return p_bo() + 1; }
+    __host__ __device__ int p_bo() const { return p_wo() + O * hl(); }
+    __host__ __device__ int p_so() const { return p_bo() + O; }
+    // a shape the ICNN kernels never served: its own feature width, several outputs or no hidden layer (the notebooks' encode nets) -
+    // the layer-by-layer path with the multi-channel head (wide_head_kernel) and the output layer's gradient as a GEMM
+    __host__ __device__ bool general() const { return F != h || O != 1 || L == 0; }
 };
-inline WideMap make_wide_map(int h, int C, int L) {
-    WideMap m{h, C, L, 0};
-    m.P = m.p_so() + C;
+inline WideMap make_wide_map(int h, int C, int L, int F = 0, int O = 0) {
+    WideMap m{h, C, L, 0, F > 0 ? F : h, O > 0 ? O : 1};
+    m.P = m.p_so() + m.O * C;
     return m;
+}
+inline WideMap make_wide_map(const InrModelDesc* md) {
+    return make_wide_map(md->n_hidden, md->in_features, md->n_layers, md->n_features, md->n_out);
+}
+// packed copies of the hidden layers' weights: layer 0 [hq][Fq], layer k >= 1 [hq][hq] (h, F rounded up to 16, zero padded)
+inline __host__ __device__ int wide_q16(int n) { return (n + 15) / 16 * 16; }
+inline __host__ __device__ long long wide_wp_off(const WideMap& m, int k) {
+    const long long hq = wide_q16(m.h);
+    return k == 0 ? 0 : hq * wide_q16(m.F) + (long long)(k - 1) * hq * hq;
 }
 
 constexpr int WIDE_MAX_HIDDEN = 1024, WIDE_MAX_LAYERS = 8;
@@ -78,10 +95,13 @@ __global__ __launch_bounds__(256) void wide_layer0_kernel(InrGridDesc gd, int im
     const int nq = hs >> 2;
     if ((int)blockIdx.x >= pt_blocks) {   // the launch's last blocks: hidden-layer weights -> [L][hq][hq], hq = h rounded up to 16, zero padded:
                                           // whatever a k-step reads past h of the other operand meets a zero here (gemm.h, GemmArgs::buf)
-        const int hq = (pk.h + 15) / 16 * 16, per = hq * hq, e = (((int)blockIdx.x - pt_blocks) * gridDim.y + blockIdx.y) * 256 + threadIdx.x;
-        if (e < pk.L * per) {
-            const int k = e / per, r = e - k * per, i = r / hq, j = r - i * hq;
-            wp[e] = i < pk.h && j < pk.h ? params[pk.p_w(k) + i * pk.h + j] : 0.f;
+        // (layer 0 reads the F features: [hq][Fq], Fq = F rounded up to 16, first)
+        const int hq = wide_q16(pk.h), fq = wide_q16(pk.F), e0 = hq * fq, per = hq * hq;
+        const int e = (((int)blockIdx.x - pt_blocks) * gridDim.y + blockIdx.y) * 256 + threadIdx.x;
+        if (pk.L > 0 && e < e0 + (pk.L - 1) * per) {
+            const int k = e < e0 ? 0 : 1 + (e - e0) / per, r = e < e0 ? e : (e - e0) - (k - 1) * per;
+            const int ld = k == 0 ? fq : hq, kin = pk.kin(k), i = r / ld, j = r - i * ld;
+            wp[e] = i < pk.h && j < kin ? params[pk.p_w(k) + i * kin + j] : 0.f;
         }
         return;
     }
@@ -310,13 +330,145 @@ __global__ __launch_bounds__(256) void wide_out_kernel(const WideOutArgs a) {
     }
 }
 
+// The output layer of the general shapes (WideMap::general: n_out <= 4 channels, its own feature width, or no hidden layer), one pass per
+// WIDE_OUT_CHUNK points like wide_out_kernel, 16 lanes per point, 16 points per iteration:
+//   y_c = w_o[c] . z_L + b_o[c] + s_o[c] . x   -> logits [O][N];   TRAIN: sigmoid, the data term of every channel -> dy [N][4], the
+//   block's loss partial;  dZ_L[p][j] = (sum_c dy_c w_o[c][j]) (.) mask  with mask = [z_L > 0], or act0'(pre0) when the output layer reads
+//   the periodic features directly (L = 0, PER).
+// The row is walked twice (the dot products first, then dZ_L once dy is known; the second walk hits the cache) and the output weights sit
+// in LDS, so the registers do not grow with O x the row length.  The output layer's own gradient (dw_o | db_o | ds_o) = dY^T (Z_L | 1 | X)
+// is a small split-K GEMM over the points (wide_forward), the (1, x) sums of dZ_L are wide_extgrad_kernel's.
+struct WideHeadArgs {
+    const float* zl;        // [N][ls]: the hl units of the last activation, then (1, x), then zeros
+    const float* wo;        // [O][hl]
+    const float* sc;        // b_o [O], s_o [O][C]  (flat parameters at p_bo)
+    const float* pre;       // PER: [N][lp] pre-activation of layer 0
+    const float* target;    // [O][N] or null
+    const float* coef;      // c_fg, c_bg of this image
+    float* logits;          // [O][N] or null
+    float* dy;              // [N][4] dL/dy_c, zeros past O (train)
+    float* dz;              // [N][lp] (train)
+    float* lpart;           // [blocks] the blocks' loss partials (train)
+    long long N;
+    int hl, C, ls, lp, loss_kind, train, act;
+    float omega;
+};
+template <int O, bool PER>
+__global__ __launch_bounds__(256) void wide_head_kernel(const WideHeadArgs a) {
+    __shared__ __attribute__((aligned(16))) float sw[O][WIDE_OUT_MAXQ * 64];   // output weights, zeros past hl
+    __shared__ float sm[4];
+    const int tid = threadIdx.x, l15 = tid & 15, rg = tid >> 4;
+    const long long p0 = (long long)blockIdx.x * WIDE_OUT_CHUNK;
+    const int nq = (a.ls + 63) / 64, row = nq * 64;
+    for (int i = tid; i < O * row; i += 256) {
+        const int c = i / row, j = i - c * row;
+        sw[c][j] = j < a.hl ? a.wo[c * a.hl + j] : 0.f;
+    }
+    float bo[O], so[O][3];
+#pragma unroll
+    for (int c = 0; c < O; ++c) {
+        bo[c] = a.sc[c];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) so[c][i] = i < a.C ? a.sc[O + c * a.C + i] : 0.f;
+    }
+    __syncthreads();
+    float lsum = 0.f;
+    for (int it = 0; it < WIDE_OUT_CHUNK / 16; ++it) {
+        const long long p = p0 + it * 16 + rg;
+        const bool valid = p < a.N;
+        const float* zr = a.zl + (size_t)(valid ? p : 0) * a.ls;
+        float yp[O];
+#pragma unroll
+        for (int c = 0; c < O; ++c) yp[c] = 0.f;
+        for (int q = 0; q < nq; ++q) {
+            const int j = 64 * q + 4 * l15;
+            if (j < a.ls) {
+                const f32x4 z = *(const f32x4*)(zr + j);   // (ls is a multiple of 4)
+#pragma unroll
+                for (int c = 0; c < O; ++c) {
+                    const f32x4 w = *(const f32x4*)(&sw[c][j]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) yp[c] = fmaf(w[e], z[e], yp[c]);
+                }
+            }
+        }
+        float x[3] = {0.f, 0.f, 0.f};
+        for (int i = 0; i < a.C; ++i) x[i] = zr[a.hl + 1 + i];
+        float dyv[O], l = 0.f;
+#pragma unroll
+        for (int c = 0; c < O; ++c) {
+            float y = sum_over_points(yp[c]) + bo[c];   // (over the 16 lanes of the point: every lane has it)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) y = fmaf(so[c][i], x[i], y);   // (unused channels: 0 * x)
+            if (a.logits && valid && l15 == 0) a.logits[(size_t)c * a.N + p] = y;
+            float dy = 0.f;
+            if (a.train && valid) {
+                const float tg = a.target[(size_t)c * a.N + p];
+                if (a.loss_kind == INR_LOSS_EXTERNAL) {
+                    dy = tg;
+                } else {
+                    const float pr = 1.f / (1.f + expf(-y));
+                    const float cw = tg < 0.5f ? a.coef[0] : a.coef[1];
+                    if (a.loss_kind == INR_LOSS_SE) {
+                        const float d = tg - pr;
+                        l += d * d * cw;
+                        dy = 2.f * (pr - tg) * pr * (1.f - pr) * cw;
+                    } else {
+                        const float lp = bce_log(pr), lq = bce_log(1.f - pr);   // clamped at -100, NaN kept (torch.nn.BCELoss)
+                        l += -(tg * lp + (1.f - tg) * lq) * cw;
+                        const float pq = pr * (1.f - pr);
+                        dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
+                    }
+                }
+            }
+            dyv[c] = dy;
+        }
+        if (!a.train) continue;
+        if (l15 == 0) lsum += l;
+        if (!valid) continue;
+        if (l15 == 0) {
+            f32x4 d4 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < O; ++c) d4[c] = dyv[c];
+            *(f32x4*)(a.dy + (size_t)p * 4) = d4;
+        }
+        float* dr = a.dz + (size_t)p * a.lp;
+        const float* pr0 = PER ? a.pre + (size_t)p * a.lp : nullptr;
+        for (int q = 0; q < nq; ++q) {
+            const int j = 64 * q + 4 * l15;
+            if (j >= a.lp) continue;   // (lp <= ls: the row holds every column of dZ_L)
+            const f32x4 z = *(const f32x4*)(zr + j);
+            f32x4 d;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = 0.f;
+#pragma unroll
+                for (int c = 0; c < O; ++c) v = fmaf(dyv[c], sw[c][j + e], v);
+                if (PER) {
+                    const float pz = j + e < a.hl ? pr0[j + e] : 0.f;   // (pre0's padding columns are never written)
+                    v = j + e < a.hl ? v * (a.act == INR_ACT_COS ? -hw_sin(pz) : a.omega * hw_cos(a.omega * pz)) : 0.f;
+                } else {
+                    v = z[e] > 0.f ? v : 0.f;   // (w_o = 0 past hl: the padding columns get zeros)
+                }
+                d[e] = v;
+            }
+            *(f32x4*)(dr + j) = d;
+        }
+    }
+    if (!a.train) return;
+    const float v = sum_over_groups(sum_over_points(lsum));   // loss partial of the block: the 16 row groups in order
+    if ((tid & 63) == 0) sm[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0) a.lpart[blockIdx.x] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+}
+
 // dL/dcoords (an ICNN behind a learned deformation: convex_diffeomorphism_net.py:170-177): every pre-activation gradient dz [N][hp] the
 // backward pass produces contributes dz . Wx with Wx [h][C] = the weights the coordinates enter that layer with (S_k of a hidden layer,
 // W_in of layer 0); the output layer contributes s_o dL/dlogit (`init`: dx is started from it).  One pass over dz per layer, 16 lanes per
 // point; dx is planar [C][N] like the fused kernels' (icnn_step.h, DX).  Only the autograd bridge asks for it.
 __global__ __launch_bounds__(256) void wide_dx_kernel(const float* __restrict__ dz, int hp, const float* __restrict__ wx, int h, int C, long long N,
                                                       const float* __restrict__ dlogits, const float* __restrict__ so, float* __restrict__ dx,
-                                                      int init) {
+                                                      int init, int O = 1) {   // O output channels: dlogits [O][N], s_o [O][C]
     const int l15 = threadIdx.x & 15;
     const long long p = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool valid = p < N;
@@ -334,7 +486,9 @@ __global__ __launch_bounds__(256) void wide_dx_kernel(const float* __restrict__ 
     if (valid && l15 < C) {
         const float a = l15 == 0 ? acc[0] : (l15 == 1 ? acc[1] : acc[2]);
         float* o = dx + (size_t)l15 * N + p;
-        *o = (init ? so[l15] * dlogits[p] : *o) + a;
+        float b = init ? so[l15] * dlogits[p] : *o;
+        for (int c = 1; init && c < O; ++c) b += so[c * C + l15] * dlogits[(size_t)c * N + p];
+        *o = b + a;
     }
 }
 
@@ -383,6 +537,9 @@ __global__ __launch_bounds__(256) void wide_extgrad_kernel(const float* __restri
 //   mode 1 (layer 0, B = the ext columns):           column 0 -> b_in[i]; j >= 1 -> W_in[i][j - 1]
 //   mode 3 (hidden layer k, the ext columns only):   column 0 -> b_k[i];  j >= 1 -> S_k[i][j - 1]
 //   mode 2 (output layer, a = 1, b = hsv + 1):       column j < h -> w_o[j]; j == h -> b_o; h < j <= h + C -> s_o[j - h - 1]; the last -> the loss
+//   mode 4 (output layer of a general shape, a = O, b = hl + 1 + C): row c, column j < hl -> w_o[c][j]; j == hl -> b_o[c]; j > hl -> s_o[c][.]
+//   mode 5 (the loss, a = b = 1)
+// (mode 0 at layer k: the columns j < kin(k) are W_k - kin(0) = F)
 // (one launch takes up to two such reductions - e.g. a layer's weight-gradient partials and the (db | dS) partials its backward GEMM
 // left: the first j0.nblocks blocks serve the first)
 struct WideRedJob {
@@ -415,7 +572,10 @@ __global__ __launch_bounds__(1024) void wide_reduce_kernel(const WideRedJob j0, 
     for (int r = 1; r < 16; ++r) v += sm[r][el];
     const int i = e / b, j = e - i * b;
     int dst;
-    if (mode == 0) dst = j < m.h ? m.p_w(k) + i * m.h + j : (j == m.h ? m.p_b(k) + i : m.p_s(k) + i * m.C + (j - m.h - 1));
+    const int kin = m.kin(k), hl = m.hl();
+    if (mode == 0) dst = j < kin ? m.p_w(k) + i * kin + j : (j == kin ? m.p_b(k) + i : m.p_s(k) + i * m.C + (j - kin - 1));
+    else if (mode == 4) dst = j < hl ? m.p_wo() + i * hl + j : (j == hl ? m.p_bo() + i : m.p_so() + i * m.C + (j - hl - 1));
+    else if (mode == 5) dst = m.P;
     else if (mode == 3) dst = j == 0 ? m.p_b(k) + i : m.p_s(k) + i * m.C + (j - 1);
     else if (mode == 1) dst = j == 0 ? m.p_bin() + i : m.p_win() + i * m.C + (j - 1);
     else dst = j < m.h ? m.p_wo() + j : (j == m.h ? m.p_bo() : (j <= m.h + m.C ? m.p_so() + (j - m.h - 1) : m.P));   // (last column: the loss)
@@ -427,9 +587,10 @@ inline void wide_reduce(hipStream_t s, const WideMap& m, float* grads, WideRedJo
 
 // ---- workspace --------------------------------------------------------------------------------------------------------------------------
 struct WideWs {
-    float *z[WIDE_MAX_LAYERS + 1], *pre0, *dza, *dzb, *part, *part2, *grads, *coef, *wp;
-    int blocks;            // blocks of wide_out_kernel / wide_l0grad_kernel (WIDE_OUT_CHUNK points each)
-    int hs, hp, hsv;       // row length of the activations (multiple of 4), of the dz / pre0 buffers (multiple of 4), h + 1 + C
+    float *z[WIDE_MAX_LAYERS + 1], *pre0, *dza, *dzb, *part, *part2, *grads, *coef, *wp, *dy, *lpart;
+    int blocks;            // blocks of wide_out_kernel / wide_head_kernel (WIDE_OUT_CHUNK points each)
+    int hs, hp, hsv;       // row length of the activations (multiple of 4), of the dz buffers (multiple of 4), h + 1 + C
+    int fs, fp, fsv;       // the same for layer 0 (F features): z[0] rows, pre0 / dZ_0 rows, F + 1 + C  (= hs, hp, hsv when F = h)
     long long bytes;
 };
 
@@ -440,25 +601,30 @@ inline WideWs carve_wide(const WideMap& m, long long N, bool need_pre0, void* ba
     char* b = (char*)base;
     long long off = 0;
     auto take = [&](long long bytes) { float* p = (float*)(b + off); off += wide_align(bytes); return p; };
+    auto mx = [](long long x, long long y) { return x > y ? x : y; };
     w.blocks = out_parts(N);
     w.hsv = m.h + 1 + m.C;
     w.hs = (w.hsv + 3) / 4 * 4;
     w.hp = (m.h + 3) / 4 * 4;
-    for (int k = 0; k <= m.L; ++k) w.z[k] = take(N * w.hs * 4);
-    w.pre0 = need_pre0 ? take(N * w.hp * 4) : nullptr;
-    w.dza = take(N * w.hp * 4);
-    w.dzb = take(N * w.hp * 4);
-    const long long part_gemm = (long long)splitk_parts(N, m.h) * m.h * m.h, part_out = (long long)w.blocks * (w.hsv + 1 > m.h * (1 + m.C) ? w.hsv + 1 : m.h * (1 + m.C));
-    w.part = take((part_gemm > part_out ? part_gemm : part_out) * 4);
+    w.fsv = m.F + 1 + m.C;
+    w.fs = (w.fsv + 3) / 4 * 4;
+    w.fp = (m.F + 3) / 4 * 4;
+    for (int k = 0; k <= m.L; ++k) w.z[k] = take(N * (k == 0 ? w.fs : w.hs) * 4);
+    w.pre0 = need_pre0 ? take(N * w.fp * 4) : nullptr;
+    w.dza = take(N * mx(w.hp, w.fp) * 4);
+    w.dzb = take(N * mx(w.hp, w.fp) * 4);
+    long long part_gemm = m.L > 0 ? (long long)splitk_parts(N, m.h) * m.h * mx(m.h, m.F) : 0;
+    long long part_out = (long long)w.blocks * (w.hsv + 1 > m.h * (1 + m.C) ? w.hsv + 1 : m.h * (1 + m.C));
+    if (m.general()) part_out = (long long)splitk_parts(N, m.O) * m.O * (m.hl() + 1 + m.C);   // the output layer's GEMM partials
+    w.part = take(mx(part_gemm, part_out) * 4);
     {   // (db | dS) partials: one [h][1 + C] block per wide_out_kernel block / per 128-row tile of the backward GEMM
         const long long tiles = (N + GM_BM - 1) / GM_BM;
-        w.part2 = take((w.blocks > tiles ? w.blocks : tiles) * m.h * (1 + m.C) * 4);
+        w.part2 = take(mx(w.blocks, tiles) * mx(m.h, m.F) * (1 + m.C) * 4);
     }
     w.grads = take(((long long)m.P + 1 + 31) / 32 * 32 * 4);
-    {
-        const long long hq = (m.h + 15) / 16 * 16;
-        w.wp = take((long long)m.L * hq * hq * 4);
-    }
+    w.wp = take(wide_wp_off(m, m.L) * 4);
+    w.dy = m.general() ? take(N * 4 * 4) : nullptr;
+    w.lpart = m.general() ? take((long long)w.blocks * 4) : nullptr;
     w.coef = nullptr;
     w.bytes = off;
     return w;
@@ -468,9 +634,19 @@ inline long long wide_total_bytes(const WideMap& m, long long N, bool pre0, int 
     return carve_wide(m, N, pre0, nullptr).bytes + wide_align((long long)n_images * 2 * 4);
 }
 
+// the descriptor's own feature width / output count, 0 = today's meaning (F = h, O = 1)
+inline int wide_desc_F(const InrModelDesc* md) { return md->n_features > 0 ? md->n_features : md->n_hidden; }
+inline int wide_desc_O(const InrModelDesc* md) { return md->n_out > 0 ? md->n_out : 1; }
+inline bool wide_desc_general(const InrModelDesc* md) {
+    return wide_desc_F(md) != md->n_hidden || wide_desc_O(md) != 1 || md->n_layers == 0;
+}
 inline bool wide_shape_ok(const InrModelDesc* md) {
-    return md && md->kind == INR_MODEL_ICNN && md->n_hidden >= 1 && md->n_hidden <= WIDE_MAX_HIDDEN && md->n_layers >= 1 &&
-           md->n_layers <= WIDE_MAX_LAYERS && (md->in_features == 2 || md->in_features == 3);
+    if (!md || md->kind != INR_MODEL_ICNN || md->n_hidden < 1 || md->n_hidden > WIDE_MAX_HIDDEN || md->n_layers < 0 ||
+        md->n_layers > WIDE_MAX_LAYERS || (md->in_features != 2 && md->in_features != 3))
+        return false;
+    if (md->n_features < 0 || md->n_features > WIDE_MAX_HIDDEN || md->n_out < 0 || md->n_out > 4) return false;
+    // no hidden layer: only behind a periodic encode (the sine net's direct read-out); a relu layer 0 + read-out is not an ICNN shape
+    return md->n_layers >= 1 || md->act0 == INR_ACT_COS || md->act0 == INR_ACT_SIN;
 }
 
 #define WIDE_EW(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, s
@@ -478,28 +654,68 @@ inline bool wide_shape_ok(const InrModelDesc* md) {
 // rows short enough for the wide_out_kernel instantiations that also sum dZ_L^T (1, X) (16 more accumulators per 64-column slice)
 inline bool wide_out_has_ext(int hs) { return hs <= 9 * 64; }
 
+// the output layer of a general shape: wide_head_kernel, and with `train` the output layer's gradient (a GEMM over the points), the
+// (1, x) sums of dZ_L (the (db | dS) of the last hidden layer, or (db_in | dW_in) when the output layer reads the features) and the loss
+inline int wide_head(const WideMap& m, const WideWs& w, const InrModelDesc* md, const float* params, long long N, const float* target,
+                     int loss_kind, bool train, float* logits, hipStream_t s) {
+    const int L = m.L, hl = m.hl(), C = m.C;
+    const int ls = L > 0 ? w.hs : w.fs, lp = L > 0 ? w.hp : w.fp;
+    WideHeadArgs a{};
+    a.zl = w.z[L]; a.wo = params + m.p_wo(); a.sc = params + m.p_bo(); a.pre = w.pre0; a.target = target; a.coef = w.coef; a.logits = logits;
+    a.dy = w.dy; a.dz = w.dza; a.lpart = w.lpart;
+    a.N = N; a.hl = hl; a.C = C; a.ls = ls; a.lp = lp; a.loss_kind = loss_kind; a.train = train ? 1 : 0; a.act = md->act0; a.omega = md->act_omega;
+#define WIDE_HEAD_GO(O_)                                                                                                   \
+    do {                                                                                                                   \
+        if (L == 0) hipLaunchKernelGGL((wide_head_kernel<O_, true>), dim3(w.blocks), dim3(256), 0, s, a);                  \
+        else hipLaunchKernelGGL((wide_head_kernel<O_, false>), dim3(w.blocks), dim3(256), 0, s, a);                        \
+    } while (0)
+    if (m.O == 1) WIDE_HEAD_GO(1);
+    else if (m.O == 2) WIDE_HEAD_GO(2);
+    else if (m.O == 3) WIDE_HEAD_GO(3);
+    else WIDE_HEAD_GO(4);
+#undef WIDE_HEAD_GO
+    if (!train) return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    {   // (dw_o | db_o | ds_o) [O][hl + 1 + C] = dY^T (Z_L | 1 | X): dY [N][4] is the A operand stored along its free index (its fourth
+        // column holds zeros), the rows of Z_L carry their ext columns; split over the points like the hidden layers' weight gradients
+        GemmArgs g{};
+        g.A = w.dy; g.lda = 4; g.B = w.z[L]; g.ldb = ls; g.C = w.part; g.ldc = hl + 1 + C;
+        g.M = m.O; g.N = hl + 1 + C; g.K = (int)N; g.k_per_split = wide_chunk(m.O); g.c_split_stride = (long long)m.O * (hl + 1 + C);
+        g.padA = g.padB = 1; g.buf = 1;
+        if (const int rc = gemm_launch(s, true, false, g)) return rc;
+    }
+    hipLaunchKernelGGL(wide_extgrad_kernel, dim3(w.blocks), dim3(256), 0, s, (const float*)w.dza, lp, (const float*)(w.z[L] + hl), ls, N, hl, C, w.part2);
+    const int parts = splitk_parts(N, m.O);
+    wide_reduce(s, m, w.grads, wide_red_job(w.part, parts, m.O, hl + 1 + C, 4, 0),
+                wide_red_job(w.part2, w.blocks, hl, 1 + C, L > 0 ? 3 : 1, L > 0 ? L - 1 : 0));
+    wide_reduce(s, m, w.grads, wide_red_job(w.lpart, w.blocks, 1, 1, 5, 0));
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
 // forward of ONE image; with `train`: also dZ_L (w.dza), the output layer's gradients and the loss (w.grads)
 inline int wide_forward(const WideMap& m, const WideWs& w, const InrModelDesc* md, const float* params, const InrGridDesc* grid, int img,
                         const float* target, int loss_kind, bool train, float* logits, hipStream_t s) {
     const long long N = grid->n_points;
     const int h = m.h, C = m.C, hs = w.hs;
-    // layer 0 (+ in the launch's last blocks: the padded copy of the hidden layers' weights)
+    // layer 0 at width F (+ in the launch's last blocks: the padded copy of the hidden layers' weights)
     const int pt_blocks = (int)((N + WIDE_L0_POINTS * WIDE_L0_REP - 1) / (WIDE_L0_POINTS * WIDE_L0_REP));
-    const unsigned l0y = (unsigned)((WIDE_L0_POINTS * (hs / 4) + 255) / 256);
-    const int hq = (h + 15) / 16 * 16;   // row / column count of a packed weight matrix
-    const int pk_blocks = (int)(((long long)m.L * hq * hq + 256ll * l0y - 1) / (256ll * l0y));
+    const unsigned l0y = (unsigned)((WIDE_L0_POINTS * (w.fs / 4) + 255) / 256);
+    const int hq = wide_q16(h);   // row count of a packed weight matrix (and column count of layers k >= 1)
+    const int pk_blocks = (int)((wide_wp_off(m, m.L) + 256ll * l0y - 1) / (256ll * l0y));
     const dim3 l0grid((unsigned)(pt_blocks + pk_blocks), l0y);
-    if (C == 2) hipLaunchKernelGGL(wide_layer0_kernel<2>, l0grid, dim3(256), 0, s, *grid, img, params + m.p_win(), params + m.p_bin(), N, h, hs, w.hp, md->act0, md->act_omega, w.z[0], w.pre0, pt_blocks, params, m, w.wp);
-    else hipLaunchKernelGGL(wide_layer0_kernel<3>, l0grid, dim3(256), 0, s, *grid, img, params + m.p_win(), params + m.p_bin(), N, h, hs, w.hp, md->act0, md->act_omega, w.z[0], w.pre0, pt_blocks, params, m, w.wp);
+    if (C == 2) hipLaunchKernelGGL(wide_layer0_kernel<2>, l0grid, dim3(256), 0, s, *grid, img, params + m.p_win(), params + m.p_bin(), N, m.F, w.fs, w.fp, md->act0, md->act_omega, w.z[0], w.pre0, pt_blocks, params, m, w.wp);
+    else hipLaunchKernelGGL(wide_layer0_kernel<3>, l0grid, dim3(256), 0, s, *grid, img, params + m.p_win(), params + m.p_bin(), N, m.F, w.fs, w.fp, md->act0, md->act_omega, w.z[0], w.pre0, pt_blocks, params, m, w.wp);
     for (int k = 0; k < m.L; ++k) {
-        // z_{k+1} [N x h] = relu(z_k [N x h] . W_k^T + b_k + S_k x)   (W_k stored [h_out][h_in]; bias, skip and relu in the GEMM's epilogue)
+        // z_{k+1} [N x h] = relu(z_k [N x kin] . W_k^T + b_k + S_k x)   (W_k stored [h_out][h_in]; bias, skip and relu in the GEMM's epilogue;
+        // kin = F for k = 0)
+        const int kin = m.kin(k), ks = k == 0 ? w.fs : hs;
         GemmArgs g{};
-        g.A = w.z[k]; g.lda = hs; g.B = w.wp + (size_t)k * hq * hq; g.ldb = hq; g.C = w.z[k + 1]; g.ldc = hs;
-        g.M = (int)N; g.N = h; g.K = h; g.padA = g.padB = 1; g.buf = 1;
-        g.epi = GEMM_EPI_HIDDEN; g.bias = params + m.p_b(k); g.skip = params + m.p_s(k); g.ext = w.z[k] + h; g.ext_ld = hs; g.C_in = C; g.ext_copy = hs - h;
+        g.A = w.z[k]; g.lda = ks; g.B = w.wp + wide_wp_off(m, k); g.ldb = k == 0 ? wide_q16(m.F) : hq; g.C = w.z[k + 1]; g.ldc = hs;
+        g.M = (int)N; g.N = h; g.K = kin; g.padA = g.padB = 1; g.buf = 1;
+        g.epi = GEMM_EPI_HIDDEN; g.bias = params + m.p_b(k); g.skip = params + m.p_s(k); g.ext = w.z[k] + kin; g.ext_ld = ks; g.C_in = C; g.ext_copy = hs - h;
         int rc = gemm_launch(s, false, true, g);
         if (rc) return rc;
     }
+    if (m.general()) return wide_head(m, w, md, params, N, target, loss_kind, train, logits, s);
     WideOutArgs a{};
     a.zl = w.z[m.L]; a.wo = params + m.p_wo(); a.sc = params + m.p_bo(); a.target = target; a.coef = w.coef; a.logits = logits;
     a.dz = w.dza; a.part = w.part;
@@ -519,45 +735,58 @@ inline int wide_forward(const WideMap& m, const WideWs& w, const InrModelDesc* m
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
-// backward of ONE image from dZ_L (w.dza, written by wide_forward): every remaining parameter gradient into w.grads (flat order)
+// backward of ONE image from dZ_L (w.dza, written by wide_forward): every remaining parameter gradient into w.grads (flat order).
+// need_dz0 = false (general shapes only): dZ_0 and with it (db_in | dW_in) are not computed - the fit of frozen Fourier features.
 inline int wide_backward(const WideMap& m, const WideWs& w, const InrModelDesc* md, const float* params, long long N, hipStream_t s,
-                         const float* dlogits = nullptr, float* dcoords = nullptr) {   // dcoords [C][N] (with dlogits = dL/dlogits): also dL/dcoords
+                         const float* dlogits = nullptr, float* dcoords = nullptr,   // dcoords [C][N] (with dlogits = dL/dlogits): also dL/dcoords
+                         bool need_dz0 = true) {
     const int h = m.h, C = m.C, hs = w.hs, hp = w.hp, parts = splitk_parts(N, h);
+    const bool gen = m.general();
     float* gr = w.grads;
     int rc;
     float *dz = w.dza, *dzn = w.dzb;
-    const int tiles = (int)((N + GM_BM - 1) / GM_BM), hq = (h + 15) / 16 * 16;
+    const int tiles = (int)((N + GM_BM - 1) / GM_BM), hq = wide_q16(h);
     const dim3 dxgrid((unsigned)((N + 15) / 16));
-    if (dcoords)   // s_o dL/dlogit + dZ_L . S_{L-1}
-        hipLaunchKernelGGL(wide_dx_kernel, dxgrid, dim3(256), 0, s, dz, hp, params + m.p_s(m.L - 1), h, C, N, dlogits, params + m.p_so(), dcoords, 1);
+    if (dcoords) {   // s_o dL/dlogit + dZ_L . S_{L-1}  (L = 0: dZ_0 . W_in)
+        if (m.L > 0)
+            hipLaunchKernelGGL(wide_dx_kernel, dxgrid, dim3(256), 0, s, dz, hp, params + m.p_s(m.L - 1), h, C, N, dlogits, params + m.p_so(), dcoords, 1, m.O);
+        else
+            hipLaunchKernelGGL(wide_dx_kernel, dxgrid, dim3(256), 0, s, dz, w.fp, params + m.p_win(), m.F, C, N, dlogits, params + m.p_so(), dcoords, 1, m.O);
+    }
     for (int k = m.L - 1; k >= 0; --k) {
-        {   // dW_k [h x h] = dz^T Z_k: the contraction over the points, split into chunks of WIDE_CHUNK
+        const int kin = m.kin(k), ks = k == 0 ? w.fs : hs, kp = k == 0 ? w.fp : hp;   // layer k's input width, its activation / dz rows
+        {   // dW_k [h x kin] = dz^T Z_k: the contraction over the points, split into chunks of WIDE_CHUNK
             GemmArgs g{};
-            g.A = dz; g.lda = hp; g.B = w.z[k]; g.ldb = hs; g.C = w.part; g.ldc = h;
-            g.M = h; g.N = h; g.K = (int)N; g.k_per_split = wide_chunk(h); g.c_split_stride = (long long)h * h; g.padA = g.padB = 1; g.buf = 1;
+            g.A = dz; g.lda = hp; g.B = w.z[k]; g.ldb = ks; g.C = w.part; g.ldc = kin;
+            g.M = h; g.N = kin; g.K = (int)N; g.k_per_split = wide_chunk(h); g.c_split_stride = (long long)h * kin; g.padA = g.padB = 1; g.buf = 1;
             if ((rc = gemm_launch(s, true, false, g))) return rc;   // (its partials are added up with the (1, x) sums below: one launch)
-            // (db_k | dS_k) = dz^T (1, X): summed by the kernel that wrote dz (wide_out_kernel for the last layer, the backward GEMM's
-            // epilogue below for the others); only rows too long for wide_out_kernel's accumulators take a pass of their own
-            if (k == m.L - 1 && !wide_out_has_ext(hs)) {
+            // (db_k | dS_k) = dz^T (1, X): summed by the kernel that wrote dz (wide_out_kernel / wide_head for the last layer, the backward
+            // GEMM's epilogue below for the others); only rows too long for wide_out_kernel's accumulators take a pass of their own
+            if (!gen && k == m.L - 1 && !wide_out_has_ext(hs)) {
                 hipLaunchKernelGGL(wide_extgrad_kernel, dim3(w.blocks), dim3(256), 0, s, dz, hp, w.z[k] + h, hs, N, h, C, w.part2);
                 wide_reduce(s, m, gr, wide_red_job(w.part2, w.blocks, h, 1 + C, 3, k));
             }
         }
+        if (k == 0 && gen && !need_dz0) {   // frozen input layer, no coordinate gradient: dW_0 is the last product
+            wide_reduce(s, m, gr, wide_red_job(w.part, parts, h, kin, 0, k));
+            break;
+        }
         {   // dz_k = (dz W_k) (.) act'(layer k)     (the mask in the GEMM's epilogue, and dz_k^T (1, X) per 128-row tile)
             GemmArgs g{};
-            g.A = dz; g.lda = hp; g.B = w.wp + (size_t)k * hq * hq; g.ldb = hq; g.C = dzn; g.ldc = hp;   // (the weights wide_forward packed)
-            g.M = (int)N; g.N = h; g.K = h; g.padA = g.padB = 1; g.buf = 1; g.c_zero_to = hp;
+            g.A = dz; g.lda = hp; g.B = w.wp + wide_wp_off(m, k); g.ldb = k == 0 ? wide_q16(m.F) : hq; g.C = dzn; g.ldc = kp;   // (the weights wide_forward packed)
+            g.M = (int)N; g.N = kin; g.K = h; g.padA = g.padB = 1; g.buf = 1; g.c_zero_to = kp;
             g.epi = GEMM_EPI_MASK;
             const int act = k == 0 ? md->act0 : INR_ACT_RELU;
             g.mask_act = act; g.omega = md->act_omega;
-            if (act == INR_ACT_RELU) { g.mask = w.z[k]; g.mask_ld = hs; }
-            else { g.mask = w.pre0; g.mask_ld = hp; }
-            g.extsum = w.part2; g.ext = w.z[k] + h; g.ext_ld = hs; g.C_in = C;
+            if (act == INR_ACT_RELU) { g.mask = w.z[k]; g.mask_ld = ks; }
+            else { g.mask = w.pre0; g.mask_ld = w.fp; }
+            g.extsum = w.part2; g.ext = w.z[k] + kin; g.ext_ld = ks; g.C_in = C;
             if ((rc = gemm_launch(s, false, false, g))) return rc;
             // what the ext inputs multiply in the layer below: (db_{k-1} | dS_{k-1}), or (db_in | dW_in) of layer 0
-            wide_reduce(s, m, gr, wide_red_job(w.part, parts, h, h, 0, k), wide_red_job(w.part2, tiles, h, 1 + C, k > 0 ? 3 : 1, k > 0 ? k - 1 : 0));            if (dcoords)   // ... and what the coordinates multiply there: S_{k-1}, or W_in
-                hipLaunchKernelGGL(wide_dx_kernel, dxgrid, dim3(256), 0, s, dzn, hp, params + (k > 0 ? m.p_s(k - 1) : m.p_win()), h, C, N, dlogits,
-                                   params + m.p_so(), dcoords, 0);
+            wide_reduce(s, m, gr, wide_red_job(w.part, parts, h, kin, 0, k), wide_red_job(w.part2, tiles, kin, 1 + C, k > 0 ? 3 : 1, k > 0 ? k - 1 : 0));
+            if (dcoords)   // ... and what the coordinates multiply there: S_{k-1}, or W_in
+                hipLaunchKernelGGL(wide_dx_kernel, dxgrid, dim3(256), 0, s, dzn, kp, params + (k > 0 ? m.p_s(k - 1) : m.p_win()), kin, C, N, dlogits,
+                                   params + m.p_so(), dcoords, 0, m.O);
         }
         float* t = dz; dz = dzn; dzn = t;
     }

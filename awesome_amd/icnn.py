@@ -30,18 +30,30 @@ class IcnnSpec:
     n_layers: int = 1
     act0: str = "relu"     # layer-0 activation = the encode stage: 'relu' | 'cos' (Fourier features) | 'sin' (sine layer)
     omega: float = 1.0     # 'sin' only: z0 = sin(omega (W_in x + b_in))
+    n_features: int = 0    # F, width of layer 0 (the encode stage); 0 = n_hidden
+    n_out: int = 1         # O, output channels (1..4); logits / targets of O > 1 are [n_images, O, N]
+
+    @property
+    def features(self) -> int:
+        return self.n_features or self.n_hidden
+
+    @property
+    def general(self) -> bool:
+        """Not an ICNN shape: own feature width, several outputs or no hidden layer (the layer-by-layer path only)."""
+        return self.features != self.n_hidden or self.n_out != 1 or self.n_layers == 0
 
     def desc(self) -> L.InrModelDesc:
         return L.InrModelDesc(L.INR_MODEL_ICNN, self.n_hidden, self.in_features, self.n_layers, L.ACT_KINDS[self.act0],
-                              float(self.omega))
+                              float(self.omega), int(self.n_features), int(self.n_out))
 
     def keys_shapes(self) -> List[Tuple[str, Tuple[int, ...]]]:
-        """state_dict keys of ConvexNextNet in flat-vector order (awesome/model/convex_net.py:188-203)."""
-        h, c = self.n_hidden, self.in_features
-        out = [("input.weight", (h, c)), ("input.bias", (h,))]
+        """state_dict keys of ConvexNextNet in flat-vector order (awesome/model/convex_net.py:188-203); with n_features / n_out the
+        general layout of include/inrfit.h (input.weight [F, C], skip.0.ln.weight [h, F], out.ln.weight [O, h or F], ...)."""
+        h, c, f, o = self.n_hidden, self.in_features, self.features, self.n_out
+        out = [("input.weight", (f, c)), ("input.bias", (f,))]
         for k in range(self.n_layers):
-            out += [(f"skip.{k}.ln.weight", (h, h)), (f"skip.{k}.ln.bias", (h,)), (f"skip.{k}.skp.weight", (h, c))]
-        out += [("out.ln.weight", (1, h)), ("out.ln.bias", (1,)), ("out.skp.weight", (1, c))]
+            out += [(f"skip.{k}.ln.weight", (h, f if k == 0 else h)), (f"skip.{k}.ln.bias", (h,)), (f"skip.{k}.skp.weight", (h, c))]
+        out += [("out.ln.weight", (o, h if self.n_layers > 0 else f)), ("out.ln.bias", (o,)), ("out.skp.weight", (o, c))]
         return out
 
     @property
@@ -61,7 +73,7 @@ class IcnnSpec:
     def fused(self) -> bool:
         """A fused MFMA step kernel serves this shape (n_hidden <= 130, L <= 2; other widths zero-padded) - what the composite
         priors and the fused joint step need; wider / deeper nets run layer by layer (csrc/wide.h) through inrfit_fit etc. only."""
-        return self.supported() and self.n_hidden <= 130 and self.n_layers <= 2
+        return self.supported() and not self.general and self.n_hidden <= 130 and self.n_layers <= 2
 
     def supported(self) -> bool:
         d = self.desc()
@@ -182,7 +194,13 @@ def _check_dev(t: Tensor, name: str) -> Tensor:
 def _check_spec(spec: IcnnSpec) -> None:
     if not spec.supported():
         raise L.InrfitError(f"no kernel path for {spec}: n_hidden <= 1024, in_features in {{2, 3}}, 1..8 hidden layers (fused MFMA kernels "
-                            f"for n_hidden <= 130 and L <= 2, zero-padded to the next compiled width; the layer-by-layer path beyond)")
+                            f"for n_hidden <= 130 and L <= 2, zero-padded to the next compiled width; the layer-by-layer path beyond), "
+                            f"n_features <= 1024, n_out <= 4, no hidden layer only behind a 'cos' / 'sin' layer 0")
+
+
+def _out_shape(spec: IcnnSpec, n_images: int, n_points: int) -> Tuple[int, ...]:
+    """logits / targets / dlogits: [n_images, N] for one output, [n_images, O, N] for several."""
+    return (n_images, n_points) if spec.n_out == 1 else (n_images, spec.n_out, n_points)
 
 
 def _workspace(spec: IcnnSpec, grid: Grid, n_images: int) -> Tensor:
@@ -197,14 +215,14 @@ def _workspace(spec: IcnnSpec, grid: Grid, n_images: int) -> Tensor:
 # entry points
 # ----------------------------------------------------------------------------------------------------------------------
 def forward(spec: IcnnSpec, params: Tensor, grid: Grid) -> Tensor:
-    """params [n_images, P] -> logits [n_images, N]."""
+    """params [n_images, P] -> logits [n_images, N] ([n_images, O, N] for n_out = O > 1)."""
     _check_spec(spec)
     params = _check_dev(params, "params")
     if params.dim() == 1:
         params = params[None]
     n_images = params.shape[0]
     assert params.shape[1] == spec.n_params, (params.shape, spec.n_params)
-    logits = L.scratch(n_images, grid.n_points, dtype=torch.float32, device=params.device)
+    logits = L.scratch(*_out_shape(spec, n_images, grid.n_points), dtype=torch.float32, device=params.device)
     md, gd = spec.desc(), grid.desc()
     ws = _workspace(spec, grid, n_images)
     rc = L.load().inrfit_forward(C.byref(md), params.data_ptr(), C.byref(gd), n_images, logits.data_ptr(), ws.data_ptr(),
@@ -219,7 +237,8 @@ def _loss_desc(kind: str, weight_mode: str, ratio: float, c_fg: float, c_bg: flo
 
 def loss_grad(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, loss: str = "se", weight_mode: str = "none",
               ratio: float = 1.0, c_fg: float = 0.0, c_bg: float = 0.0) -> Tuple[Tensor, Tensor]:
-    """-> (loss [n_images], grads [n_images, P]) of the data term at `params`."""
+    """-> (loss [n_images], grads [n_images, P]) of the data term at `params`.  targets [n_images, N] ([n_images, O, N] for n_out > 1;
+    the data term is then averaged over O x N like torch's MSELoss on (N, O))."""
     _check_spec(spec)
     params = _check_dev(params, "params")
     targets = _check_dev(targets, "targets")
@@ -227,7 +246,7 @@ def loss_grad(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, loss:
         params = params[None]
     n_images = params.shape[0]
     targets = targets.reshape(n_images, -1)
-    assert targets.shape[1] == grid.n_points
+    assert targets.shape[1] == spec.n_out * grid.n_points
     ws = _workspace(spec, grid, n_images)
     loss_out = L.scratch(n_images, dtype=torch.float32, device=params.device)
     grads = L.scratch_like(params)
@@ -248,8 +267,8 @@ def backward(spec: IcnnSpec, params: Tensor, grid: Grid, dlogits: Tensor, want_d
     if params.dim() == 1:
         params = params[None]
     n_images = params.shape[0]
-    dlogits = dlogits.reshape(n_images, -1)
-    assert dlogits.shape[1] == grid.n_points
+    dlogits = dlogits.reshape(n_images, -1)   # ([n_images, O, N] for n_out > 1)
+    assert dlogits.shape[1] == spec.n_out * grid.n_points
     ws = _workspace(spec, grid, n_images)
     grads = L.scratch_like(params)
     dco = L.scratch(n_images, spec.in_features, grid.n_points, dtype=torch.float32, device=params.device) if want_dcoords else None
@@ -319,14 +338,14 @@ def fit(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, steps: int,
     if params.dim() != 2:
         raise ValueError("params must be [n_images, P]")
     n_images = params.shape[0]
-    targets = targets.reshape(n_images, -1)
-    assert targets.shape[1] == grid.n_points
+    targets = targets.reshape(n_images, -1)   # ([n_images, O, N] for n_out > 1)
+    assert targets.shape[1] == spec.n_out * grid.n_points
     dev = params.device
     if opt_state is None:
         opt_state = new_opt_state(spec, n_images, dev)
     ws = _workspace(spec, grid, n_images)
     hist = L.scratch(n_images, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    logits = L.scratch(n_images, grid.n_points, dtype=torch.float32, device=dev) if want_logits else None
+    logits = L.scratch(*_out_shape(spec, n_images, grid.n_points), dtype=torch.float32, device=dev) if want_logits else None
     status = torch.zeros(n_images, dtype=torch.int32, device=dev)
     pl = plateau or {}
     od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),

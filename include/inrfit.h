@@ -20,6 +20,17 @@
  *     for k in 0..L-1: skip.k.ln.weight [h][h] | skip.k.ln.bias [h] | skip.k.skp.weight [h][C] |
  *     out.ln.weight [h] | out.ln.bias [1] | out.skp.weight [C]
  *   P = h*C + h + L*(h*h + h + h*C) + h + 1 + C            (17813 for h=130, C=2, L=1)
+ * General form (ABI 8), F = n_features or h, O = n_out or 1 - the coordinate MLPs of the notebooks (an encode stage of F features, L relu
+ * layers of h units, O outputs):
+ *     input.weight [F][C] | input.bias [F] | skip.0.ln.weight [h][F] | skip.0.ln.bias [h] | skip.0.skp.weight [h][C] |
+ *     for k in 1..L-1: skip.k.ln.weight [h][h] | skip.k.ln.bias [h] | skip.k.skp.weight [h][C] |
+ *     out.ln.weight [O][h] | out.ln.bias [O] | out.skp.weight [O][C]          (L = 0: out.ln.weight [O][F], read from the features)
+ *   P = F*C + F + (L > 0 ? (h*F + h + h*C) + (L-1)*(h*h + h + h*C) : 0) + O*(L > 0 ? h : F) + O + O*C   (256269 for h=350, C=2, L=3, F=20, O=3)
+ * With F = h and O = 1 this is the layout above.  Support: 1 <= F <= 1024, 1 <= O <= 4; L = 0 only with a periodic layer 0 (INR_ACT_COS /
+ * INR_ACT_SIN).  A shape with F != h, O > 1 or L = 0 runs on the layer-by-layer path only; the composite priors (cdn_*, pcn_*), the joint
+ * steps and inrfit_step_only return INR_EUNSUPPORTED for it.  With O > 1, logits, targets and dlogits are [n_images][O][n_points]
+ * (channel-planar like the coordinates); the data term is averaged over O * n_points (torch's MSELoss on (N, O)) and takes weight_mode
+ * INR_WEIGHT_NONE or INR_WEIGHT_EXPLICIT only (others: INR_EINVAL).
  */
 #ifndef INRFIT_H
 #define INRFIT_H
@@ -35,7 +46,7 @@ extern "C" {
  * exported (nm -D shows the inrfit_* entry points and nothing else of the library's own). */
 #pragma GCC visibility push(default)
 
-#define INRFIT_ABI_VERSION 7
+#define INRFIT_ABI_VERSION 8
 
 enum {
     INR_OK = 0,
@@ -72,6 +83,8 @@ typedef struct InrModelDesc {
     int32_t n_layers;    /* L hidden skip layers (ConvexNet: 1) */
     int32_t act0;        /* INR_ACT_* (0 = relu: a zero-initialised tail keeps old callers' meaning) */
     float act_omega;     /* INR_ACT_SIN only */
+    int32_t n_features;  /* F: width of layer 0 (the encode stage), 1..1024; 0 = n_hidden (ABI 8; zero tail = ABI 7 meaning) */
+    int32_t n_out;       /* O: output channels, 1..4; 0 = 1 (ABI 8) */
 } InrModelDesc;
 
 /* The dense coordinate grid every image is evaluated on.
