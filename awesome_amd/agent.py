@@ -118,17 +118,22 @@ class JointTrainer:
       variants, awesome_amd.joint).  The torch optimizer then steps the segmentation parameters only (the prior's Parameters never
       receive a .grad, which torch.optim skips); the prior's hyper-parameters are read from their param group every step, so host
       LR schedulers keep working.  Applies to: batch size 1 (what a PriorManager swap implies), FBMSJointLoss / AwesomeImageLoss
-      (before its extra penalty) with fusable criteria, Adam or Adamax without amsgrad, a prior with a device form (ICNN,
-      PathConnectedNet, ConvexDiffeomorphismNet; these two only without weight decay, which torch would also apply to their 1x1 /
-      linear layer).
+      (before its extra penalty; with it on too when `fused_extra_penalty=True`, unaries targets without a noneclass) with fusable
+      criteria, Adam or Adamax without amsgrad, a prior with a device form (ICNN, PathConnectedNet, ConvexDiffeomorphismNet; these
+      two only without weight decay, which torch would also apply to their 1x1 / linear layer).
     * **autograd**: WrapperModule forward -> criterion -> loss.backward() through the HIP autograd bridges -> optimizer.step() ->
       enforce_convexity(); any criterion, any optimizer.
 
     The reference shares ONE optimizer state over all images' priors (it has one prior model whose VALUES are swapped): that is
-    `shared_prior_moments=True`, the default; False keeps Adam moments and step counts per image (fused path only)."""
+    `shared_prior_moments=True`, the default; False keeps Adam moments and step counts per image (fused path only).
+
+    `fused_extra_penalty` (opt-in, default False): AwesomeImageLoss steps with `extra_penalty` on (the runner's hook flips it in
+    mid-run) also take the fused path, where the prior's step kernel evaluates both of its data terms - the weighted criterion
+    against the targets and the align term against [seg > 0.5] - in one pass.  Off, those steps take the autograd path."""
 
     def __init__(self, wrapper: torch.nn.Module, bank: PriorBank, criterion: Callable, optimizer: torch.optim.Optimizer,
-                 fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch"):
+                 fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch",
+                 fused_extra_penalty: bool = False):
         if check_finite not in ("step", "epoch"):
             raise ValueError("check_finite: 'step' (raise before backward like the reference, one host sync per step) or 'epoch' "
                              "(device flag, the caller polls raise_if_failed())")
@@ -136,6 +141,7 @@ class JointTrainer:
         self.wrapper, self.bank, self.criterion, self.optimizer = wrapper, bank, criterion, optimizer
         self.forward_additional_loss_args = _loss_takes_input(criterion)
         self.shared_prior_moments = bool(shared_prior_moments)
+        self.fused_extra_penalty = bool(fused_extra_penalty)
         self._fused_plan = self._plan_fused()
         if fused and self._fused_plan is None:
             raise ValueError("this combination of prior module / criterion / optimizer has no fused joint step")
@@ -149,9 +155,9 @@ class JointTrainer:
     # -- ONE optimizer state for the prior, whichever implementation steps it -----------------------------------------------
     # The reference has one torch optimizer for the whole run (torch_agent.py:812-839).  The fused step keeps the prior's moments
     # in its own flat buffers; when a step has to take the other implementation (AwesomeImageLoss once the runner's hook has set
-    # `extra_penalty`, a batch of more than one image, the step that initialises ActNorm) the moments and the step count move
-    # with it, so the trajectory is the single-optimizer one.  Per-image moments (shared_prior_moments=False) exist
-    # in the fused buffers only and are not carried over.
+    # `extra_penalty`, unless fused_extra_penalty; a batch of more than one image; the step that initialises ActNorm) the moments
+    # and the step count move with it, so the trajectory is the single-optimizer one.  Per-image moments
+    # (shared_prior_moments=False) exist in the fused buffers only and are not carried over.
     def _prior_params(self):
         from .prior_bank import _ordered_parameters
         return list(_ordered_parameters(self.wrapper.prior_module))
@@ -265,8 +271,11 @@ class JointTrainer:
         g = plan["group"]
         if desc is None or (plan["family"] != "icnn" and float(g.get("weight_decay", 0.0)) != 0.0):
             return None
-        if desc.form != 0 and (desc.form != 1 or desc.extra_penalty or desc.target_rule or desc.use_noneclass):
-            return None   # AwesomeImageLoss with its extra penalty on: two data terms on the prior (inrfit_joint_step: INR_EUNSUPPORTED)
+        if desc.form != 0 and (desc.form != 1 or desc.target_rule or desc.use_noneclass):
+            return None   # the pixel form; AwesomeImageLoss on class labels or with a noneclass (inrfit_joint_step: INR_EUNSUPPORTED)
+        if desc.form == 1 and desc.extra_penalty and not self.fused_extra_penalty:
+            return None   # AwesomeImageLoss with its extra penalty on: the autograd step unless asked for (the desc is read every
+                          # step, so gamma / alpha / beta and the hook's switch take effect at once)
         xi = inputs[0] if inputs[0].dim() == 4 else inputs[0][None]
         if xi.shape[0] != 1:
             return None

@@ -252,6 +252,8 @@ struct StepArgs {
     long long N;
     int n_images, wgs, PS, loss_kind;
     float act_omega;       // INR_ACT_SIN kernels
+    const float* seg;      // [n_images][N] or null (TRAIN): the align mode of the fused joint step, see align_term
+    float c_align;         // its coefficient
 };
 
 // Cross-lane sums on the VALU (DPP / permlane swaps): no LDS round trip, no s_waitcnt.
@@ -264,6 +266,18 @@ __device__ __forceinline__ float dpp_f(float v) {
 __device__ __forceinline__ float bce_log(float x) {
     const float l = logf(x);
     return l < -100.f ? -100.f : l;
+}
+
+// The align mode of the fused joint step (AwesomeImageLoss with extra_penalty, joint_loss.h): `seg` != null adds the align term
+// c_align (p - [s > 0.5])^2 to the prior's data term (SE or BCE, loss_kind) and its derivative to dy.  The indicator carries no
+// gradient; the comparison is strict, so a NaN in s counts as 0 like torch's (nan > 0.5).  With cw = gamma alpha w' / n_d (the
+// coefficients) and c_align = beta / N, the loss column is the prior's whole share of the composite loss and the gradient scale is 1.
+// The read sits at the data term, inside the mode's branch: no register held across the chunk loop in any other mode.
+__device__ __forceinline__ void align_term(const float* __restrict__ seg, float c_align, float pr, float& l, float& dy) {
+    const float d = pr - (*seg > 0.5f ? 1.f : 0.f);
+    const float cd = c_align * d;
+    l = fmaf(cd, d, l);
+    dy = fmaf(2.f * cd, pr * (1.f - pr), dy);
 }
 
 __device__ __forceinline__ float sum_over_points(float v) {  // the 16 lanes sharing lane>>4 (one DPP row)
@@ -659,6 +673,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 const float pq = pr * (1.f - pr);
                 dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
             }
+            if (a.seg != nullptr && valid) align_term(a.seg + (size_t)img * N + p, a.c_align, pr, l, dy);
             if (!valid) {
                 l = 0.f;
                 dy = 0.f;

@@ -475,6 +475,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn2_step_kernel(const StepArg
                 const float pq = pr * (1.f - pr);
                 dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
             }
+            if (a.seg != nullptr && valid) align_term(a.seg + (size_t)img * N + p, a.c_align, pr, l, dy);
             if (!valid) {
                 l = 0.f;
                 dy = 0.f;

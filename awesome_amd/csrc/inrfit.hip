@@ -347,9 +347,10 @@ __global__ __launch_bounds__(256) void pack_params_kernel(const float* __restric
     if (ns > 1) wi[slot[1]] = v;
 }
 
-// per-image loss coefficients (c_fg, c_bg): 'mean' normalisation x UnariesWeightedLoss class weight
+// per-image loss coefficients (c_fg, c_bg): 'mean' normalisation x UnariesWeightedLoss class weight x `scale` (1, or the fused joint
+// step's gamma alpha in the align mode)
 __global__ __launch_bounds__(256) void loss_coef_kernel(const float* __restrict__ targets, long long N, InrLossDesc loss,
-                                                        float* __restrict__ coef) {
+                                                        float* __restrict__ coef, float scale) {
     const int img = blockIdx.x;
     __shared__ unsigned long long cnt[4];
     unsigned long long fg = 0;
@@ -378,8 +379,8 @@ __global__ __launch_bounds__(256) void loss_coef_kernel(const float* __restrict_
             cfg = w * inv_n;
             cbg = inv_n;
         }
-        coef[2 * img] = cfg;
-        coef[2 * img + 1] = cbg;
+        coef[2 * img] = cfg * scale;
+        coef[2 * img + 1] = cbg * scale;
     }
 }
 
@@ -701,9 +702,12 @@ static int launch_pack(const KernelEntry* e, const Workspace& w, const float* pa
 }
 
 static int launch_step(const KernelEntry* e, const Workspace& w, bool train, const InrGridDesc* grid, const float* targets,
-                       int loss_kind, int n_images, float* logits, hipStream_t s, float* dcoords = nullptr) {
+                       int loss_kind, int n_images, float* logits, hipStream_t s, float* dcoords = nullptr,
+                       const float* align_seg = nullptr, float c_align = 0.f) {
     StepArgs a{};
     a.dcoords = dcoords;
+    a.seg = align_seg;
+    a.c_align = c_align;
     a.wimg = w.wimg;
     a.targets = targets;
     a.coef = w.coef;
@@ -877,7 +881,7 @@ static int wide_loss_grad_all(const InrModelDesc* model, const float* params, co
     const long long N = grid->n_points, ON = (long long)m.O * N;   // targets / dlogits: [n_images][O][N]
     if (m.O > 1 && loss->weight_mode != INR_WEIGHT_NONE && loss->weight_mode != INR_WEIGHT_EXPLICIT) return INR_EINVAL;
     if (loss->kind != INR_LOSS_EXTERNAL)   // ('mean' over the O x N elements: torch's MSELoss on (N, O))
-        hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef);
+        hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef, 1.f);
     for (int img = 0; img < n_images; ++img) {
         w.coef = coef + 2 * img;
         const float* p = params + (size_t)img * m.P;
@@ -899,7 +903,7 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
     if (rc) return rc;
     const long long N = grid->n_points, ON = (long long)m.O * N;   // targets / logits: [n_images][O][N]
     if (m.O > 1 && loss->weight_mode != INR_WEIGHT_NONE && loss->weight_mode != INR_WEIGHT_EXPLICIT) return INR_EINVAL;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef, 1.f);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, m.P, *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
     // the optimizer step = icnn_update_kernel on a one-"slab" view of the gradient vector (column = parameter, column P = the loss)
@@ -977,7 +981,7 @@ int inrfit_loss_grad(const InrModelDesc* model, const float* params, const InrGr
         return wide_loss_grad_all(model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes, (hipStream_t)stream);
     if ((rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef, 1.f);
     if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
     if ((rc = launch_step(e, w, true, grid, targets, loss->kind, n_images, nullptr, s))) return rc;
     launch_reduce(e, w, n_images, grads, loss_out, s);
@@ -1013,7 +1017,7 @@ int inrfit_step_only(const InrModelDesc* model, const float* params, const InrGr
     if (rc) return rc;
     if ((rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef, 1.f);
     if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
     for (int it = 0; it < iters; ++it)
         if ((rc = launch_step_timed(e, w, grid, targets, loss->kind, n_images, s))) return rc;
@@ -1082,7 +1086,7 @@ int inrfit_fit(const InrModelDesc* model, float* params, float* opt_state, const
                         workspace, workspace_bytes, (hipStream_t)stream);
     if ((rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef, 1.f);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, w.Pu, *opt, step0);
     if (status) {
         if (hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
@@ -1401,7 +1405,7 @@ int inrfit_cdn_loss_grad(const InrModelDesc* model, const InrFlowDesc* flow, con
     hipStream_t s = (hipStream_t)stream;
     launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);
     launch_flow_fwd(w, grid, n_images, w.xd, s);
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
     if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
     if ((rc = launch_step(e, w.icnn, true, &w.dgrid, targets, loss->kind, n_images, nullptr, s, w.dxd))) return rc;
     launch_reduce(e, w.icnn, n_images, icnn_grads, loss_out, s);
@@ -1425,7 +1429,7 @@ int inrfit_cdn_fit(const InrModelDesc* model, const InrFlowDesc* flow, float* ic
     if (loss->kind == INR_LOSS_EXTERNAL) return INR_EINVAL;
     if ((rc = check_cdn(model, flow, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, icnn_opt_state, w.icnn.Pu, *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
     if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
@@ -1928,7 +1932,7 @@ int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, con
     if ((rc = check_pcn(model, rnvp, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
     hipStream_t s = (hipStream_t)stream;
     launch_rnvp_fwd(w, flow_params, grid, n_images, w.xd, true, s);
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
     if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
     if ((rc = launch_step(e, w.icnn, true, &w.dgrid, targets, loss->kind, n_images, nullptr, s, w.dxd))) return rc;
     launch_reduce(e, w.icnn, n_images, icnn_grads, loss_out, s);
@@ -1952,7 +1956,7 @@ int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* ic
     if (loss->kind == INR_LOSS_EXTERNAL) return INR_EINVAL;
     if ((rc = check_pcn(model, rnvp, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, icnn_opt_state, w.icnn.Pu, *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
     if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
@@ -2072,7 +2076,8 @@ namespace {
 // "frozen" flags cleared (every joint step stands alone), and the data-term coefficients of the prior's step kernel:
 // FBMS: the penalty beta mean((prior - seg)^2) as the SE term against the soft target `seg` with the UNCLIPPED, unscaled
 // coefficient 1/n (joint_step_finish_kernel turns the kernel's own loss column into the clip factor);
-// AWESOME_IMAGE: left to loss_coef_kernel (class weights of the prior criterion from the targets).
+// AWESOME_IMAGE: left to loss_coef_kernel (class weights of the prior criterion from the targets; x gamma alpha with the extra
+// penalty on, where the step kernel's align mode adds the second data term).
 __global__ void joint_prep_kernel(float* hdr, float lr, int t, float* coef, float c, int write_coef) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         hdr[t & 1] = lr;
@@ -2101,14 +2106,36 @@ __global__ __launch_bounds__(256) void joint_step_finish_kernel(const JointFinAr
     float tot[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 5; ++k) tot[SLOT[k]] = jl_block_sum(v[k], sm);
-    float lc = 0.f;   // the prior's share, as the step kernel summed it: FBMS mean((prior - seg)^2); AWESOME_IMAGE mean(w' pcrit)
+    // the prior's share, as the step kernel summed it: FBMS mean((prior - seg)^2); AWESOME_IMAGE mean(w' pcrit), with the extra
+    // penalty on gamma alpha mean(w' pcrit) + beta mean((prior - [seg > 0.5])^2) (the align mode)
+    float lc = 0.f;
     for (int w = threadIdx.x; w < f.wgs; w += 256) lc += f.slabs[(size_t)w * f.PS + f.loss_col];
     const float prior_term = jl_block_sum(lc, sm);
+    const bool align = a.d.form == INR_JOINT_AWESOME_IMAGE && a.pen_on;
+    float pen_sum = 0.f;   // the align term alone (joint_align_partial_kernel), for loss_out[2]
+    if (align) {
+        float v3 = 0.f;
+        for (int b = threadIdx.x; b < a.blocks; b += 256) v3 += a.part[JL_PART * b + 3];
+        pen_sum = jl_block_sum(v3, sm);
+    }
     if (threadIdx.x != 0) return;
     float gs;
     if (a.d.form == INR_JOINT_FBMS) {
         jl_finish(a, tot, prior_term * (float)a.total);     // jl_finish divides the penalty sum by n again
         gs = a.res[3] * a.d.beta;                           // d penalty / d theta = clip * beta * d mean((p - s)^2) / d theta
+    } else if (align) {
+        const float nd = tot[6], nfg = tot[2], g = a.d.gamma;
+        const float w = jl_class_weight(a.d.weight_mode, a.d.ratio, nfg, tot[7]);
+        const float seg_raw = (w * tot[0] + tot[1]) / nd;
+        a.res[0] = g * seg_raw + prior_term;
+        a.res[1] = seg_raw;
+        a.res[2] = pen_sum / (float)a.total;
+        a.res[3] = 1.f;
+        a.res[4] = g * w / nd;
+        a.res[5] = g / nd;
+        a.res[6] = 0.f;                                     // the indicator carries no gradient to seg
+        a.res[7] = nfg;
+        gs = 1.f;                                           // gamma alpha and beta sit in the step kernel's coefficients
     } else {
         const float nd = tot[6], nfg = tot[2];
         const float w = jl_class_weight(a.d.weight_mode, a.d.ratio, nfg, tot[7]);
@@ -2124,7 +2151,7 @@ __global__ __launch_bounds__(256) void joint_step_finish_kernel(const JointFinAr
         gs = a.d.alpha;
     }
     // a non-finite COMPOSITE loss freezes the row: the update kernels read a non-finite gradient scale as "no step" (a NaN in
-    // `seg` does not reach the prior's own loss column in the AWESOME_IMAGE form)
+    // `seg` does not reach the prior's own loss column in the AWESOME_IMAGE form; it reaches res[0] through seg_raw)
     f.gscale[0] = isfinite(a.res[0]) ? gs : __builtin_nanf("");
     if (f.loss_out) {
 #pragma unroll
@@ -2139,6 +2166,8 @@ struct JointCtx {
     float* logits;
     InrLossDesc prior_loss;   // the data term the prior's step kernel evaluates
     const float* prior_targets;
+    const float* align_seg;   // AWESOME_IMAGE with the extra penalty: the step kernel's align mode (seg, beta / n), else null
+    float c_align;
 };
 
 int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float* seg, const float* target, long long N, int step,
@@ -2147,13 +2176,14 @@ int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float
     if (rc) return rc;
     if (!opt || (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) || step < 1) return INR_EINVAL;
     if (desc->form == INR_JOINT_AWESOME_PIXEL) return INR_EUNSUPPORTED;            // pixel mode has no dense-grid prior pass
-    if (desc->form == INR_JOINT_AWESOME_IMAGE && desc->extra_penalty) return INR_EUNSUPPORTED;   // two data terms on the prior
     // the AWESOME_IMAGE prior term runs inside the step kernel, which reads unaries (fg < 0.5) and has no pixel mask
     if (desc->form == INR_JOINT_AWESOME_IMAGE && (desc->target_rule != 0 || desc->use_noneclass)) return INR_EUNSUPPORTED;
     // seg-side sums over the single image: output = seg (channel stride unused), PRIOR = false
     if ((rc = make_joint_args(seg, target, 1, N, desc, nullptr, jws, &c->jl))) return rc;
     c->gscale = c->jl.res + JL_RES;
     c->logits = prior_logits;
+    c->align_seg = nullptr;
+    c->c_align = 0.f;
     hipLaunchKernelGGL(joint_loss_partial_kernel<false>, dim3(c->jl.blocks), dim3(256), 0, s, c->jl);
     const bool fbms = desc->form == INR_JOINT_FBMS;
     hipLaunchKernelGGL(joint_prep_kernel, dim3(1), dim3(64), 0, s, icnn_hdr, opt->lr, step, coef, 1.f / (float)N, fbms ? 1 : 0);
@@ -2163,7 +2193,13 @@ int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float
     } else {
         c->prior_loss = InrLossDesc{desc->prior_kind, desc->prior_weight_mode, desc->prior_ratio, 0.f, 0.f};
         c->prior_targets = target;
-        hipLaunchKernelGGL(loss_coef_kernel, dim3(1), dim3(256), 0, s, target, N, c->prior_loss, coef);
+        float scale = 1.f;
+        if (c->jl.pen_on) {   // loss = gamma (crit(seg) + alpha pcrit(prior)) + beta align: both prior terms in the step kernel
+            scale = desc->gamma * desc->alpha;
+            c->align_seg = seg;
+            c->c_align = desc->beta / (float)N;
+        }
+        hipLaunchKernelGGL(loss_coef_kernel, dim3(1), dim3(256), 0, s, target, N, c->prior_loss, coef, scale);
     }
     return INR_OK;
 }
@@ -2177,6 +2213,7 @@ static void joint_finish(const JointCtx& c, const KernelEntry* e, const Workspac
     f.loss_col = e->img.sl_cols - 1;
     f.gscale = c.gscale;
     f.loss_out = loss_out;
+    if (c.align_seg) hipLaunchKernelGGL(joint_align_partial_kernel, dim3(c.jl.blocks), dim3(256), 0, s, c.jl, (const float*)c.logits);
     hipLaunchKernelGGL(joint_step_finish_kernel, dim3(1), dim3(256), 0, s, f);
 }
 
@@ -2219,7 +2256,7 @@ int inrfit_joint_step(const InrModelDesc* model, float* params, float* opt_state
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
     if ((rc = launch_pack(e, w, params, 1, s))) return rc;
     w.set_step(step);
-    if ((rc = launch_step(e, w, true, grid, c.prior_targets, c.prior_loss.kind, 1, logits, s))) return rc;
+    if ((rc = launch_step(e, w, true, grid, c.prior_targets, c.prior_loss.kind, 1, logits, s, nullptr, c.align_seg, c.c_align))) return rc;
     joint_finish(c, e, w, loss_out, s);
     InrOptDesc o = *opt;
     o.plateau = 0;
@@ -2254,7 +2291,8 @@ int inrfit_pcn_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, fl
     if ((rc = launch_pack(e, w.icnn, icnn_params, 1, s))) return rc;
     w.icnn.set_step(step);
     launch_rnvp_fwd(w, flow_params, grid, 1, w.xd, true, s);
-    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, w.dxd))) return rc;
+    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, w.dxd, c.align_seg,
+                              c.c_align))) return rc;
     joint_finish(c, e, w.icnn, loss_out, s);
     InrOptDesc o = *opt;
     o.plateau = 0;
@@ -2301,7 +2339,8 @@ int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, fl
     w.icnn.set_step(step);
     launch_flow_update(w, flow, 1, 2, flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);  // effective weights
     launch_flow_fwd(w, grid, 1, w.xd, s);
-    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, w.dxd))) return rc;
+    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, w.dxd, c.align_seg,
+                              c.c_align))) return rc;
     joint_finish(c, e, w.icnn, loss_out, s);
     InrOptDesc o = *opt;
     o.plateau = 0;

@@ -177,6 +177,21 @@ __global__ __launch_bounds__(256) void joint_loss_finish_kernel(const JointLossA
     jl_finish(a, tot, tot[3]);
 }
 
+// the fused joint step with AWESOME_IMAGE's extra penalty: the align term's sum on its own (loss_out[2]; the step kernel's loss
+// column holds it mixed with the prior criterion), into part[.][3] of the blocks of joint_loss_partial_kernel<false>, for the
+// finish kernel to combine in fixed order.  p from the step kernel's logits, as joint_loss_grad_kernel<true> computes it.
+__global__ __launch_bounds__(256) void joint_align_partial_kernel(const JointLossArgs a, const float* __restrict__ logits) {
+    __shared__ float sm[4];
+    float pen = 0.f;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < a.total; e += (long long)a.blocks * 256) {
+        const float p = 1.f / (1.f + expf(-logits[e]));
+        const float d = p - (a.output[e] > 0.5f ? 1.f : 0.f);   // one image, es = 1: output[e] is seg
+        pen = fmaf(d, d, pen);
+    }
+    const float r = jl_block_sum(pen, sm);
+    if (threadIdx.x == 0) a.part[JL_PART * blockIdx.x + 3] = r;
+}
+
 // SEG_ONLY: d loss / d seg into a compact [B][n] array (the fused joint step: the prior's gradient never leaves the prior kernels);
 // `prior` then comes from `logits` (the prior's pre-sigmoid output written by the step kernel)
 template <bool SEG_ONLY>

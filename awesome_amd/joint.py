@@ -2,8 +2,12 @@
 
 One call = everything of TorchAgent._perform_step (awesome/agent/torch_agent.py:428-551) that lies behind the segmentation
 network's output, for ONE image: prior forward on this image's parameter row, sigmoid, the composite loss (FBMSJointLoss, or
-AwesomeImageLoss before its extra penalty), d loss / d seg for the backbone, the prior's backward from the activations of that same
-pass, Adam / Adamax + enforce_convexity on the row in place.  Nothing syncs with the host."""
+AwesomeImageLoss before or after its extra penalty), d loss / d seg for the backbone, the prior's backward from the activations of
+that same pass, Adam / Adamax + enforce_convexity on the row in place.  Nothing syncs with the host.
+
+AwesomeImageLoss with `extra_penalty=True` in the desc, loss = gamma (crit(seg, t) + alpha pcrit(prior, t)) + beta
+mean((prior - [seg > 0.5])^2): the prior's step kernel evaluates both of its data terms in the same pass (unaries targets, no
+noneclass); `loss[2]` is then the mean align term before beta and `loss[3]` = 1, as inrfit_joint_loss gives them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,7 +24,7 @@ Tensor = torch.Tensor
 
 @dataclass
 class JointStepResult:
-    loss: Tensor                 # [4] device: loss, mean weighted crit(seg), mean penalty, clip factor
+    loss: Tensor                 # [4] device: loss, mean weighted crit(seg), mean penalty / align term, clip factor
     dseg: Tensor                 # [N] d loss / d seg
     prior_logits: Tensor         # [N] the prior's pre-sigmoid output of this step's forward
     status: Tensor               # [1] int32: 1 = non-finite loss, nothing was updated

@@ -381,9 +381,11 @@ int inrfit_joint_loss(const float* output, const float* target, int batch, int64
  * by passing the same opt_state with every row and `step` = the global step count; a state per row with its own count is the
  * per-image variant.  `step` >= 1 is torch's state['step'] after this step (bias corrections); the learning rate is opt->lr (host
  * schedulers stay on the host), opt->plateau is ignored.  A non-finite loss leaves the row untouched and sets *status (optional).
- * Forms: INR_JOINT_FBMS (any target rule / noneclass: the prior's term has no targets), and INR_JOINT_AWESOME_IMAGE while
- * extra_penalty is off (with it on the prior has two data terms: use inrfit_joint_loss + inrfit_backward) on unaries without a
- * noneclass (its prior term is evaluated by the step kernel, which reads unaries); otherwise INR_EUNSUPPORTED.
+ * Forms: INR_JOINT_FBMS (any target rule / noneclass: the prior's term has no targets), and INR_JOINT_AWESOME_IMAGE with
+ * extra_penalty off or on, on unaries without a noneclass (its prior terms are evaluated by the step kernel, which reads unaries:
+ * with the penalty on, the class-weighted criterion against the targets AND the align term against [seg > 0.5] in the same pass);
+ * otherwise INR_EUNSUPPORTED (INR_JOINT_AWESOME_PIXEL always).  With the penalty on, loss_out[2] is the mean align term before
+ * beta and loss_out[3] = 1, as inrfit_joint_loss gives them.
  * A non-finite COMPOSITE loss (a NaN in `seg` as much as in the prior) freezes the row.
  * How the clip stays on the device with a single prior pass: the prior's gradient is linear in the penalty's coefficient, so the step
  * kernel runs with the unclipped coefficient, its own loss column gives the penalty, and the update kernel multiplies the reduced

@@ -168,9 +168,9 @@ def main(cfg):
     # unless `agent_args.pretrain_only` is set (awesome_runner.py:318-340 trains `num_epochs` after the agent's pretraining)
     agent_args = dict(cfg.agent_args or {})
     joint_epochs = int(agent_args.get("joint_epochs", 0 if agent_args.get("pretrain_only", True) else cfg.num_epochs))
-    report, joint_losses, error = [], [], None
+    report, joint_losses, fused_steps, error = [], [], {}, None
     try:                                        # rank-local work: an exception here must not strand the other ranks (below)
-        report, joint_losses = _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args, opt_args, device, joint_epochs)
+        report, joint_losses, fused_steps = _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args, opt_args, device, joint_epochs)
     except Exception as err:   # noqa: BLE001 - reported, agreed on by all ranks, and turned into a non-zero exit
         import traceback
         traceback.print_exc()
@@ -192,6 +192,7 @@ def main(cfg):
         f32 = lambda xs: torch.tensor(xs, dtype=torch.float32, device=device).reshape(len(mine))  # noqa: E731
         iou = f32([0.0 if r["skipped"] else r["iou"] for r in report])
         retries = f32([r["retries"] for r in report])
+        fused = f32([fused_steps.get(k, 0) for k in mine])
         gt_iou = noisy_iou = None
         if hasattr(ds, "ground_truth_batch") and dataset_args.get("kind") == "noisy_blob":
             # refinement configs: score the fitted prior (and the input labels) against the clean mask
@@ -222,6 +223,7 @@ def main(cfg):
         raise SystemExit(1)
     iou_all = parallel.gather_per_image(iou, len(ds), rank, world)
     retries_all = parallel.gather_per_image(retries, len(ds), rank, world)
+    fused_all = parallel.gather_per_image(fused, len(ds), rank, world)
     if gt_iou is not None:
         gt_all = parallel.gather_per_image(gt_iou, len(ds), rank, world)
         noisy_all = parallel.gather_per_image(noisy_iou, len(ds), rank, world)
@@ -256,6 +258,7 @@ def main(cfg):
         if joint_losses:
             summary["joint_epochs"] = joint_epochs
             summary["joint_loss_first_last"] = [round(joint_losses[0], 6), round(joint_losses[-1], 6)]
+            summary["joint_steps_fused"] = int(fused_all.sum())   # joint steps that took the fused path (JointTrainer)
             if cfg.get("use_extra_penalty_hook"):
                 summary["extra_penalty"] = bool(getattr(criterion, "extra_penalty", False))
         with open(os.path.join(out_dir, "summary.json"), "w") as f:
@@ -265,7 +268,8 @@ def main(cfg):
 
 
 def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args, opt_args, device, joint_epochs):
-    """This rank's share of the work: the per-image pretrain fits, then the joint-training epochs.  -> (report, joint_losses)"""
+    """This rank's share of the work: the per-image pretrain fits, then the joint-training epochs.
+    -> (report, joint_losses, {image: joint steps that took the fused path})"""
     import torch
     from awesome_amd.model import WrapperModule
     report = []
@@ -275,7 +279,7 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
     # ---- joint training epochs (TorchAgent._perform_step, torch_agent.py:428-551): segmentation module + per-image priors +
     # the composite loss (FBMSJointLoss / AwesomeImageLoss), the priors resident on the device in a PriorBank.  Each rank trains
     # its own copy of the segmentation stand-in on its shard (sharing a backbone over ranks is ordinary DDP, out of scope §8e).
-    joint_losses = []
+    joint_losses, fused_steps = [], {}
     if joint_epochs > 0 and mine and criterion is not None and not _fusable(criterion):
         from awesome_amd.agent import JointTrainer
         from awesome_amd.prior_bank import PriorBank
@@ -295,7 +299,8 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
         params = [p for p in seg.parameters()] + bank_params(prior)
         opt_cls = cfg.optimizer_type if not isinstance(cfg.optimizer_type, str) else dynamic_import(cfg.optimizer_type)
         opt = opt_cls(params, **opt_args)       # awesome_runner.py:246-252: optimizer_type(**optimizer_args)
-        trainer = JointTrainer(jw, bank, criterion, opt)
+        # agent_args.fused_extra_penalty (opt-in): AwesomeImageLoss steps after the extra-penalty hook stay on the fused path
+        trainer = JointTrainer(jw, bank, criterion, opt, fused_extra_penalty=bool((cfg.agent_args or {}).get("fused_extra_penalty", False)))
         for epoch in range(joint_epochs):
             # the runner's extra-penalty hook (awesome/run/awesome_runner.py:351-371; config fields awesome_config.py:164-173): from
             # epoch N on the loss adds its penalty term, optionally with the learning rate scaled once
@@ -310,13 +315,14 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
                 (_, _), ((image, feat, xy), target) = ds[k]
                 loss, _ = trainer.perform_step(k, (image[None].to(device), feat[None].to(device), xy[None].to(device)),
                                                target[None].to(device))
+                fused_steps[k] = fused_steps.get(k, 0) + (trainer._path == "fused")
                 acc = acc + loss
             trainer.raise_if_failed()          # ValueError("Loss is nan or inf!") like the reference, one sync per epoch
             joint_losses.append(float(acc) / len(mine))
         for k in mine:   # the jointly trained priors replace the pretrained ones in the cache
             with bank.manager(prior, k):
                 cache0[k] = {n: v.detach().cpu().clone() for n, v in prior.state_dict().items()}
-    return report, joint_losses
+    return report, joint_losses, fused_steps
 
 
 def bank_params(prior):
