@@ -67,6 +67,15 @@ class InrJointLossDesc(C.Structure):
 JOINT_FBMS, JOINT_AWESOME_IMAGE, JOINT_AWESOME_PIXEL = 0, 1, 2
 
 
+class InrJointPriorDesc(C.Structure):   # inrfit_joint_prior_step: the prior's share of a joint step
+    _fields_ = [("kind", C.c_int32), ("weight_mode", C.c_int32), ("ratio", C.c_float), ("use_noneclass", C.c_int32),
+                ("noneclass", C.c_float), ("data_count", C.c_int64), ("c_data", C.c_float), ("align_rule", C.c_int32),
+                ("beta", C.c_float), ("align_begin", C.c_int64)]
+
+
+ALIGN_NONE, ALIGN_HARD, ALIGN_SOFT = 0, 1, 2
+
+
 class InrStarDesc(C.Structure):
     _fields_ = [("n_hidden", C.c_int32)]
 
@@ -145,6 +154,9 @@ EXPORTS = {
     "inrfit_joint_step": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p, C.c_void_p,
                                     C.POINTER(InrJointLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_joint_prior_step": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p,
+                                          C.c_void_p, C.POINTER(InrJointPriorDesc), C.c_void_p, C.POINTER(InrOptDesc), C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_pcn_joint_step": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrRnvpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(InrGridDesc), C.c_void_p, C.c_void_p, C.POINTER(InrJointLossDesc),
                                         C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

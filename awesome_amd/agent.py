@@ -129,11 +129,19 @@ class JointTrainer:
 
     `fused_extra_penalty` (opt-in, default False): AwesomeImageLoss steps with `extra_penalty` on (the runner's hook flips it in
     mid-run) also take the fused path, where the prior's step kernel evaluates both of its data terms - the weighted criterion
-    against the targets and the align term against [seg > 0.5] - in one pass.  Off, those steps take the autograd path."""
+    against the targets and the align term against [seg > 0.5] - in one pass.  Off, those steps take the autograd path.
+
+    `fused_convexity_losses` (opt-in, default False): the convexity benchmark's losses (AwesomeImageLoss, AwesomeImageLossJoint,
+    AwesomeLoss, AwesomeLossJoint) on an ICNN prior take a fused path in every phase, wherever the step above refuses them, for ANY
+    segmentation criterion (GradientPenaltyLoss's second-order penalty included): the segmentation share g crit(seg, t) is evaluated
+    in torch exactly as the class does, and `inrfit_joint_prior_step` evaluates the prior's share (its masked data term and the hard
+    / soft align term), steps the row and returns d(prior's share) / d seg (measures.losses.convexity_joint_form).  Pixel mode
+    (input_mode='pixel', coordinates pre-attached) included; a step whose prior criterion has no kernel form, or without scribble
+    pixels, takes the autograd path."""
 
     def __init__(self, wrapper: torch.nn.Module, bank: PriorBank, criterion: Callable, optimizer: torch.optim.Optimizer,
                  fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch",
-                 fused_extra_penalty: bool = False):
+                 fused_extra_penalty: bool = False, fused_convexity_losses: bool = False):
         if check_finite not in ("step", "epoch"):
             raise ValueError("check_finite: 'step' (raise before backward like the reference, one host sync per step) or 'epoch' "
                              "(device flag, the caller polls raise_if_failed())")
@@ -142,6 +150,7 @@ class JointTrainer:
         self.forward_additional_loss_args = _loss_takes_input(criterion)
         self.shared_prior_moments = bool(shared_prior_moments)
         self.fused_extra_penalty = bool(fused_extra_penalty)
+        self.fused_convexity_losses = bool(fused_convexity_losses)
         self._fused_plan = self._plan_fused()
         if fused and self._fused_plan is None:
             raise ValueError("this combination of prior module / criterion / optimizer has no fused joint step")
@@ -248,8 +257,14 @@ class JointTrainer:
         else:
             return None
         if not hasattr(self.criterion, "joint_desc") or self.criterion.joint_desc() is None:
-            return None
+            if not self._convexity_applies(family):
+                return None
         return dict(kind=kind, group=groups[0], family=family, ispec=ispec, dspec=dspec)
+
+    def _convexity_applies(self, family: str) -> bool:
+        """fused_convexity_losses: one of the convexity benchmark's losses on an ICNN prior (inrfit_joint_prior_step)."""
+        from .measures.losses import CONVEXITY_LOSSES
+        return self.fused_convexity_losses and family == "icnn" and isinstance(self.criterion, CONVEXITY_LOSSES)
 
     def _state_for(self, key: Any, plan) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         k = None if self.shared_prior_moments else key
@@ -267,15 +282,12 @@ class JointTrainer:
         from . import icnn as K
         from . import joint as J
         plan, w = self._fused_plan, self.wrapper
-        desc = self.criterion.joint_desc()
+        desc = self.criterion.joint_desc() if hasattr(self.criterion, "joint_desc") else None
         g = plan["group"]
-        if desc is None or (plan["family"] != "icnn" and float(g.get("weight_decay", 0.0)) != 0.0):
+        if not self._joint_desc_fusable(desc, plan):
+            if self._convexity_applies(plan["family"]):
+                return self._perform_step_prior_share(key, inputs, labels)
             return None
-        if desc.form != 0 and (desc.form != 1 or desc.target_rule or desc.use_noneclass):
-            return None   # the pixel form; AwesomeImageLoss on class labels or with a noneclass (inrfit_joint_step: INR_EUNSUPPORTED)
-        if desc.form == 1 and desc.extra_penalty and not self.fused_extra_penalty:
-            return None   # AwesomeImageLoss with its extra penalty on: the autograd step unless asked for (the desc is read every
-                          # step, so gamma / alpha / beta and the hook's switch take effect at once)
         xi = inputs[0] if inputs[0].dim() == 4 else inputs[0][None]
         if xi.shape[0] != 1:
             return None
@@ -319,6 +331,91 @@ class JointTrainer:
             seg.backward(res.dseg.view_as(seg))
         self.optimizer.step()                                                  # segmentation parameters only
         out = torch.cat([seg.detach(), torch.sigmoid(res.prior_logits).view_as(seg)], dim=0)[None]
+        return res.loss[0], out
+
+    def _joint_desc_fusable(self, desc, plan) -> bool:
+        """Whether inrfit_joint_step (and its path-connected variants) take this step's composite loss."""
+        if desc is None or (plan["family"] != "icnn" and float(plan["group"].get("weight_decay", 0.0)) != 0.0):
+            return False
+        if desc.form != 0 and (desc.form != 1 or desc.target_rule or desc.use_noneclass):
+            return False  # the pixel form; AwesomeImageLoss on class labels or with a noneclass (inrfit_joint_step: INR_EUNSUPPORTED)
+        if desc.form == 1 and desc.extra_penalty and not self.fused_extra_penalty:
+            return False  # AwesomeImageLoss with its extra penalty on: the autograd step unless asked for (the desc is read every
+                          # step, so gamma / alpha / beta and the hook's switch take effect at once)
+        return True
+
+    def _perform_step_prior_share(self, key: Any, inputs: Sequence[torch.Tensor], labels: torch.Tensor):
+        """fused_convexity_losses: g crit(seg, t) in torch + inrfit_joint_prior_step for the prior's share, one backward through the
+        segmentation network for both (torch.autograd.backward([seg_term, seg], [None, dseg])).  None -> the autograd step."""
+        from . import _lib as L
+        from . import icnn as K
+        from . import joint as J
+        from .measures.losses import convexity_joint_form, convexity_seg_share
+        plan, w, crit = self._fused_plan, self.wrapper, self.criterion
+        g = plan["group"]
+        pixel = getattr(w, "input_mode", "image") == "pixel"
+        if pixel:       # WrapperModule._forward_pixels: _input (img, n, F) or (n, F), the coordinates are its first two features
+            if w.prior_arg_mode != "xy_c_preattached":
+                return None
+            x0, rest = inputs[0], tuple(inputs[1:])
+            if x0.dim() == 2:
+                x0 = x0[None]
+                rest = tuple(a[None] if isinstance(a, torch.Tensor) and a.dim() == 2 else a for a in rest)
+            if x0.dim() != 3 or x0.shape[0] != 1:
+                return None
+            xi, ai = x0[0], tuple(a[0] if isinstance(a, torch.Tensor) else a for a in rest)
+            n = xi.shape[0]
+        else:
+            xi = inputs[0] if inputs[0].dim() == 4 else inputs[0][None]
+            if xi.shape[0] != 1:
+                return None
+            ai = tuple(a if not isinstance(a, torch.Tensor) or a.dim() == 4 else a[None] for a in inputs[1:])
+            n = xi.shape[-2] * xi.shape[-1]
+        form = convexity_joint_form(crit, n)
+        if form is None or form.pixel != pixel or labels.numel() != (form.data_count or n):
+            return None
+        self._hand_over("fused")
+        self.optimizer.zero_grad()
+        seg = w.segmentation_output(xi, ai)                                   # image (1, H, W) / pixel (n, 1), autograd attached
+        kw = {"_input": list(inputs)} if self.forward_additional_loss_args else {}
+        seg_term = convexity_seg_share(crit, form, seg[None], labels, **kw)  # the class's own view of the segmentation channel
+        pa, _ = w.get_prior_args(xi, *ai, segm=seg)
+        coords = pa[0]
+        if pixel:
+            coords = coords.reshape(-1, coords.shape[-1]).t()                  # (n, 2) -> (2, n)
+        else:
+            coords = coords[0] if coords.dim() == 4 else coords
+            coords = coords.reshape(coords.shape[0], -1)
+        grid = K.Grid.explicit(coords.to(torch.float32).contiguous())
+        row = self.bank.row(key)
+        kc = None if self.shared_prior_moments else key
+        t = self._t[kc] = self._t.get(kc, 0) + 1
+        iopt, _ = self._state_for(key, plan)
+        segd = seg.detach().reshape(-1).to(torch.float32).contiguous()
+        tgt = labels.detach().reshape(-1).to(torch.float32).contiguous()
+        st = seg_term.detach().reshape(1).to(torch.float32).contiguous()
+        res = J.joint_prior_step(plan["ispec"], row, iopt, grid, segd, tgt, form.prior_desc(), step=t, lr=float(g["lr"]),
+                                 seg_term=st, optimizer=plan["kind"], betas=tuple(g.get("betas", (0.9, 0.999))),
+                                 eps=float(g.get("eps", 1e-8)), weight_decay=float(g.get("weight_decay", 0.0)), clamp=True)
+        self.last_status = res.status
+        self.failed |= res.status.reshape(-1)[0] != 0                         # see _perform_step_fused
+        if self.check_finite == "step":
+            self.raise_if_failed()
+        roots, grads = [], []
+        if seg_term.requires_grad:
+            roots.append(seg_term)
+            grads.append(None)
+        if form.align_rule == L.ALIGN_SOFT and seg.requires_grad:     # hard / none: d(prior's share) / d seg = 0
+            roots.append(seg)
+            grads.append(res.dseg.view_as(seg))
+        if roots:
+            torch.autograd.backward(roots, grads)
+        self.optimizer.step()                                                  # segmentation parameters only
+        prior = torch.sigmoid(res.prior_logits)
+        if pixel:
+            out = torch.cat([seg.detach(), prior.view_as(seg)], dim=-1)[None]
+        else:
+            out = torch.cat([seg.detach(), prior.view_as(seg)], dim=0)[None]
         return res.loss[0], out
 
     # -- the step ------------------------------------------------------------------------------------------------------------

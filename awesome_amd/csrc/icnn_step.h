@@ -254,6 +254,12 @@ struct StepArgs {
     float act_omega;       // INR_ACT_SIN kernels
     const float* seg;      // [n_images][N] or null (TRAIN): the align mode of the fused joint step, see align_term
     float c_align;         // its coefficient
+    // the data-term mask of inrfit_joint_prior_step (every other caller: data_count = N, no noneclass, hard align from 0)
+    int data_count;        // points p >= data_count carry no data term; targets hold data_count values per image
+    int use_noneclass;     // points whose target equals `noneclass` carry no data term either
+    float noneclass;
+    int align_soft;        // align against s itself instead of [s > 0.5]
+    int align_begin;       // the align term applies to points p >= align_begin
 };
 
 // Cross-lane sums on the VALU (DPP / permlane swaps): no LDS round trip, no s_waitcnt.
@@ -273,8 +279,10 @@ __device__ __forceinline__ float bce_log(float x) {
 // gradient; the comparison is strict, so a NaN in s counts as 0 like torch's (nan > 0.5).  With cw = gamma alpha w' / n_d (the
 // coefficients) and c_align = beta / N, the loss column is the prior's whole share of the composite loss and the gradient scale is 1.
 // The read sits at the data term, inside the mode's branch: no register held across the chunk loop in any other mode.
-__device__ __forceinline__ void align_term(const float* __restrict__ seg, float c_align, float pr, float& l, float& dy) {
-    const float d = pr - (*seg > 0.5f ? 1.f : 0.f);
+// `soft` (AwesomeImageLossJoint / AwesomeLossJoint, inrfit_joint_prior_step): d = p - s, a NaN in s reaches the loss column.
+__device__ __forceinline__ void align_term(const float* __restrict__ seg, float c_align, int soft, float pr, float& l, float& dy) {
+    const float s = *seg;
+    const float d = pr - (soft ? s : (s > 0.5f ? 1.f : 0.f));
     const float cd = c_align * d;
     l = fmaf(cd, d, l);
     dy = fmaf(2.f * cd, pr * (1.f - pr), dy);
@@ -492,7 +500,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 #pragma unroll
             for (int c = 0; c < C; ++c) q.x[c] = cp[(size_t)c * N + pc];
         }
-        q.tg = TRAIN ? a.targets[(size_t)img * N + pc] : 0.f;
+        q.tg = TRAIN ? a.targets[(size_t)img * a.data_count + min(pc, a.data_count - 1)] : 0.f;   // never past the targets
         return q;
     };
     PointIn nxt = load_point(wg);
@@ -673,7 +681,11 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 const float pq = pr * (1.f - pr);
                 dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
             }
-            if (a.seg != nullptr && valid) align_term(a.seg + (size_t)img * N + p, a.c_align, pr, l, dy);
+            if (p >= a.data_count || (a.use_noneclass && tg == a.noneclass)) {   // a select: a NaN prior there stays out of the sum
+                l = 0.f;
+                dy = 0.f;
+            }
+            if (a.seg != nullptr && valid && p >= a.align_begin) align_term(a.seg + (size_t)img * N + p, a.c_align, a.align_soft, pr, l, dy);
             if (!valid) {
                 l = 0.f;
                 dy = 0.f;

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn2_step_kernel(const StepArg
 #pragma unroll
             for (int c = 0; c < C; ++c) q.x[c] = cp[(size_t)c * N + pc];
         }
-        q.tg = TRAIN ? a.targets[(size_t)img * N + pc] : 0.f;
+        q.tg = TRAIN ? a.targets[(size_t)img * a.data_count + min(pc, a.data_count - 1)] : 0.f;   // never past the targets
         return q;
     };
     PointIn nxt = load_point(wg);
@@ -475,7 +475,11 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn2_step_kernel(const StepArg
                 const float pq = pr * (1.f - pr);
                 dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
             }
-            if (a.seg != nullptr && valid) align_term(a.seg + (size_t)img * N + p, a.c_align, pr, l, dy);
+            if (p >= a.data_count || (a.use_noneclass && tg == a.noneclass)) {   // a select: a NaN prior there stays out of the sum
+                l = 0.f;
+                dy = 0.f;
+            }
+            if (a.seg != nullptr && valid && p >= a.align_begin) align_term(a.seg + (size_t)img * N + p, a.c_align, a.align_soft, pr, l, dy);
             if (!valid) {
                 l = 0.f;
                 dy = 0.f;

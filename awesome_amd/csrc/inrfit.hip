@@ -6,6 +6,8 @@
 //                      gradient slab.  Replaces ConvexNextNet.forward + criterion + loss.backward()
 //                      (awesome/model/convex_net.py:205-214, awesome/measures/weighted_loss.py:67-92,
 //                      awesome/model/path_connected_net.py:941-948).
+//                      The same kernel is the prior's share of the convexity losses' joint step (inrfit_joint_prior_step):
+//                      a data-term mask (data_count, noneclass) and a hard / soft align term, all run-time StepArgs fields.
 //   icnn_update_kernel fixed-order slab reduction + Adam/Adamax + enforce_convexity clamp + ReduceLROnPlateau
 //                      (torch.optim.Adam/Adamax; convex_net.py:151-154,216-220; path_connected_net.py:949-951).
 //
@@ -348,21 +350,35 @@ __global__ __launch_bounds__(256) void pack_params_kernel(const float* __restric
 }
 
 // per-image loss coefficients (c_fg, c_bg): 'mean' normalisation x UnariesWeightedLoss class weight x `scale` (1, or the fused joint
-// step's gamma alpha in the align mode)
+// step's gamma alpha in the align mode).  `use_noneclass`: targets equal to `noneclass` leave before the criterion (weighted_loss.py
+// :71-74), so N counts, and the class weight is taken over, only the others (inrfit_joint_prior_step; everyone else passes 0).
 __global__ __launch_bounds__(256) void loss_coef_kernel(const float* __restrict__ targets, long long N, InrLossDesc loss,
-                                                        float* __restrict__ coef, float scale) {
+                                                        float* __restrict__ coef, float scale, int use_noneclass = 0,
+                                                        float noneclass = 0.f) {
     const int img = blockIdx.x;
-    __shared__ unsigned long long cnt[4];
-    unsigned long long fg = 0;
-    if (loss.weight_mode != INR_WEIGHT_NONE && loss.weight_mode != INR_WEIGHT_EXPLICIT) {
+    __shared__ unsigned long long cnt[4], cnt_nc[4];
+    unsigned long long fg = 0, nc = 0;
+    const bool weighted = loss.weight_mode != INR_WEIGHT_NONE && loss.weight_mode != INR_WEIGHT_EXPLICIT;
+    if (weighted || use_noneclass) {
         const float* t = targets + (size_t)img * N;
-        for (long long i = threadIdx.x; i < N; i += blockDim.x) fg += t[i] < 0.5f ? 1ull : 0ull;
-        for (int o = 32; o > 0; o >>= 1) fg += __shfl_xor(fg, o);
-        if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = fg;
+        for (long long i = threadIdx.x; i < N; i += blockDim.x) {
+            const bool drop = use_noneclass && t[i] == noneclass;
+            fg += !drop && t[i] < 0.5f ? 1ull : 0ull;
+            nc += drop ? 1ull : 0ull;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            fg += __shfl_xor(fg, o);
+            nc += __shfl_xor(nc, o);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            cnt[threadIdx.x >> 6] = fg;
+            cnt_nc[threadIdx.x >> 6] = nc;
+        }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         float cfg, cbg;
+        if (use_noneclass) N -= (long long)(cnt_nc[0] + cnt_nc[1] + cnt_nc[2] + cnt_nc[3]);   // the valid points
         const float inv_n = 1.f / (float)N;
         if (loss.weight_mode == INR_WEIGHT_EXPLICIT) {
             cfg = loss.c_fg;
@@ -701,13 +717,27 @@ static int launch_pack(const KernelEntry* e, const Workspace& w, const float* pa
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
+// the data-term mask and align rule of inrfit_joint_prior_step; the default is what every other caller runs (all points, hard align)
+struct StepMask {
+    long long data_count = 0;   // 0 = all points
+    int use_noneclass = 0;
+    float noneclass = 0.f;
+    int align_soft = 0;
+    long long align_begin = 0;
+};
+
 static int launch_step(const KernelEntry* e, const Workspace& w, bool train, const InrGridDesc* grid, const float* targets,
                        int loss_kind, int n_images, float* logits, hipStream_t s, float* dcoords = nullptr,
-                       const float* align_seg = nullptr, float c_align = 0.f) {
+                       const float* align_seg = nullptr, float c_align = 0.f, const StepMask& mask = StepMask{}) {
     StepArgs a{};
     a.dcoords = dcoords;
     a.seg = align_seg;
     a.c_align = c_align;
+    a.data_count = (int)(mask.data_count > 0 ? mask.data_count : grid->n_points);
+    a.use_noneclass = mask.use_noneclass;
+    a.noneclass = mask.noneclass;
+    a.align_soft = mask.align_soft;
+    a.align_begin = (int)mask.align_begin;
     a.wimg = w.wimg;
     a.targets = targets;
     a.coef = w.coef;
@@ -2360,6 +2390,184 @@ int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, fl
                            c.gscale);
     }
     joint_dseg(c, dseg, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the prior's share of a joint step (include/inrfit.h: inrfit_joint_prior_step); the segmentation share stays with the caller
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct PriorShareArgs {
+    const float* logits;    // the step kernel's pre-sigmoid output of this step
+    const float* seg;
+    const float* targets;   // [data_count]
+    const float* coef;      // c_fg, c_bg (loss_coef_kernel: c_data / n_valid x class weight)
+    long long N, data_count, align_begin;
+    int kind, use_noneclass, align_rule;
+    float noneclass;
+    float* part;            // [blocks][2]: data term, raw align sum
+    int blocks;
+};
+
+// loss_out[1] and [2] on their own (the step kernel's loss column holds them mixed), per block, for the finish kernel to combine in
+// fixed order.  The data term repeats the step kernel's arithmetic on its logits; masked points are skipped, not multiplied by 0.
+__global__ __launch_bounds__(256) void joint_prior_partial_kernel(const PriorShareArgs a) {
+    __shared__ float sm[4];
+    float ld = 0.f, la = 0.f;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < a.N; e += (long long)a.blocks * 256) {
+        const float p = 1.f / (1.f + expf(-a.logits[e]));
+        if (e < a.data_count) {
+            const float t = a.targets[e];
+            if (!(a.use_noneclass && t == a.noneclass)) {
+                const float cw = t < 0.5f ? a.coef[0] : a.coef[1];
+                if (a.kind == INR_LOSS_SE) {
+                    const float d = t - p;
+                    ld += d * d * cw;
+                } else {
+                    ld += -(t * bce_log(p) + (1.f - t) * bce_log(1.f - p)) * cw;
+                }
+            }
+        }
+        if (a.align_rule != INR_ALIGN_NONE && e >= a.align_begin) {
+            const float s = a.seg[e];
+            const float d = p - (a.align_rule == INR_ALIGN_SOFT ? s : (s > 0.5f ? 1.f : 0.f));
+            la = fmaf(d, d, la);
+        }
+    }
+    const float r0 = jl_block_sum(ld, sm);
+    const float r1 = jl_block_sum(la, sm);
+    if (threadIdx.x == 0) {
+        a.part[2 * blockIdx.x] = r0;
+        a.part[2 * blockIdx.x + 1] = r1;
+    }
+}
+
+struct PriorFinArgs {
+    const float* part;
+    int blocks;
+    const float* slabs;     // the step kernel's gradient slabs of this step [wgs][PS]
+    int wgs, PS, loss_col;
+    const float* seg_term;  // [1] or null
+    float n_align;          // 0 without an align term
+    float* gscale;          // [1] -> the update kernel
+    float* loss_out;        // [4] or null
+};
+
+__global__ __launch_bounds__(256) void joint_prior_finish_kernel(const PriorFinArgs f) {
+    __shared__ float sm[4];
+    float v0 = 0.f, v1 = 0.f, lc = 0.f;
+    for (int b = threadIdx.x; b < f.blocks; b += 256) {
+        v0 += f.part[2 * b];
+        v1 += f.part[2 * b + 1];
+    }
+    for (int w = threadIdx.x; w < f.wgs; w += 256) lc += f.slabs[(size_t)w * f.PS + f.loss_col];
+    const float data = jl_block_sum(v0, sm);
+    const float align = jl_block_sum(v1, sm);
+    const float prior_term = jl_block_sum(lc, sm);   // the prior's whole share, as the step kernel summed it
+    if (threadIdx.x != 0) return;
+    const float total = (f.seg_term ? f.seg_term[0] : 0.f) + prior_term;
+    // a non-finite COMPOSITE loss freezes the row: the update kernel reads a non-finite gradient scale as "no step"
+    const float gs = isfinite(total) ? 1.f : __builtin_nanf("");
+    f.gscale[0] = gs;
+    if (f.loss_out) {
+        f.loss_out[0] = total;
+        f.loss_out[1] = data;
+        f.loss_out[2] = f.n_align > 0.f ? align / f.n_align : 0.f;
+        f.loss_out[3] = gs;
+    }
+}
+
+// d(prior's share) / d seg: the soft align's -2 beta (p - s) / n_align on [align_begin, N), 0 everywhere else
+__global__ __launch_bounds__(256) void joint_prior_dseg_kernel(const float* __restrict__ logits, const float* __restrict__ seg, long long N,
+                                                               long long align_begin, int soft, float c, float* __restrict__ dseg) {
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long long)gridDim.x * 256) {
+        float d = 0.f;
+        if (soft && e >= align_begin) d = c * (1.f / (1.f + expf(-logits[e])) - seg[e]);
+        dseg[e] = d;
+    }
+}
+
+}  // namespace
+
+int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                            const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
+                            int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
+    if (!opt || (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) || step < 1) return INR_EINVAL;
+    if (desc->kind != INR_LOSS_SE && desc->kind != INR_LOSS_BCE) return INR_EINVAL;
+    if (desc->weight_mode < INR_WEIGHT_NONE || desc->weight_mode > INR_WEIGHT_SSSDMS) return INR_EINVAL;
+    if (desc->align_rule < INR_ALIGN_NONE || desc->align_rule > INR_ALIGN_SOFT) return INR_EINVAL;
+    const KernelEntry* e;
+    Workspace w;
+    int rc = prepare(model, grid, 1, workspace, workspace_bytes, &e, &w);   // no fused kernel for this shape: INR_EUNSUPPORTED
+    if (rc) return rc;
+    const long long N = grid->n_points;
+    const long long data_count = desc->data_count > 0 ? desc->data_count : N;
+    if (desc->data_count < 0 || data_count > N) return INR_EINVAL;
+    const bool align = desc->align_rule != INR_ALIGN_NONE;
+    if (align && (desc->align_begin < 0 || desc->align_begin >= N)) return INR_EINVAL;
+    if (workspace_bytes < inrfit_joint_step_workspace_bytes(model, grid)) return INR_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float* jws = (float*)((char*)workspace + align256(w.bytes));
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
+    float* hdr = opt_state + 2 * (size_t)w.Pu;
+    const long long n_align = align ? N - desc->align_begin : 0;
+    hipLaunchKernelGGL(joint_prep_kernel, dim3(1), dim3(64), 0, s, hdr, opt->lr, step, w.coef, 0.f, 0);
+    const InrLossDesc pl{desc->kind, desc->weight_mode, desc->ratio, 0.f, 0.f};
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(1), dim3(256), 0, s, target, data_count, pl, w.coef, desc->c_data, desc->use_noneclass,
+                       desc->noneclass);
+    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
+    if ((rc = launch_pack(e, w, params, 1, s))) return rc;
+    w.set_step(step);
+    StepMask m;
+    m.data_count = data_count;
+    m.use_noneclass = desc->use_noneclass ? 1 : 0;
+    m.noneclass = desc->noneclass;
+    m.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
+    m.align_begin = align ? desc->align_begin : 0;
+    if ((rc = launch_step(e, w, true, grid, target, desc->kind, 1, logits, s, nullptr, align ? seg : nullptr,
+                          align ? desc->beta / (float)n_align : 0.f, m))) return rc;
+    PriorShareArgs pa{};
+    pa.logits = logits;
+    pa.seg = seg;
+    pa.targets = target;
+    pa.coef = w.coef;
+    pa.N = N;
+    pa.data_count = data_count;
+    pa.align_begin = m.align_begin;
+    pa.kind = desc->kind;
+    pa.use_noneclass = m.use_noneclass;
+    pa.align_rule = desc->align_rule;
+    pa.noneclass = desc->noneclass;
+    pa.part = jws;
+    const long long want = (N + 1023) / 1024;
+    pa.blocks = (int)(want < 1 ? 1 : (want > JL_MAX_BLOCKS ? JL_MAX_BLOCKS : want));   // 2 x blocks <= the JL_PART x JL_MAX_BLOCKS floats
+    hipLaunchKernelGGL(joint_prior_partial_kernel, dim3(pa.blocks), dim3(256), 0, s, pa);
+    PriorFinArgs f{};
+    f.part = jws;
+    f.blocks = pa.blocks;
+    f.slabs = w.slabs;
+    f.wgs = w.wgs;
+    f.PS = w.PS;
+    f.loss_col = e->img.sl_cols - 1;
+    f.seg_term = seg_term;
+    f.n_align = (float)n_align;
+    f.gscale = gscale;
+    f.loss_out = loss_out;
+    hipLaunchKernelGGL(joint_prior_finish_kernel, dim3(1), dim3(256), 0, s, f);
+    InrOptDesc o = *opt;
+    o.plateau = 0;
+    UpdArgs u = make_upd_args(e, w, params, opt_state, nullptr, status, &o, 1, 1);
+    u.slabs = w.slabs;
+    u.gscale = gscale;
+    set_step_consts(u, &o, step);
+    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, 1), upd_block(e->img.sl_cols), 0, s, u);
+    const bool soft = desc->align_rule == INR_ALIGN_SOFT;
+    hipLaunchKernelGGL(joint_prior_dseg_kernel, dim3(pa.blocks), dim3(256), 0, s, (const float*)logits, seg, N, m.align_begin, soft ? 1 : 0,
+                       soft ? -2.f * desc->beta / (float)n_align : 0.f, dseg);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 

@@ -7,7 +7,11 @@ that same pass, Adam / Adamax + enforce_convexity on the row in place.  Nothing 
 
 AwesomeImageLoss with `extra_penalty=True` in the desc, loss = gamma (crit(seg, t) + alpha pcrit(prior, t)) + beta
 mean((prior - [seg > 0.5])^2): the prior's step kernel evaluates both of its data terms in the same pass (unaries targets, no
-noneclass); `loss[2]` is then the mean align term before beta and `loss[3]` = 1, as inrfit_joint_loss gives them."""
+noneclass); `loss[2]` is then the mean align term before beta and `loss[3]` = 1, as inrfit_joint_loss gives them.
+
+`joint_prior_step` (inrfit_joint_prior_step) is the prior's share alone, for the convexity benchmark's losses: the caller evaluates
+the segmentation share in torch (any criterion, second-order autograd included) and hands its device scalar over; the call adds
+the prior's masked data term and the hard / soft align term, steps the row and returns d(prior's share) / d seg."""
 from __future__ import annotations
 
 import ctypes as C
@@ -120,4 +124,37 @@ def cdn_joint_step(ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: T
                                    C.byref(od), float(weight_decay_on_weight_g), int(step), loss.data_ptr(), dseg.data_ptr(),
                                    logits.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
     L.check(rc, "inrfit_cdn_joint_step")
+    return JointStepResult(loss, dseg, logits, status)
+
+
+def joint_prior_desc(kind: str = "bce", weight_mode: str = "none", ratio: float = 1.0, noneclass=None, data_count: int = 0,
+                     c_data: float = 1.0, align_rule: int = L.ALIGN_NONE, beta: float = 0.0, align_begin: int = 0) -> L.InrJointPriorDesc:
+    return L.InrJointPriorDesc(L.LOSS_KINDS[kind], L.WEIGHT_MODES[weight_mode], float(ratio), int(noneclass is not None),
+                               float(noneclass if noneclass is not None else 0.0), int(data_count), float(c_data), int(align_rule),
+                               float(beta), int(align_begin))
+
+
+def joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
+                     desc: L.InrJointPriorDesc, step: int, lr: float, seg_term: Optional[Tensor] = None, optimizer: str = "adam",
+                     betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
+    """ICNN prior, the prior's share only (include/inrfit.h: inrfit_joint_prior_step).  `target` holds desc.data_count values (all
+    points when 0); `seg_term` is None or a one-element float32 device tensor, the caller's segmentation share.  `params` [P] and
+    `opt_state` [2P + 8] are updated IN PLACE.  loss: composite, data term, mean align term before beta, gradient scale."""
+    params, seg, target = K._check_dev(params, "params"), K._check_dev(seg, "seg"), K._check_dev(target, "target")
+    dev, n = params.device, grid.n_points
+    assert params.numel() == spec.n_params and seg.numel() == n
+    assert target.numel() == (desc.data_count if desc.data_count > 0 else n)
+    assert opt_state.numel() == 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS and opt_state.is_contiguous()
+    if seg_term is not None:
+        seg_term = K._check_dev(seg_term, "seg_term")
+        assert seg_term.numel() == 1
+    md, gd, od = spec.desc(), grid.desc(), _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp)
+    lib = L.load()
+    ws = _workspace(("icnn", spec, n), lambda: lib.inrfit_joint_step_workspace_bytes(C.byref(md), C.byref(gd)), dev)
+    loss, dseg, logits, status = _outputs(n, dev)
+    rc = lib.inrfit_joint_prior_step(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), seg.data_ptr(),
+                                     target.data_ptr(), C.byref(desc), None if seg_term is None else seg_term.data_ptr(), C.byref(od),
+                                     int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                     ws.numel() * 4, K._stream_ptr(dev))
+    L.check(rc, "inrfit_joint_prior_step")
     return JointStepResult(loss, dseg, logits, status)

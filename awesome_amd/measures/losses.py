@@ -4,6 +4,7 @@ the fused fitter (awesome_amd.fitter) they are translated into the kernel's InrL
 E-step loop never leaves the device.  MIOU on GPU tensors is the HIP counting kernel."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -171,6 +172,25 @@ def joint_criterion_form(criterion):
     if isinstance(inner, torch.nn.BCELoss) and inner.weight is None:
         return "bce", mode, ratio, class_targets, noneclass
     raise TypeError(f"{type(criterion).__name__} has no kernel form (supported: SE, BCELoss, WeightedLoss / UnariesWeightedLoss of those)")
+
+
+def joint_prior_criterion_form(criterion):
+    """How the step kernel of inrfit_joint_prior_step evaluates `criterion` on the PRIOR channel: (loss kind, weight mode, ratio,
+    noneclass) - or TypeError.  A GradientPenaltyLoss there runs with its penalty off (the joint losses switch it off for the prior
+    call), so it is its inner criterion on the pixels whose target is not its `noneclass`.  A plain BCELoss / SE reads every target as
+    it is, a 2 included (no mask: torch has none either).  Class labels (WeightedLoss, fg = target == 0) have no form here."""
+    noneclass = None
+    if isinstance(criterion, GradientPenaltyLoss):
+        noneclass = None if criterion.noneclass is None else float(criterion.noneclass)
+        criterion = criterion.criterion
+    kind, mode, ratio, class_targets, inner_nc = joint_criterion_form(criterion)
+    if class_targets:
+        raise TypeError("class-label targets (WeightedLoss) have no form in the prior's step kernel")
+    if inner_nc is not None:
+        if noneclass is not None and noneclass != inner_nc:
+            raise TypeError("two different noneclass masks")
+        noneclass = inner_nc
+    return kind, mode, ratio, noneclass
 
 
 def _target_fields(class_targets: bool, noneclass):
@@ -506,6 +526,88 @@ class AwesomeLossJoint:
 
     def get_name(self) -> str:
         return self.name or type(self).__name__
+
+
+# ---- the convexity benchmark's losses, split for the fused joint step (awesome_amd.agent.JointTrainer, fused_convexity_losses) ----
+# Each of AwesomeImageLoss / AwesomeImageLossJoint / AwesomeLoss / AwesomeLossJoint is
+#     loss = g crit(seg, t, **kw) + g a pcrit_masked(prior[data range], t) + beta mean_{align range}((prior - A(seg))^2)
+# with A = [seg > 0.5] (hard) or seg (soft).  The first term stays in torch (`seg_share`, exactly the call the class makes); the rest
+# is inrfit_joint_prior_step's (`prior_desc`).
+
+CONVEXITY_LOSSES = (AwesomeImageLoss, AwesomeImageLossJoint, AwesomeLoss, AwesomeLossJoint)
+
+
+@dataclass
+class ConvexityJointForm:
+    pixel: bool            # AwesomeLoss / AwesomeLossJoint: output (..., n, 2), targets of the first n_scr pixels
+    g: float               # the factor on both data terms (gamma once a penalty is on, else 1; AwesomeLoss: 0.1)
+    alpha: float
+    prior_form: Tuple[str, str, float, Optional[float]]   # joint_prior_criterion_form of the prior's criterion
+    align_rule: int        # _lib.ALIGN_NONE / HARD / SOFT
+    beta: float
+    data_count: int        # points with a data term (0 = all)
+    align_begin: int
+
+    def prior_desc(self):
+        from .. import joint as J
+        kind, mode, ratio, nc = self.prior_form
+        return J.joint_prior_desc(kind, mode, ratio, nc, self.data_count, self.g * self.alpha, self.align_rule, self.beta,
+                                  self.align_begin)
+
+
+def _penalty_is_off(criterion) -> bool:
+    """A criterion the class calls WITHOUT switching a GradientPenaltyLoss's penalty off must have it off already."""
+    return not (isinstance(criterion, GradientPenaltyLoss) and criterion.apply_gradient_penalty)
+
+
+def convexity_joint_form(loss, n_points: int) -> Optional[ConvexityJointForm]:
+    """The split of one of CONVEXITY_LOSSES at its current switches (extra_penalty, map_initially_on_segmentation) for an output of
+    `n_points` pixels, or None when the prior's share has no kernel form (the step then takes the autograd path)."""
+    from .. import _lib as L
+    try:
+        if isinstance(loss, AwesomeImageLoss):
+            if not _penalty_is_off(loss.prior_criterion):
+                return None
+            pen = bool(loss.extra_penalty)
+            return ConvexityJointForm(False, loss.gamma if pen else 1.0, loss.alpha, joint_prior_criterion_form(loss.prior_criterion),
+                                      L.ALIGN_HARD if pen else L.ALIGN_NONE, loss.beta if pen else 0.0, 0, 0)
+        if isinstance(loss, AwesomeImageLossJoint):
+            rule = L.ALIGN_SOFT if loss.extra_penalty else (L.ALIGN_HARD if loss.map_initially_on_segmentation else L.ALIGN_NONE)
+            on = rule != L.ALIGN_NONE
+            return ConvexityJointForm(False, loss.gamma if on else 1.0, loss.alpha, joint_prior_criterion_form(loss.criterion), rule,
+                                      loss.beta if on else 0.0, 0, 0)
+        if isinstance(loss, (AwesomeLoss, AwesomeLossJoint)):
+            n_scr = int(n_points * loss.scribble_percentage // 1)
+            n_rand = n_points - n_scr
+            if n_scr <= 0:
+                return None
+            joint = isinstance(loss, AwesomeLossJoint)
+            if not joint and not _penalty_is_off(loss.criterion):
+                return None
+            pen = bool(loss.extra_penalty) and n_rand > 0
+            g, beta = (loss.gamma, loss.beta) if joint else (0.1, 100.0)
+            rule = (L.ALIGN_SOFT if joint else L.ALIGN_HARD) if pen else L.ALIGN_NONE
+            return ConvexityJointForm(True, g if pen else 1.0, loss.alpha, joint_prior_criterion_form(loss.criterion), rule,
+                                      beta if pen else 0.0, n_scr, n_rand if pen else 0)
+    except TypeError:
+        return None
+    return None
+
+
+def convexity_seg_share(loss, form: ConvexityJointForm, seg_out: torch.Tensor, target: torch.Tensor, **kwargs) -> torch.Tensor:
+    """g crit(seg, t) as the class's `__call__` computes it, side effects included.  `seg_out` is the segmentation channel as the class
+    slices it from the wrapper's output: (B, 1, H, W) in image mode, (B, n, 1) in pixel mode."""
+    if isinstance(loss, AwesomeImageLoss):
+        seg_loss = loss.criterion(seg_out, target)
+    elif isinstance(loss, AwesomeImageLossJoint):
+        takes_kwargs = not isinstance(loss.criterion, torch.nn.modules.loss._Loss)
+        seg_loss = loss.criterion(seg_out, target, **(kwargs if takes_kwargs else {}))
+        loss.criterion.apply_gradient_penalty = True      # what __call__ leaves behind after its prior call
+    else:
+        seg_loss = loss.criterion(seg_out[..., :form.data_count, 0:1], target)
+        if isinstance(loss, AwesomeLossJoint):
+            loss.criterion.apply_gradient_penalty = True
+    return form.g * seg_loss if form.g != 1.0 else seg_loss
 
 
 def criterion_to_desc(criterion, conversion: str = "reject") -> Tuple[str, str, float]:

@@ -409,6 +409,41 @@ int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, fl
                           int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+
+/* The PRIOR's share of a joint step, for losses whose segmentation share stays with the caller (the convexity benchmark's
+ * AwesomeImageLoss / AwesomeImageLossJoint / AwesomeLoss / AwesomeLossJoint, whose segmentation criterion may need second-order
+ * autograd through the segmentation network).  Every one of them splits into
+ *     loss = seg_term                                       (the caller's, e.g. gamma crit(seg, t), evaluated in torch)
+ *          + c_data  pcrit_masked(prior[p < data_count], t)  (the prior's data term: 'mean' over the valid points)
+ *          + beta    mean_{p >= align_begin}((prior - A(seg))^2),   A = [seg > 0.5] (INR_ALIGN_HARD) or seg (INR_ALIGN_SOFT)
+ * and this call evaluates the last two in the step kernel: prior forward, loss, backward, Adam / Adamax + enforce_convexity on the
+ * row in place, as inrfit_joint_step.  `target` holds data_count values: target[p] is the target of point p.  Points whose target
+ * equals `noneclass` (use_noneclass) contribute nothing and are not counted; the class weight (weight_mode) is taken over the rest.
+ * ICNN priors with a fused kernel only (a layer-by-layer shape: INR_EUNSUPPORTED). */
+enum { INR_ALIGN_NONE = 0, INR_ALIGN_HARD = 1, INR_ALIGN_SOFT = 2 };
+typedef struct InrJointPriorDesc {
+    int32_t kind;             /* the prior's data term: INR_LOSS_SE or INR_LOSS_BCE */
+    int32_t weight_mode;      /* INR_WEIGHT_NONE .. INR_WEIGHT_SSSDMS on unaries (fg = target < 0.5) */
+    float ratio;              /* INR_WEIGHT_RATIO */
+    int32_t use_noneclass;
+    float noneclass;
+    int64_t data_count;       /* points with a data term: [0, data_count); 0 = all points */
+    float c_data;             /* the data term's factor (gamma alpha) */
+    int32_t align_rule;       /* INR_ALIGN_* */
+    float beta;               /* the align term's factor; the mean runs over n_points - align_begin points */
+    int64_t align_begin;
+} InrJointPriorDesc;
+/* Arguments as inrfit_joint_step (same workspace, inrfit_joint_step_workspace_bytes), plus `seg_term`: null or ONE device float,
+ * the caller's segmentation share, read on the device after the caller's own work on `stream`.  loss_out [4]: the composite loss
+ * (*seg_term + the prior's share), the data term (c_data included), the mean align term before beta, the gradient scale (1; NaN =
+ * frozen).  dseg [n_points] = d(prior's share) / d seg: 0 for INR_ALIGN_NONE / HARD, -2 beta (prior - seg) / n_align on the align
+ * range for INR_ALIGN_SOFT.  A non-finite composite loss (a NaN in *seg_term as much as in the prior's share) leaves the row and its
+ * moments untouched and sets *status; a NaN in seg counts as 0 under INR_ALIGN_HARD (torch's nan > 0.5). */
+int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                            const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
+                            int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* Measurement hook (bench.py, rocprof): launch ONLY the fused forward+loss+backward step kernel `iters` times
  * back-to-back on `stream` (no optimizer step), so its average duration can be bracketed with events. */
 int inrfit_step_only(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,

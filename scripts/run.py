@@ -299,8 +299,11 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
         params = [p for p in seg.parameters()] + bank_params(prior)
         opt_cls = cfg.optimizer_type if not isinstance(cfg.optimizer_type, str) else dynamic_import(cfg.optimizer_type)
         opt = opt_cls(params, **opt_args)       # awesome_runner.py:246-252: optimizer_type(**optimizer_args)
-        # agent_args.fused_extra_penalty (opt-in): AwesomeImageLoss steps after the extra-penalty hook stay on the fused path
-        trainer = JointTrainer(jw, bank, criterion, opt, fused_extra_penalty=bool((cfg.agent_args or {}).get("fused_extra_penalty", False)))
+        # agent_args.fused_extra_penalty (opt-in): AwesomeImageLoss steps after the extra-penalty hook stay on the fused path;
+        # agent_args.fused_convexity_losses (opt-in): the convexity benchmark's losses take inrfit_joint_prior_step in every phase
+        aa = cfg.agent_args or {}
+        trainer = JointTrainer(jw, bank, criterion, opt, fused_extra_penalty=bool(aa.get("fused_extra_penalty", False)),
+                               fused_convexity_losses=bool(aa.get("fused_convexity_losses", False)))
         for epoch in range(joint_epochs):
             # the runner's extra-penalty hook (awesome/run/awesome_runner.py:351-371; config fields awesome_config.py:164-173): from
             # epoch N on the loss adds its penalty term, optionally with the learning rate scaled once
