@@ -76,6 +76,13 @@ class InrJointPriorDesc(C.Structure):   # inrfit_joint_prior_step: the prior's s
 ALIGN_NONE, ALIGN_HARD, ALIGN_SOFT = 0, 1, 2
 
 
+class InrCnnSegDesc(C.Structure):   # inrfit_cnnseg_*: the convexity benchmark's CNNNet segmentation step
+    _fields_ = [("in_channels", C.c_int32), ("image_channels", C.c_int32), ("width", C.c_int32), ("depth", C.c_int32),
+                ("kernel_size", C.c_int32), ("height", C.c_int32), ("width_px", C.c_int32), ("inversion", C.c_int32),
+                ("use_noneclass", C.c_int32), ("noneclass", C.c_float), ("g", C.c_float), ("penalty", C.c_int32),
+                ("coef", C.c_float * 3), ("channel_group", C.c_int32 * 8)]
+
+
 class InrStarDesc(C.Structure):
     _fields_ = [("n_hidden", C.c_int32)]
 
@@ -179,6 +186,13 @@ EXPORTS = {
                               C.c_void_p]),
     "inrfit_timing_begin": (C.c_int, [C.c_int]),
     "inrfit_timing_end": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "inrfit_cnnseg_param_count": (C.c_int64, [C.POINTER(InrCnnSegDesc)]),
+    "inrfit_cnnseg_workspace_bytes": (C.c_int64, [C.POINTER(InrCnnSegDesc)]),
+    "inrfit_cnnseg_forward": (C.c_int, [C.POINTER(InrCnnSegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_cnnseg_step": (C.c_int, [C.POINTER(InrCnnSegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
     "inrfit_strerror": (C.c_char_p, [C.c_int]),
 }
 

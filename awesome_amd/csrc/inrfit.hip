@@ -29,6 +29,7 @@
 #include "joint_loss.h"
 #include "wide.h"
 #include "star.h"
+#include "cnnseg.h"
 
 #include <vector>
 
@@ -654,6 +655,246 @@ __global__ __launch_bounds__(256) void mfma_stream_kernel(float* __restrict__ si
     if (s == 12345.678f) sink[blockIdx.x * 256 + threadIdx.x] = s;   // never true: keeps the products alive
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// CNNNet segmentation step (csrc/cnnseg.h)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct CnnWs {
+    int n, L, Wd, cin, P, nb, tiles, tiles_x, rblocks;
+    float *act, *f, *s, *u, *e, *g, *t, *tout, *df, *dl, *stats_part, *stats, *slab;
+    int32_t* flags;
+    long long bytes;
+    float* map(float* base, int l) const { return base + (size_t)l * Wd * n; }
+};
+
+static bool cnn_desc_ok(const InrCnnSegDesc* d) {
+    return d && d->kernel_size == 3 && d->width == CNN_WIDTH && d->depth >= 0 && d->depth <= CNN_MAX_LAYERS - 2 &&
+           d->in_channels >= 1 && d->in_channels <= CNN_MAX_IN && d->image_channels >= 0 && d->image_channels <= d->in_channels &&
+           d->height >= 1 && d->width_px >= 1 && (long long)d->height * d->width_px < (1LL << 30);
+}
+
+static long long cnn_param_count(const InrCnnSegDesc* d) {
+    const long long W = d->width;
+    return (W * d->in_channels * 9 + W) + (long long)d->depth * (W * W * 9 + W) + (W * 9 + 1);
+}
+
+static CnnWs cnn_layout(const InrCnnSegDesc* d, void* base) {
+    CnnWs w{};
+    w.n = d->height * d->width_px;
+    w.L = d->depth + 2;
+    w.Wd = d->width;
+    w.cin = d->in_channels;
+    w.P = (int)cnn_param_count(d);
+    w.nb = (w.n + CNN_BLOCK - 1) / CNN_BLOCK;
+    w.tiles_x = (d->width_px + CNN_TILE - 1) / CNN_TILE;
+    w.tiles = w.tiles_x * ((d->height + CNN_TILE - 1) / CNN_TILE);
+    w.rblocks = (w.P + CNN_BLOCK - 1) / CNN_BLOCK;
+    char* p = (char*)base;
+    long long off = 0;
+    auto take = [&](long long floats) {
+        float* r = (float*)(p + off);
+        off += (floats * 4 + 255) / 256 * 256;
+        return r;
+    };
+    const long long maps = (long long)(w.L - 1) * w.Wd * w.n;
+    w.act = take(maps);
+    w.f = take(w.n);
+    w.s = take(w.n);
+    w.u = take(w.n);
+    w.e = take(maps);
+    w.g = take((long long)w.cin * w.n);
+    w.t = take(maps);
+    w.tout = take(w.n);
+    w.df = take(w.n);
+    w.dl = take(maps);
+    w.stats_part = take((long long)w.nb * CNN_STATS);
+    w.stats = take(CNN_STATS);
+    w.slab = take((long long)w.tiles * w.P);
+    w.flags = (int32_t*)take(w.rblocks);
+    w.bytes = off;
+    return w;
+}
+
+static void cnn_conv(const CnnWs& w, const InrCnnSegDesc* d, bool transposed, const float* x0, const float* x1, int c0, int ci, int co,
+                     const float* wt, const float* b, int act, const float* mask, float slope, float* out, hipStream_t s) {
+    CnnConvArgs a{x0, x1, c0, ci, co, wt, b, act, mask, slope, out, d->height, d->width_px};
+    const dim3 grid(w.nb), block(CNN_BLOCK);
+    if (transposed) {
+        if (co == 1) hipLaunchKernelGGL((cnn_conv_kernel<1, true>), grid, block, 0, s, a);
+        else if (co <= CNN_MAX_IN) hipLaunchKernelGGL((cnn_conv_kernel<CNN_MAX_IN, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((cnn_conv_kernel<CNN_WIDTH, true>), grid, block, 0, s, a);
+    } else {
+        if (co == 1) hipLaunchKernelGGL((cnn_conv_kernel<1, false>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((cnn_conv_kernel<CNN_WIDTH, false>), grid, block, 0, s, a);
+    }
+}
+
+// layer l: input channels / output channels
+static inline int cnn_ci(const CnnWs& w, int l) { return l == 0 ? w.cin : w.Wd; }
+static inline int cnn_co(const CnnWs& w, int l) { return l == w.L - 1 ? 1 : w.Wd; }
+static inline float cnn_slope(int l) { return l == 0 ? 0.01f : 0.f; }   // the mask of activation l: LeakyReLU, then ReLU
+
+static CnnPointArgs cnn_point_args(const CnnWs& w, const InrCnnSegDesc* d, const float* target) {
+    CnnPointArgs a{};
+    a.f = w.f;
+    a.target = target;
+    a.seg = w.s;
+    a.u = w.u;
+    a.g = w.g;
+    a.stats_part = w.stats_part;
+    a.n = w.n;
+    a.inversion = d->inversion;
+    a.use_noneclass = d->use_noneclass;
+    a.noneclass = d->noneclass;
+    a.cin = w.cin;
+    a.penalty = d->penalty;
+    int cnt[3] = {0, 0, 0};
+    for (int c = 0; c < w.cin; ++c)
+        if (d->channel_group[c] >= 0 && d->channel_group[c] < 3) cnt[d->channel_group[c]]++;
+    for (int c = 0; c < CNN_MAX_IN; ++c) {
+        const int grp = c < w.cin ? d->channel_group[c] : -1;
+        const bool on = grp >= 0 && grp < 3 && d->coef[grp] != 0.f;
+        a.group[c] = on ? grp : -1;
+        a.qscale[c] = on ? (float)((double)d->g * d->coef[grp] / ((double)cnt[grp] * w.n)) : 0.f;
+    }
+    return a;
+}
+
+// pass 1 (+ pass 2 and the loss value with a target)
+static int cnn_forward_passes(const CnnWs& w, const InrCnnSegDesc* d, const float* const* wts, const float* const* bs, const float* image,
+                              const float* feat, const float* target, float* logits, float* seg, float* loss_out, hipStream_t s) {
+    const int ic = d->image_channels;
+    for (int l = 0; l < w.L; ++l) {
+        const bool first = l == 0, last = l == w.L - 1;
+        const float* x0 = first ? image : w.map(w.act, l - 1);
+        const float* x1 = first ? feat : x0;
+        cnn_conv(w, d, false, x0, x1, first ? ic : cnn_ci(w, l), cnn_ci(w, l), cnn_co(w, l), wts[l], bs[l], last ? 0 : (first ? 1 : 2),
+                 nullptr, 0.f, last ? w.f : w.map(w.act, l), s);
+    }
+    CnnPointArgs pa = cnn_point_args(w, d, target);
+    pa.f_out = logits;
+    pa.seg_out = seg;
+    hipLaunchKernelGGL(cnn_head_kernel, dim3(w.nb), dim3(CNN_BLOCK), 0, s, pa);
+    if (!target) return INR_OK;
+    if (d->penalty) {   // pass 2: e_{L-1} = u, e_{l-1} = m_{l-1} conv_l^T(e_l), g = conv_0^T(e_0)
+        for (int l = w.L - 1; l >= 0; --l) {
+            const float* src = l == w.L - 1 ? w.u : w.map(w.e, l);
+            if (l > 0)
+                cnn_conv(w, d, true, src, src, cnn_co(w, l), cnn_co(w, l), cnn_ci(w, l), wts[l], nullptr, 0, w.map(w.act, l - 1),
+                         cnn_slope(l - 1), w.map(w.e, l - 1), s);
+            else
+                cnn_conv(w, d, true, src, src, cnn_co(w, 0), cnn_co(w, 0), w.cin, wts[0], nullptr, 0, nullptr, 0.f, w.g, s);
+        }
+    }
+    hipLaunchKernelGGL(cnn_stats_kernel, dim3(w.nb), dim3(CNN_BLOCK), 0, s, pa);
+    CnnLossArgs la{};
+    la.stats_part = w.stats_part;
+    la.blocks = w.nb;
+    la.stats = w.stats;
+    la.loss_out = w.stats + 6;
+    la.loss_user = loss_out;
+    la.gfac = d->g;
+    int cnt[3] = {0, 0, 0};
+    for (int c = 0; c < w.cin; ++c)
+        if (d->channel_group[c] >= 0 && d->channel_group[c] < 3) cnt[d->channel_group[c]]++;
+    for (int grp = 0; grp < 3; ++grp)
+        la.pen_scale[grp] = (d->penalty && d->coef[grp] != 0.f && cnt[grp] > 0) ? (float)((double)d->coef[grp] / ((double)cnt[grp] * w.n)) : 0.f;
+    hipLaunchKernelGGL(cnn_loss_kernel, dim3(1), dim3(CNN_BLOCK), 0, s, la);
+    return INR_OK;
+}
+
+static int cnn_check(const InrCnnSegDesc* d, const float* const* wts, const float* const* bs, const float* image, const float* feat,
+                     void* ws, long long ws_bytes, CnnWs* w) {
+    if (!d || !wts || !bs || !image || !ws) return INR_EINVAL;
+    if (!cnn_desc_ok(d)) return INR_EUNSUPPORTED;
+    if (d->image_channels < d->in_channels && !feat) return INR_EINVAL;
+    for (int l = 0; l < d->depth + 2; ++l)
+        if (!wts[l] || !bs[l]) return INR_EINVAL;
+    *w = cnn_layout(d, ws);
+    if (ws_bytes < w->bytes) return INR_EWORKSPACE;
+    return INR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t inrfit_cnnseg_param_count(const InrCnnSegDesc* desc) { return cnn_desc_ok(desc) ? cnn_param_count(desc) : -1; }
+
+int64_t inrfit_cnnseg_workspace_bytes(const InrCnnSegDesc* desc) {
+    return cnn_desc_ok(desc) ? cnn_layout(desc, nullptr).bytes : -1;
+}
+
+int inrfit_cnnseg_forward(const InrCnnSegDesc* desc, const float* const* weights, const float* const* biases, const float* image,
+                          const float* features, const float* target, float* logits, float* seg, float* loss_out, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+    CnnWs w;
+    int rc = cnn_check(desc, weights, biases, image, features, workspace, workspace_bytes, &w);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = cnn_forward_passes(w, desc, weights, biases, image, features, target, logits, seg, loss_out, s))) return rc;
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+int inrfit_cnnseg_step(const InrCnnSegDesc* desc, const float* const* weights, const float* const* biases, const float* image,
+                       const float* features, const float* target, const float* dseg, int reuse_forward, float* logits, float* seg,
+                       float* loss_out, float* grads, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    CnnWs w;
+    int rc = cnn_check(desc, weights, biases, image, features, workspace, workspace_bytes, &w);
+    if (rc) return rc;
+    if (!target || !grads || !status) return INR_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (!reuse_forward && (rc = cnn_forward_passes(w, desc, weights, biases, image, features, target, logits, seg, nullptr, s))) return rc;
+    const bool pen = desc->penalty != 0;
+    if (pen) {   // pass 3: t_l = m_l conv_l(t_{l-1}) from t_{-1} = q (in w.g), no biases
+        for (int l = 0; l < w.L; ++l) {
+            const bool last = l == w.L - 1;
+            const float* x0 = l == 0 ? w.g : w.map(w.t, l - 1);
+            cnn_conv(w, desc, false, x0, x0, cnn_ci(w, l), cnn_ci(w, l), cnn_co(w, l), weights[l], nullptr, 0,
+                     last ? nullptr : w.map(w.act, l), cnn_slope(l), last ? w.tout : w.map(w.t, l), s);
+        }
+    }
+    CnnSeedArgs sa{w.s, w.f, target, w.stats, pen ? w.tout : nullptr, dseg, w.df, w.n, desc->inversion, desc->use_noneclass,
+                   desc->noneclass};
+    hipLaunchKernelGGL(cnn_seed_kernel, dim3(w.nb), dim3(CNN_BLOCK), 0, s, sa);
+    // pass 4: d_{l-1} = m_{l-1} conv_l^T(d_l)
+    for (int l = w.L - 1; l > 0; --l) {
+        const float* src = l == w.L - 1 ? w.df : w.map(w.dl, l);
+        cnn_conv(w, desc, true, src, src, cnn_co(w, l), cnn_co(w, l), cnn_ci(w, l), weights[l], nullptr, 0, w.map(w.act, l - 1),
+                 cnn_slope(l - 1), w.map(w.dl, l - 1), s);
+    }
+    int off = 0;
+    for (int l = 0; l < w.L; ++l) {
+        const int ci = cnn_ci(w, l), co = cnn_co(w, l);
+        CnnWgradArgs a{};
+        a.x0 = l == 0 ? image : w.map(w.act, l - 1);
+        a.x1 = l == 0 ? features : a.x0;
+        a.c0 = l == 0 ? desc->image_channels : ci;
+        a.d = l == w.L - 1 ? w.df : w.map(w.dl, l);
+        a.t = pen ? (l == 0 ? w.g : w.map(w.t, l - 1)) : nullptr;
+        a.e = l == w.L - 1 ? w.u : w.map(w.e, l);
+        a.ci = ci;
+        a.co = co;
+        a.H = desc->height;
+        a.W = desc->width_px;
+        a.tiles_x = w.tiles_x;
+        a.slab = w.slab;
+        a.P = w.P;
+        a.w_off = off;
+        a.b_off = off + co * ci * 9;
+        off = a.b_off + co;
+        hipLaunchKernelGGL(cnn_wgrad_kernel<CNN_WIDTH>, dim3(w.tiles), dim3(CNN_BLOCK), 0, s, a);
+    }
+    if (off != w.P) return INR_EINVAL;
+    hipLaunchKernelGGL(cnn_grad_reduce_kernel, dim3(w.rblocks), dim3(CNN_BLOCK), 0, s, (const float*)w.slab, w.tiles, w.P, grads, w.flags);
+    hipLaunchKernelGGL(cnn_finalize_kernel, dim3(1), dim3(CNN_BLOCK), 0, s, (const int32_t*)w.flags, w.rblocks,
+                       (const float*)(w.stats + 6), grads, w.P, status, loss_out);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+}  // extern "C"
 
 extern "C" {
 

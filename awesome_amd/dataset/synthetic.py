@@ -86,15 +86,19 @@ class SyntheticPriorDataset(PriorDataset):
     WrapperModule(ForwardModule(), prior, use_segmentation_output_inversion=...) reproduces them like a trained backbone would);
     `features` is an empty placeholder, `xy_clean` the (2, S, S) linspace grid of Transformator.get_positional_matrices, `target`
     (1, S, S) the clean mask in the unaries' convention (object = 0, background = 1: what the inverted segmentation output is
-    trained against).  `kind`: 'blob' | 'noisy_blob' | 'disc' (see SyntheticUnariesDataset)."""
+    trained against).  `kind`: 'blob' | 'noisy_blob' | 'disc' (see SyntheticUnariesDataset).  `features='xy'`: the features are
+    the (2, S, S) grid as well (the spatial features a CNNNet with 'rgbxy' input reads)."""
 
     returns_index = False
     training_batch_size = 1
 
     def __init__(self, n_images: int = 1, size: int = 256, kind: str = "blob", seed0: int = 0, prior_model_type=None,
-                 prior_model_args=None, **kwargs):
+                 prior_model_args=None, features: str = "none", **kwargs):
         super().__init__(prior_model_type=prior_model_type, prior_model_args=prior_model_args)
+        if features not in ("none", "xy"):
+            raise ValueError(f"features must be 'none' or 'xy' but is {features!r}")
         self.kind = kind
+        self.features = features
         if kind == "sequence":
             masks = dumbbell_sequence_masks(int(size), int(n_images), int(seed0))
             frames = [torch.from_numpy(1.0 - m.astype(np.float32)) for m in masks]
@@ -144,7 +148,8 @@ class SyntheticPriorDataset(PriorDataset):
         if self.kind == "sequence":
             t = float(i) / float(max(len(self) - 1, 1))
             xy = torch.cat([xy, torch.full((1, self.size, self.size), t)], 0)
-        return (image, torch.zeros(1, 1, 1), xy), target
+        feat = xy.clone() if self.features == "xy" else torch.zeros(1, 1, 1)
+        return (image, feat, xy), target
 
 
 class SyntheticUnariesDataset:

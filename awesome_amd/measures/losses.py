@@ -197,6 +197,12 @@ def _target_fields(class_targets: bool, noneclass):
     return int(bool(class_targets)), int(noneclass is not None), float(noneclass if noneclass is not None else 0.0)
 
 
+def _criterion_kwargs(criterion, forward: bool, kwargs) -> dict:
+    """The kwargs a composite loss hands its criterion: all of them when it forwards them and the criterion is not a torch _Loss
+    (whose forward takes none), else none."""
+    return kwargs if forward and not isinstance(criterion, torch.nn.modules.loss._Loss) else {}
+
+
 class AwesomeImageLoss:
     """awesome/measures/awesome_image_loss.py:34-53: crit(seg,t) + alpha*crit(prior,t) [+ penalty].
 
@@ -204,11 +210,15 @@ class AwesomeImageLoss:
     fused HIP loss `inrfit_joint_loss` (form INR_JOINT_AWESOME_IMAGE: value and both gradient channels in three launches); any other
     criterion is composed from torch ops."""
 
-    def __init__(self, criterion=None, prior_criterion=None, alpha=1.0, beta=100.0, gamma=0.1, name=None, **kwargs):
+    def __init__(self, criterion=None, prior_criterion=None, alpha=1.0, beta=100.0, gamma=0.1, name=None,
+                 forward_kwargs_criterion: bool = True, forward_kwargs_prior_criterion: bool = False, **kwargs):
         self.criterion = criterion or torch.nn.BCELoss()
         self.prior_criterion = prior_criterion or torch.nn.BCELoss()
         self.alpha, self.beta, self.gamma, self.name = alpha, beta, gamma, name
         self.extra_penalty = False  # toggled by the runner (awesome/run/awesome_runner.py:351-371)
+        # the step's kwargs (e.g. GradientPenaltyLoss's _input) go to a criterion that is not a torch _Loss (awesome_image_loss.py:36-45)
+        self.forward_kwargs_criterion = forward_kwargs_criterion
+        self.forward_kwargs_prior_criterion = forward_kwargs_prior_criterion
 
     def joint_desc(self):
         """InrJointLossDesc of this loss, or None if a criterion has no kernel form."""
@@ -231,7 +241,9 @@ class AwesomeImageLoss:
                 return _FusedJointLoss.apply(output, target, desc)
         c = output.shape[1] // 2
         seg, prior = output[:, :c], output[:, c:]
-        loss = self.criterion(seg, target) + self.alpha * self.prior_criterion(prior, target)
+        loss = self.criterion(seg, target, **_criterion_kwargs(self.criterion, self.forward_kwargs_criterion, kwargs))
+        loss = loss + self.alpha * self.prior_criterion(prior, target, **_criterion_kwargs(self.prior_criterion,
+                                                                                           self.forward_kwargs_prior_criterion, kwargs))
         if self.extra_penalty:
             loss = self.gamma * loss + self.beta * torch.mean((prior - (seg > 0.5).float()) ** 2)
         return loss
@@ -598,7 +610,7 @@ def convexity_seg_share(loss, form: ConvexityJointForm, seg_out: torch.Tensor, t
     """g crit(seg, t) as the class's `__call__` computes it, side effects included.  `seg_out` is the segmentation channel as the class
     slices it from the wrapper's output: (B, 1, H, W) in image mode, (B, n, 1) in pixel mode."""
     if isinstance(loss, AwesomeImageLoss):
-        seg_loss = loss.criterion(seg_out, target)
+        seg_loss = loss.criterion(seg_out, target, **_criterion_kwargs(loss.criterion, loss.forward_kwargs_criterion, kwargs))
     elif isinstance(loss, AwesomeImageLossJoint):
         takes_kwargs = not isinstance(loss.criterion, torch.nn.modules.loss._Loss)
         seg_loss = loss.criterion(seg_out, target, **(kwargs if takes_kwargs else {}))

@@ -44,6 +44,7 @@ ALIASES: Dict[str, str] = {
     "awesome.model.path_connected_net.PathConnectedNet": "awesome_amd.model.PathConnectedNet",
     "awesome.model.noisy_path_connected_net.NoisyPathConnectedNet": "awesome_amd.model.NoisyPathConnectedNet",
     "awesome.model.fc_net.FCNet": "awesome_amd.model.FCNet",
+    "awesome.model.cnn_net.CNNNet": "awesome_amd.model.CNNNet",
     "awesome.model.forward_module.ForwardModule": "awesome_amd.model.ForwardModule",
     "awesome.model.wrapper_module.WrapperModule": "awesome_amd.model.WrapperModule",
     "awesome.model.zoo.Zoo": "awesome_amd.model.Zoo",

@@ -503,6 +503,47 @@ int inrfit_star_fit(const InrStarDesc* star, float* params, float* opt_state, co
                     int64_t n_pixels, const int32_t* batch_index, int64_t batch, const InrOptDesc* opt, int32_t steps, int32_t step0,
                     int32_t offset_first_step, float* loss_hist, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the convexity benchmark's segmentation network (awesome/model/cnn_net.py CNNNet, csrc/cnnseg.h) --------------------------------
+ * Conv3x3 in_channels -> width, LeakyReLU(0.01), depth x [Conv3x3 width -> width, ReLU], Conv3x3 width -> 1, all with padding 1, batch 1,
+ * fp32; the input is the channel concatenation of `image` [image_channels][H][W] and `features` [in_channels - image_channels][H][W].
+ * s = sigmoid(f), or 1 - sigmoid(f) with `inversion`.  The share of the joint loss it is trained with (GradientPenaltyLoss(BCELoss) or
+ * BCELoss, times g):
+ *     loss = g ( mean_{t != noneclass} BCE(s, t) + sum_grp coef[grp] mean_{channels of grp, pixels} |d sum(s) / d input| )
+ * channel_group[c] names the group of input channel c (0 rgb, 1 xy, 2 feat, -1 none); coef[grp] = 0: no term; penalty = 0: no
+ * penalty at all.  Supported: kernel_size 3, width 16, depth <= 3, 1 <= in_channels <= 8, any H x W (INR_EUNSUPPORTED otherwise).
+ * weights / biases: host arrays of depth + 2 device pointers, the layers' torch tensors ([co][ci][3][3] and [co]). */
+typedef struct InrCnnSegDesc {
+    int32_t in_channels;
+    int32_t image_channels;
+    int32_t width;
+    int32_t depth;
+    int32_t kernel_size;
+    int32_t height;
+    int32_t width_px;
+    int32_t inversion;
+    int32_t use_noneclass;
+    float noneclass;
+    float g;
+    int32_t penalty;
+    float coef[3];
+    int32_t channel_group[8];
+} InrCnnSegDesc;
+
+/* gradient layout: the module's parameters() order, w_0 | b_0 | w_1 | b_1 | ... */
+int64_t inrfit_cnnseg_param_count(const InrCnnSegDesc* desc);
+int64_t inrfit_cnnseg_workspace_bytes(const InrCnnSegDesc* desc);
+/* Forward: logits [H W] = f, seg [H W] = s.  With `target` [H W] (else null) also the loss above into loss_out[0] (one device float,
+ * the seg_term inrfit_joint_prior_step can take) and everything inrfit_cnnseg_step needs from the forward, kept in `workspace`. */
+int inrfit_cnnseg_forward(const InrCnnSegDesc* desc, const float* const* weights, const float* const* biases, const float* image,
+                          const float* features, const float* target, float* logits, float* seg, float* loss_out, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+/* One step: the forward above (skipped with reuse_forward = 1 when inrfit_cnnseg_forward ran with the same arguments on the same
+ * workspace), then grads [param_count] = d (loss + sum_p dseg[p] s[p]) / d parameters; dseg [H W] or null.  A non-finite loss or gradient
+ * zeroes grads and sets *status = 1 (else 0).  Reductions are fixed-order: results are bit-reproducible.  No host sync. */
+int inrfit_cnnseg_step(const InrCnnSegDesc* desc, const float* const* weights, const float* const* biases, const float* image,
+                       const float* features, const float* target, const float* dseg, int reuse_forward, float* logits, float* seg,
+                       float* loss_out, float* grads, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 const char* inrfit_strerror(int code);
 
 #pragma GCC visibility pop

@@ -288,7 +288,11 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
             raise SystemExit(f"segmentation_model_type {seg_name} is outside this build (SURVEY.md section 8: backbones run on torch as "
                              "they are); pass --segmentation-model-type with an importable torch module type")
         seg_type = dynamic_import(seg_name) if isinstance(seg_name, str) else seg_name
-        seg = seg_type(**dict(cfg.get("segmentation_model_args") or {})).to(device)
+        seg_args = dict(cfg.get("segmentation_model_args") or {})
+        from awesome_amd.model import CNNNet
+        if isinstance(seg_type, type) and issubclass(seg_type, CNNNet):
+            seg_args = segmentation_model_args(cfg, seg_args, ds[mine[0]])
+        seg = seg_type(**seg_args).to(device)
         prior = wrapper.prior_module
         jw = WrapperModule(seg, prior, use_segmentation_output_inversion=True).to(device)
         bank = PriorBank(lambda: model_type(**model_args).to(device), n_images=len(mine), device=device, keys=mine)
@@ -302,8 +306,10 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
         # agent_args.fused_extra_penalty (opt-in): AwesomeImageLoss steps after the extra-penalty hook stay on the fused path;
         # agent_args.fused_convexity_losses (opt-in): the convexity benchmark's losses take inrfit_joint_prior_step in every phase
         aa = cfg.agent_args or {}
+        # agent_args.fused_segmentation (opt-in, with fused_convexity_losses): a supported CNNNet takes its step in HIP too
         trainer = JointTrainer(jw, bank, criterion, opt, fused_extra_penalty=bool(aa.get("fused_extra_penalty", False)),
-                               fused_convexity_losses=bool(aa.get("fused_convexity_losses", False)))
+                               fused_convexity_losses=bool(aa.get("fused_convexity_losses", False)),
+                               fused_segmentation=bool(aa.get("fused_segmentation", False)))
         for epoch in range(joint_epochs):
             # the runner's extra-penalty hook (awesome/run/awesome_runner.py:351-371; config fields awesome_config.py:164-173): from
             # epoch N on the loss adds its penalty term, optionally with the learning rate scaled once
@@ -326,6 +332,26 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
             with bank.manager(prior, k):
                 cache0[k] = {n: v.detach().cpu().clone() for n, v in prior.state_dict().items()}
     return report, joint_losses, fused_steps
+
+
+def segmentation_model_args(cfg, args, item):
+    """AwesomeRunner.get_sisbosi_segmentation_model_args (awesome/run/awesome_runner.py:43-73) on this build's item format
+    ((image, features, xy_clean), target): `input` becomes `in_type`; in_chn = image channels (3 for RGB) + the channel count of the
+    item's second input for 'rgbxy', one of the two for 'rgb' / 'xy'; out_chn = 1 for binary classification."""
+    args = dict(args)
+    mode = args.pop("input", "rgbxy")
+    (_, _), ((image, feat, _), _) = item
+    c_img, c_feat = int(image.shape[-3]) if image.dim() >= 3 else 1, int(feat.shape[-3]) if feat.dim() >= 3 else 1
+    if "in_chn" not in args:
+        chn = {"rgb": c_img, "rgbxy": c_img + c_feat, "xy": c_feat}
+        if mode not in chn:
+            raise ValueError(f"Invalid input mode: {mode}")
+        args["in_chn"] = chn[mode]
+    if "out_chn" not in args:
+        args["out_chn"] = 1 if cfg.get("use_binary_classification", True) else 2   # the synthetic items are binary
+    args["in_type"] = mode
+    args.pop("dtype", None)
+    return args
 
 
 def bank_params(prior):
