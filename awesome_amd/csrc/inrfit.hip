@@ -31,6 +31,7 @@
 #include "star.h"
 #include "cnnseg.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -554,17 +555,17 @@ int wgs_per_image(long long n_points, int n_images) {
     return (int)w;
 }
 
+// what every path asks of a grid: a known mode with its pointers, width x height = n_points in (0, max_points], images; the callers
+// add their own rules (check_grid, check_pcn)
+bool grid_ok(const InrGridDesc* g, int n_images, long long max_points = 0x7fffffffLL) {
+    if (!g || g->n_points <= 0 || g->n_points > max_points || n_images <= 0) return false;
+    if (g->mode == INR_GRID_SEPARABLE) return g->xs && g->ys && (long long)g->width * g->height == g->n_points;
+    return g->mode == INR_GRID_EXPLICIT && g->coords;
+}
+
 int check_grid(const InrGridDesc* g, const KernelEntry* e, int n_images) {
-    if (!g || g->n_points <= 0 || g->n_points > 0x7fffffffLL || n_images <= 0) return INR_EINVAL;
-    if (g->mode == INR_GRID_SEPARABLE) {
-        if (!g->xs || !g->ys || g->width <= 0 || g->height <= 0) return INR_EINVAL;
-        if ((long long)g->width * g->height != g->n_points) return INR_EINVAL;
-        if (e->c > 3) return INR_EINVAL;
-    } else if (g->mode == INR_GRID_EXPLICIT) {
-        if (!g->coords) return INR_EINVAL;
-    } else {
-        return INR_EINVAL;
-    }
+    if (!grid_ok(g, n_images)) return INR_EINVAL;
+    if (g->mode == INR_GRID_SEPARABLE && (g->width <= 0 || g->height <= 0 || e->c > 3)) return INR_EINVAL;
     return INR_OK;
 }
 
@@ -1067,6 +1068,39 @@ static UpdArgs make_upd_args(const KernelEntry* e, const Workspace& w, float* pa
     return u;
 }
 
+// Adam's bias corrections of step t: 1 - beta1^t and sqrt(1 - beta2^t), computed on the host in double like torch does
+static void bias_corrections(const InrOptDesc* opt, int t, double* bc1, float* bc2_sqrt) {
+    *bc1 = 1.0 - pow((double)opt->beta1, (double)t);
+    *bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)t));
+}
+
+// what changes from one optimizer step of a loop to the next (t is 1-based)
+static void set_step_consts(UpdArgs& u, const InrOptDesc* opt, int t, int hist_idx = 0) {
+    u.t = t;
+    bias_corrections(opt, t, &u.bc1, &u.bc2_sqrt);
+    u.hist_idx = hist_idx;
+}
+
+static void launch_icnn_update(const KernelEntry* e, const UpdArgs& u, hipStream_t s) {
+    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, u.n_images), upd_block(e->img.sl_cols), 0, s, u);
+}
+
+// the update-kernel half of bench.py's timing hook (launch_step_timed is the step kernel's)
+static int launch_icnn_update_timed(const KernelEntry* e, const UpdArgs& u, hipStream_t s) {
+    if (!g_timing.on || (int)g_timing.evu.size() >= 2 * g_timing.max_samples) {
+        launch_icnn_update(e, u, s);
+        return INR_OK;
+    }
+    hipEvent_t a, b;
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return INR_ELAUNCH;
+    (void)hipEventRecord(a, s);
+    launch_icnn_update(e, u, s);
+    (void)hipEventRecord(b, s);
+    g_timing.evu.push_back(a);
+    g_timing.evu.push_back(b);
+    return INR_OK;
+}
+
 // common argument checks + workspace carve
 static int prepare(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
                    const KernelEntry** e_out, Workspace* w_out) {
@@ -1111,12 +1145,7 @@ static bool use_wide(const InrModelDesc* m) { return find_entry(m) == nullptr &&
 
 static int wide_prepare(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
                         WideMap* m, WideWs* w, float** coef_all, hipStream_t s) {
-    if (!workspace || !grid || grid->n_points <= 0 || grid->n_points > 0x7fffffffLL / WIDE_MAX_HIDDEN * 64 || n_images <= 0) return INR_EINVAL;
-    if (grid->mode == INR_GRID_SEPARABLE) {
-        if (!grid->xs || !grid->ys || (long long)grid->width * grid->height != grid->n_points) return INR_EINVAL;
-    } else if (grid->mode != INR_GRID_EXPLICIT || !grid->coords) {
-        return INR_EINVAL;
-    }
+    if (!workspace || !grid_ok(grid, n_images, 0x7fffffffLL / WIDE_MAX_HIDDEN * 64)) return INR_EINVAL;
     if (model->act0 < INR_ACT_RELU || model->act0 > INR_ACT_SIN) return INR_EINVAL;
     *m = make_wide_map(model);
     const bool pre0 = model->act0 != INR_ACT_RELU;
@@ -1203,10 +1232,7 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
     const dim3 ugrid = upd_grid(m.P + 1, 1), ublock = upd_block(m.P + 1);
     const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
     for (int it = 0; it < steps; ++it) {
-        u.t = step0 + it + 1;
-        u.bc1 = 1.0 - pow((double)opt->beta1, (double)u.t);
-        u.bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)u.t));
-        u.hist_idx = it;
+        set_step_consts(u, opt, step0 + it + 1, it);
         for (int img = 0; img < n_images; ++img) {
             float* p = params + (size_t)img * m.P;
             w.coef = coef + 2 * img;
@@ -1225,38 +1251,6 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
         for (int img = 0; img < n_images; ++img)
             if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, final_logits + (size_t)img * ON, s))) return rc;
     return INR_OK;
-}
-
-int inrfit_forward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
-                   void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    Workspace w;
-    if (!params || !logits) return INR_EINVAL;
-    if (use_wide(model)) return wide_forward_all(model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
-    int rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
-    return launch_step(e, w, false, grid, nullptr, 0, n_images, logits, s);
-}
-
-int inrfit_loss_grad(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
-                     const InrLossDesc* loss, int n_images, float* loss_out, float* grads, void* workspace,
-                     int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    Workspace w;
-    if (!params || !targets || !loss_out || !grads) return INR_EINVAL;
-    int rc = check_loss(loss);
-    if (rc) return rc;
-    if (use_wide(model))
-        return wide_loss_grad_all(model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes, (hipStream_t)stream);
-    if ((rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef, 1.f);
-    if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
-    if ((rc = launch_step(e, w, true, grid, targets, loss->kind, n_images, nullptr, s))) return rc;
-    launch_reduce(e, w, n_images, grads, loss_out, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
 int inrfit_backward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* dlogits,
@@ -1342,58 +1336,6 @@ int inrfit_timing_end(float* avg_step_bracket_us, float* avg_update_bracket_us, 
     return INR_OK;
 }
 
-int inrfit_fit(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
-               const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist,
-               float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    Workspace w;
-    if (!params || !opt_state || !targets || !opt || steps < 0 || step0 < 0) return INR_EINVAL;
-    if (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) return INR_EINVAL;
-    int rc = check_loss(loss);
-    if (rc) return rc;
-    if (loss->kind == INR_LOSS_EXTERNAL) return INR_EINVAL;
-    if (use_wide(model))
-        return wide_fit(model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status,
-                        workspace, workspace_bytes, (hipStream_t)stream);
-    if ((rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.coef, 1.f);
-    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, w.Pu, *opt, step0);
-    if (status) {
-        if (hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    }
-    if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
-    UpdArgs u = make_upd_args(e, w, params, opt_state, loss_hist, status, opt, n_images, steps);
-    const dim3 ugrid = upd_grid(e->img.sl_cols, n_images), ublock = upd_block(e->img.sl_cols);
-    // opt->logits_at_last_forward: final_logits = the output of the LAST training forward (parameters before the last optimizer
-    // step) - what the reference's IoU gate looks at (path_connected_net.py:939-972) - written by that step's launch itself
-    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
-    for (int it = 0; it < steps; ++it) {
-        w.set_step(step0 + it);
-        u.slabs = w.slabs;
-        if ((rc = launch_step_timed(e, w, grid, targets, loss->kind, n_images, s, gate_logits && it == steps - 1 ? final_logits : nullptr)))
-            return rc;
-        u.t = step0 + it + 1;
-        u.bc1 = 1.0 - pow((double)opt->beta1, (double)u.t);
-        u.bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)u.t));
-        u.hist_idx = it;
-        if (g_timing.on && (int)g_timing.evu.size() < 2 * g_timing.max_samples) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return INR_ELAUNCH;
-            (void)hipEventRecord(a, s);
-            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
-            (void)hipEventRecord(b, s);
-            g_timing.evu.push_back(a);
-            g_timing.evu.push_back(b);
-        } else {
-            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
-    if (final_logits && !gate_logits) return launch_step(e, w, false, grid, nullptr, 0, n_images, final_logits, s);
-    return INR_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // path-connected prior: ICNN(flow(Ax + b))
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1469,8 +1411,7 @@ FlowUpdArgs make_flow_upd_args(const CdnWs& w, int mode, float* FP, float* opt, 
     u.Wp = w.Wp;
     u.t = t;
     if (od && t > 0) {
-        u.bc1 = 1.0 - pow((double)od->beta1, (double)t);
-        u.bc2_sqrt = (float)sqrt(1.0 - pow((double)od->beta2, (double)t));
+        bias_corrections(od, t, &u.bc1, &u.bc2_sqrt);
         u.one_minus_b1 = (float)(1.0 - (double)od->beta1);
         u.one_minus_b2 = (float)(1.0 - (double)od->beta2);
     }
@@ -1479,11 +1420,13 @@ FlowUpdArgs make_flow_upd_args(const CdnWs& w, int mode, float* FP, float* opt, 
     return u;
 }
 
-void launch_flow_update(const CdnWs& w, const InrFlowDesc* f, int n_images, int mode, float* FP, float* opt, float* grads_out,
-                        const InrOptDesc* od, float wd_g, int t, const float* lr_hdr, long long hdr_stride, hipStream_t s,
-                        const int32_t* status = nullptr, const float* gscale = nullptr) {
-    const FlowUpdArgs u = make_flow_upd_args(w, mode, FP, opt, grads_out, od, wd_g, t, lr_hdr, hdr_stride, status, gscale);
+static void launch_flow_update_args(const InrFlowDesc* f, int n_images, const FlowUpdArgs& u, hipStream_t s) {
     hipLaunchKernelGGL(flow_update_kernel, dim3(2 * f->num_coupling + 1, n_images), dim3(256), 0, s, u);
+}
+
+// modes 1 (gradients only) and 2 (effective weights only)
+void launch_flow_update(const CdnWs& w, const InrFlowDesc* f, int n_images, int mode, float* FP, float* grads_out, hipStream_t s) {
+    launch_flow_update_args(f, n_images, make_flow_upd_args(w, mode, FP, nullptr, grads_out, nullptr, 0.f, 0, nullptr, 0), s);
 }
 
 // the ICNN update `ui` and the flow's optimizer step in one launch (cdn_update_kernel)
@@ -1585,14 +1528,7 @@ static int check_cdn(const InrModelDesc* model, const InrFlowDesc* flow, const I
         if (!e) return INR_EUNSUPPORTED;
         if (e->c != 2) return INR_EUNSUPPORTED;   // the reference flow is 2-D only (diffeomorphism_net.py:288)
     }
-    if (!workspace || !grid || grid->n_points <= 0 || grid->n_points > 0x7fffffffLL || n_images <= 0) return INR_EINVAL;
-    if (grid->mode == INR_GRID_SEPARABLE) {
-        if (!grid->xs || !grid->ys || (long long)grid->width * grid->height != grid->n_points) return INR_EINVAL;
-    } else if (grid->mode == INR_GRID_EXPLICIT) {
-        if (!grid->coords) return INR_EINVAL;
-    } else {
-        return INR_EINVAL;
-    }
+    if (!workspace || !grid_ok(grid, n_images)) return INR_EINVAL;
     *w_out = carve_cdn(e, flow, grid, n_images, workspace);
     if (workspace_bytes < w_out->bytes) return INR_EWORKSPACE;
     if (e) w_out->icnn.set_user(e, model);
@@ -1627,7 +1563,7 @@ int inrfit_flow_forward(const InrFlowDesc* flow, const float* flow_params, const
     int rc = check_cdn(nullptr, flow, grid, n_images, workspace, workspace_bytes, false, &e, &w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);
+    launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, s);
     launch_flow_fwd(w, grid, n_images, out_coords, s);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
@@ -1640,103 +1576,12 @@ int inrfit_flow_backward(const InrFlowDesc* flow, const float* flow_params, cons
     int rc = check_cdn(nullptr, flow, grid, n_images, workspace, workspace_bytes, false, &e, &w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);
+    launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, s);
     if (hipMemcpyAsync(w.dxd, dout_coords, sizeof(float) * 2 * (size_t)grid->n_points * n_images, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return INR_ELAUNCH;
     launch_flow_bwd(w, flow, grid, n_images, s);   // recomputes the forward from the grid, walks the couplings backwards
-    launch_flow_update(w, flow, n_images, 1, (float*)flow_params, nullptr, flow_grads, nullptr, 0.f, 0, nullptr, 0, s);
+    launch_flow_update(w, flow, n_images, 1, (float*)flow_params, flow_grads, s);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-int inrfit_cdn_forward(const InrModelDesc* model, const InrFlowDesc* flow, const float* icnn_params, const float* flow_params,
-                       const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
-                       void* stream) {
-    const KernelEntry* e;
-    CdnWs w;
-    if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
-    int rc = check_cdn(model, flow, grid, n_images, workspace, workspace_bytes, true, &e, &w);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);
-    launch_flow_fwd(w, grid, n_images, w.xd, s);
-    if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
-    return launch_step(e, w.icnn, false, &w.dgrid, nullptr, 0, n_images, logits, s);
-}
-
-int inrfit_cdn_loss_grad(const InrModelDesc* model, const InrFlowDesc* flow, const float* icnn_params,
-                         const float* flow_params, const InrGridDesc* grid, const float* targets, const InrLossDesc* loss,
-                         int n_images, float* loss_out, float* icnn_grads, float* flow_grads, void* workspace,
-                         int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    CdnWs w;
-    if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
-    int rc = check_loss(loss);
-    if (rc) return rc;
-    if ((rc = check_cdn(model, flow, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);
-    launch_flow_fwd(w, grid, n_images, w.xd, s);
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
-    if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
-    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, targets, loss->kind, n_images, nullptr, s, w.dxd))) return rc;
-    launch_reduce(e, w.icnn, n_images, icnn_grads, loss_out, s);
-    launch_flow_bwd(w, flow, grid, n_images, s);
-    launch_flow_update(w, flow, n_images, 1, (float*)flow_params, nullptr, flow_grads, nullptr, 0.f, 0, nullptr, 0, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-int inrfit_cdn_fit(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
-                   float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* targets,
-                   const InrLossDesc* loss, const InrOptDesc* opt, float wd_on_weight_g, int n_images, int steps, int step0,
-                   float* loss_hist, float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes,
-                   void* stream) {
-    const KernelEntry* e;
-    CdnWs w;
-    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
-        return INR_EINVAL;
-    if (opt->kind != INR_OPT_ADAM) return INR_EINVAL;
-    int rc = check_loss(loss);
-    if (rc) return rc;
-    if (loss->kind == INR_LOSS_EXTERNAL) return INR_EINVAL;
-    if ((rc = check_cdn(model, flow, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
-    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, icnn_opt_state, w.icnn.Pu, *opt, step0);
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
-    launch_flow_update(w, flow, n_images, 2, flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);  // effective weights
-    UpdArgs u = make_upd_args(e, w.icnn, icnn_params, icnn_opt_state, loss_hist, status, opt, n_images, steps);
-    const dim3 ugrid = upd_grid(e->img.sl_cols, n_images), ublock = upd_block(e->img.sl_cols);
-    const long long hdr_stride = 2 * (long long)w.icnn.Pu + INR_OPT_HEADER_FLOATS;
-    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;   // see inrfit_fit
-    for (int it = 0; it < steps; ++it) {
-        w.icnn.set_step(step0 + it);
-        u.slabs = w.icnn.slabs;
-        launch_flow_fwd(w, grid, n_images, w.xd, s);
-        if ((rc = launch_step(e, w.icnn, true, &w.dgrid, targets, loss->kind, n_images,
-                              gate_logits && it == steps - 1 ? final_logits : nullptr, s, w.dxd))) return rc;
-        u.t = step0 + it + 1;
-        u.bc1 = 1.0 - pow((double)opt->beta1, (double)u.t);
-        u.bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)u.t));
-        u.hist_idx = it;
-        // the learning rate of THIS step sits in header[t & 1] (the plateau thread writes the next one into the other slot)
-        if (upd_union_ok(e->img.sl_cols, 2 * flow->num_coupling + 1)) {
-            launch_flow_bwd(w, flow, grid, n_images, s);
-            launch_cdn_update(e, u, make_flow_upd_args(w, 0, flow_params, flow_opt_state, nullptr, opt, wd_on_weight_g, u.t,
-                                                       icnn_opt_state + 2 * (size_t)w.icnn.Pu, hdr_stride), flow, n_images, s);
-        } else {
-            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
-            launch_flow_bwd(w, flow, grid, n_images, s);
-            launch_flow_update(w, flow, n_images, 0, flow_params, flow_opt_state, nullptr, opt, wd_on_weight_g, u.t,
-                               icnn_opt_state + 2 * (size_t)w.icnn.Pu, hdr_stride, s, status);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
-    if (final_logits && !gate_logits) {
-        launch_flow_fwd(w, grid, n_images, w.xd, s);
-        return launch_step(e, w.icnn, false, &w.dgrid, nullptr, 0, n_images, final_logits, s);
-    }
-    return INR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1886,15 +1731,8 @@ static int check_pcn(const InrModelDesc* model, const InrRnvpDesc* r, const InrG
         if (!e) return INR_EUNSUPPORTED;
         if (e->c != r->channels) return INR_EINVAL;
     }
-    if (!workspace || !grid || grid->n_points <= 0 || grid->n_points > 0x7fffffffLL || n_images <= 0) return INR_EINVAL;
-    if (grid->mode == INR_GRID_SEPARABLE) {
-        if (!grid->xs || !grid->ys || (long long)grid->width * grid->height != grid->n_points) return INR_EINVAL;
-        if (r->channels == 3 && !grid->ts) return INR_EINVAL;
-    } else if (grid->mode == INR_GRID_EXPLICIT) {
-        if (!grid->coords) return INR_EINVAL;
-    } else {
-        return INR_EINVAL;
-    }
+    if (!workspace || !grid_ok(grid, n_images)) return INR_EINVAL;
+    if (grid->mode == INR_GRID_SEPARABLE && r->channels == 3 && !grid->ts) return INR_EINVAL;   // the separable grid's t axis
     *w_out = carve_pcn(e, r, grid, n_images, workspace);
     if (workspace_bytes < w_out->bytes) return INR_EWORKSPACE;
     if (const int rc = rnvp_set_lds()) return rc;   // flow records of wide MLPs exceed the default 64 KB of dynamic LDS
@@ -2010,8 +1848,7 @@ RnvpUpdArgs make_rnvp_upd_args(const PcnWs& w, int n_images, int mode, float* rp
     u.chunks = w.chunks;
     u.t = t;
     if (od && t > 0) {
-        u.bc1 = 1.0 - pow((double)od->beta1, (double)t);
-        u.bc2_sqrt = (float)sqrt(1.0 - pow((double)od->beta2, (double)t));
+        bias_corrections(od, t, &u.bc1, &u.bc2_sqrt);
         u.one_minus_b1 = (float)(1.0 - (double)od->beta1);
         u.one_minus_b2 = (float)(1.0 - (double)od->beta2);
     }
@@ -2038,10 +1875,9 @@ static void launch_rnvp_update_args(const PcnWs& w, int n_images, const RnvpUpdA
     else hipLaunchKernelGGL(rnvp_update_kernel<3>, g, dim3(256), 0, s, u);
 }
 
-void launch_rnvp_update(const PcnWs& w, int n_images, int mode, float* rp, float* opt, float* grads_out, const InrOptDesc* od,
-                        float wd_flow, int t, const float* lr_hdr, long long hdr_stride, const int32_t* status, hipStream_t s) {
-    launch_rnvp_update_args(w, n_images, make_rnvp_upd_args(w, n_images, mode, rp, opt, grads_out, od, wd_flow, t, lr_hdr,
-                                                             hdr_stride, status), s);
+// mode 1: gradients only
+void launch_rnvp_grads(const PcnWs& w, int n_images, float* rp, float* grads_out, hipStream_t s) {
+    launch_rnvp_update_args(w, n_images, make_rnvp_upd_args(w, n_images, 1, rp, nullptr, grads_out, nullptr, 0.f, 0, nullptr, 0, nullptr), s);
 }
 
 }  // namespace
@@ -2175,95 +2011,6 @@ int inrfit_rnvp_fit_identity(const InrRnvpDesc* rnvp, float* flow_params, float*
         launch_rnvp_update_args(w, n_images, u, s);
     }
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-int inrfit_pcn_forward(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params, const float* flow_params,
-                       const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
-                       void* stream) {
-    const KernelEntry* e;
-    PcnWs w;
-    if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
-    int rc = check_pcn(model, rnvp, grid, n_images, workspace, workspace_bytes, true, &e, &w);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    launch_rnvp_fwd(w, flow_params, grid, n_images, w.xd, false, s);
-    if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
-    return launch_step(e, w.icnn, false, &w.dgrid, nullptr, 0, n_images, logits, s);
-}
-
-int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params,
-                         const float* flow_params, const InrGridDesc* grid, const float* targets, const InrLossDesc* loss,
-                         int n_images, float* loss_out, float* icnn_grads, float* flow_grads, void* workspace,
-                         int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    PcnWs w;
-    if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
-    int rc = check_loss(loss);
-    if (rc) return rc;
-    if ((rc = check_pcn(model, rnvp, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    launch_rnvp_fwd(w, flow_params, grid, n_images, w.xd, true, s);
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
-    if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
-    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, targets, loss->kind, n_images, nullptr, s, w.dxd))) return rc;
-    launch_reduce(e, w.icnn, n_images, icnn_grads, loss_out, s);
-    launch_rnvp_bwd(w, flow_params, grid, n_images, s);
-    launch_rnvp_update(w, n_images, 1, (float*)flow_params, nullptr, flow_grads, nullptr, 0.f, 0, nullptr, 0, nullptr, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
-                   float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* targets,
-                   const InrLossDesc* loss, const InrOptDesc* opt, float flow_weight_decay, int n_images, int steps, int step0,
-                   float* loss_hist, float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes,
-                   void* stream) {
-    const KernelEntry* e;
-    PcnWs w;
-    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
-        return INR_EINVAL;
-    if (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) return INR_EINVAL;
-    int rc = check_loss(loss);
-    if (rc) return rc;
-    if (loss->kind == INR_LOSS_EXTERNAL) return INR_EINVAL;
-    if ((rc = check_pcn(model, rnvp, grid, n_images, workspace, workspace_bytes, true, &e, &w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, w.icnn.coef, 1.f);
-    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, icnn_opt_state, w.icnn.Pu, *opt, step0);
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, w.icnn, icnn_params, n_images, s))) return rc;
-    UpdArgs u = make_upd_args(e, w.icnn, icnn_params, icnn_opt_state, loss_hist, status, opt, n_images, steps);
-    const dim3 ugrid = upd_grid(e->img.sl_cols, n_images), ublock = upd_block(e->img.sl_cols);
-    const long long hdr_stride = 2 * (long long)w.icnn.Pu + INR_OPT_HEADER_FLOATS;
-    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;   // see inrfit_fit
-    for (int it = 0; it < steps; ++it) {
-        w.icnn.set_step(step0 + it);
-        u.slabs = w.icnn.slabs;
-        launch_rnvp_fwd(w, flow_params, grid, n_images, w.xd, true, s, false, it > 0);
-        if ((rc = launch_step(e, w.icnn, true, &w.dgrid, targets, loss->kind, n_images,
-                              gate_logits && it == steps - 1 ? final_logits : nullptr, s, w.dxd))) return rc;
-        u.t = step0 + it + 1;
-        u.bc1 = 1.0 - pow((double)opt->beta1, (double)u.t);
-        u.bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)u.t));
-        u.hist_idx = it;
-        // the learning rate of THIS step sits in header[t & 1] (the plateau thread writes the next one into the other slot)
-        RnvpUpdArgs ru = make_rnvp_upd_args(w, n_images, 0, flow_params, flow_opt_state, nullptr, opt, flow_weight_decay, u.t,
-                                            icnn_opt_state + 2 * (size_t)w.icnn.Pu, hdr_stride, status);
-        ru.RE = w.RE;
-        if (upd_union_ok(e->img.sl_cols, w.rm.F + 1)) {
-            launch_rnvp_bwd(w, flow_params, grid, n_images, s);
-            launch_pcn_update(e, w, u, ru, n_images, s);
-        } else {
-            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
-            launch_rnvp_bwd(w, flow_params, grid, n_images, s);
-            launch_rnvp_update_args(w, n_images, ru, s);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
-    if (final_logits && !gate_logits) {
-        launch_rnvp_fwd(w, flow_params, grid, n_images, w.xd, false, s);
-        return launch_step(e, w.icnn, false, &w.dgrid, nullptr, 0, n_images, final_logits, s);
-    }
-    return INR_OK;
 }
 
 int64_t inrfit_joint_loss_workspace_bytes(int64_t n_elems) {
@@ -2492,11 +2239,16 @@ static void joint_dseg(const JointCtx& c, float* dseg, hipStream_t s) {
     hipLaunchKernelGGL(joint_loss_grad_kernel<true>, dim3(c.jl.blocks), dim3(256), 0, s, c.jl, (const float*)c.logits, dseg);
 }
 
-static void set_step_consts(UpdArgs& u, const InrOptDesc* opt, int t) {
-    u.t = t;
-    u.bc1 = 1.0 - pow((double)opt->beta1, (double)t);
-    u.bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)t));
-    u.hist_idx = 0;
+// the ICNN update of a joint step: one optimizer step per call, so no plateau scheduler; the reduced gradient is scaled by the finish
+// kernel's `gscale`
+static UpdArgs joint_upd_args(const KernelEntry* e, const Workspace& w, float* params, float* opt_state, int32_t* status,
+                              const InrOptDesc* opt, int step, const float* gscale) {
+    InrOptDesc o = *opt;
+    o.plateau = 0;
+    UpdArgs u = make_upd_args(e, w, params, opt_state, nullptr, status, &o, 1, 1);
+    u.gscale = gscale;
+    set_step_consts(u, &o, step);
+    return u;
 }
 
 long long joint_ws_bytes(long long N) { return align256(inrfit_joint_loss_workspace_bytes(N)) + align256(N * 4); }
@@ -2509,35 +2261,316 @@ int64_t inrfit_joint_step_workspace_bytes(const InrModelDesc* model, const InrGr
     return align256(b) + joint_ws_bytes(grid->n_points);
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the three prior families on the ICNN step kernel: one driver per operation (forward, loss + gradients, fit, fused joint step)
+// ---------------------------------------------------------------------------------------------------------------------
+// The families differ only in the deformation in front of the ICNN: a workspace type with
+//   icnn, dgrid, dxd, bytes    the ICNN's Workspace, the grid its step kernel reads, where that kernel writes dL/dcoords (null: it
+//                              writes none), the bytes of the whole workspace
+//   check(...)                 argument checks, workspace carve, set_lds; the ICNN's kernel entry into *e
+//   begin(s)                   once per call, in front of the first forward
+//   forward(train, packed, s)  the coordinates the ICNN sees into dgrid (train: keep what the backward reads)
+//   gradients(s)               loss_grad: the deformation's backward and its gradients (mode 1)
+//   update(e, u, fit, s)       the deformation's backward and both optimizer steps, the ICNN's `u` included: where upd_union_ok
+//                              allows, the backward and then one combined update launch; else icnn_update_kernel, the backward and
+//                              the deformation's own update.  `u` carries status (fit and joint step) and gscale (joint step only).
+namespace {
+
+struct IcnnOnly {   // ConvexNet / ConvexNextNet: the ICNN on the caller's grid
+    Workspace icnn;
+    InrGridDesc dgrid;
+    float* dxd = nullptr;
+    long long bytes = 0;
+    int check(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* ws, int64_t ws_bytes, const KernelEntry** e) {
+        if (const int rc = prepare(model, grid, n_images, ws, ws_bytes, e, &icnn)) return rc;
+        dgrid = *grid;
+        bytes = icnn.bytes;
+        return INR_OK;
+    }
+    void begin(hipStream_t) {}
+    void forward(bool, bool, hipStream_t) {}
+    void gradients(hipStream_t) {}
+    void update(const KernelEntry* e, const UpdArgs& u, bool, hipStream_t s) { launch_icnn_update(e, u, s); }
+};
+
+struct CdnStep : CdnWs {   // ConvexDiffeomorphismNet: the ICNN behind the weight-normed coupling flow
+    const InrFlowDesc* flow;
+    float *params, *opt_state, *grads;   // the flow's (opt_state: fit and joint step; grads: loss_grad)
+    float wd_g;                          // weight decay on weight_g
+    const InrGridDesc* grid = nullptr;   // the caller's
+    int n_images = 0;
+    CdnStep(const InrFlowDesc* f, const float* p, float* o = nullptr, float* g = nullptr, float wd = 0.f)
+        : flow(f), params(const_cast<float*>(p)), opt_state(o), grads(g), wd_g(wd) {}
+    int check(const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, const KernelEntry** e) {
+        grid = g;
+        n_images = n;
+        return check_cdn(model, flow, g, n, ws, ws_bytes, true, e, this);
+    }
+    // the flow's effective weights (mode 2): once per call; in the fit, the update kernel rebuilds them after every step
+    void begin(hipStream_t s) { launch_flow_update(*this, flow, n_images, 2, params, nullptr, s); }
+    void forward(bool, bool, hipStream_t s) { launch_flow_fwd(*this, grid, n_images, xd, s); }
+    void gradients(hipStream_t s) {
+        launch_flow_bwd(*this, flow, grid, n_images, s);
+        launch_flow_update(*this, flow, n_images, 1, params, grads, s);
+    }
+    void update(const KernelEntry* e, const UpdArgs& u, bool, hipStream_t s) {
+        // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
+        const FlowUpdArgs uf = make_flow_upd_args(*this, 0, params, opt_state, nullptr, &u.opt, wd_g, u.t, u.opt_state + 2 * (size_t)u.Pu,
+                                                  2 * (long long)u.Pu + INR_OPT_HEADER_FLOATS, u.status, u.gscale);
+        if (upd_union_ok(e->img.sl_cols, 2 * flow->num_coupling + 1)) {
+            launch_flow_bwd(*this, flow, grid, n_images, s);
+            launch_cdn_update(e, u, uf, flow, n_images, s);   // (the ICNN half writes `status`: the flow half gets none)
+        } else {
+            launch_icnn_update(e, u, s);
+            launch_flow_bwd(*this, flow, grid, n_images, s);
+            launch_flow_update_args(flow, n_images, uf, s);
+        }
+    }
+};
+
+struct PcnStep : PcnWs {   // PathConnectedNet: the ICNN behind the normflows RealNVP
+    const InrRnvpDesc* rnvp;
+    float *params, *opt_state, *grads;   // the RealNVP's (opt_state: fit and joint step; grads: loss_grad)
+    float wd;                            // its weight decay
+    const InrGridDesc* grid = nullptr;   // the caller's
+    int n_images = 0;
+    PcnStep(const InrRnvpDesc* r, const float* p, float* o = nullptr, float* g = nullptr, float w = 0.f)
+        : rnvp(r), params(const_cast<float*>(p)), opt_state(o), grads(g), wd(w) {}
+    int check(const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, const KernelEntry** e) {
+        grid = g;
+        n_images = n;
+        return check_pcn(model, rnvp, g, n, ws, ws_bytes, true, e, this);
+    }
+    void begin(hipStream_t) {}
+    // the parameters are packed into RE in front of the forward - except in the fit after its first step (`packed`), where the update
+    // kernel has refreshed RE (update with fit = true)
+    void forward(bool train, bool packed, hipStream_t s) { launch_rnvp_fwd(*this, params, grid, n_images, xd, train, s, false, packed); }
+    void gradients(hipStream_t s) {
+        launch_rnvp_bwd(*this, params, grid, n_images, s);
+        launch_rnvp_grads(*this, n_images, params, grads, s);
+    }
+    void update(const KernelEntry* e, const UpdArgs& u, bool fit, hipStream_t s) {
+        // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
+        RnvpUpdArgs ru = make_rnvp_upd_args(*this, n_images, 0, params, opt_state, nullptr, &u.opt, wd, u.t, u.opt_state + 2 * (size_t)u.Pu,
+                                            2 * (long long)u.Pu + INR_OPT_HEADER_FLOATS, u.status);
+        ru.gscale = u.gscale;
+        if (fit) ru.RE = RE;   // the next step's forward reuses it (`packed`)
+        if (upd_union_ok(e->img.sl_cols, rm.F + 1)) {
+            launch_rnvp_bwd(*this, params, grid, n_images, s);
+            launch_pcn_update(e, *this, u, ru, n_images, s);   // (the ICNN half writes `status`: the RealNVP half gets none)
+        } else {
+            launch_icnn_update(e, u, s);
+            launch_rnvp_bwd(*this, params, grid, n_images, s);
+            launch_rnvp_update_args(*this, n_images, ru, s);
+        }
+    }
+};
+
+// the optimizer and loss rules of the fits (a fit evaluates its own loss: no INR_LOSS_EXTERNAL)
+static int check_fit(const InrOptDesc* opt, const InrLossDesc* loss, bool adam_only) {
+    if (opt->kind != INR_OPT_ADAM && (adam_only || opt->kind != INR_OPT_ADAMAX)) return INR_EINVAL;
+    if (const int rc = check_loss(loss)) return rc;
+    return loss->kind == INR_LOSS_EXTERNAL ? INR_EINVAL : INR_OK;
+}
+
+template <class D>
+int forward_run(D d, const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
+                void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    const KernelEntry* e;
+    int rc = d.check(model, grid, n_images, workspace, workspace_bytes, &e);
+    if (rc) return rc;
+    d.begin(s);
+    d.forward(false, false, s);
+    if ((rc = launch_pack(e, d.icnn, params, n_images, s))) return rc;
+    return launch_step(e, d.icnn, false, &d.dgrid, nullptr, 0, n_images, logits, s);
+}
+
+template <class D>
+int loss_grad_run(D d, const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
+                  const InrLossDesc* loss, int n_images, float* loss_out, float* grads, void* workspace, int64_t workspace_bytes,
+                  hipStream_t s) {
+    const KernelEntry* e;
+    int rc = d.check(model, grid, n_images, workspace, workspace_bytes, &e);
+    if (rc) return rc;
+    d.begin(s);
+    d.forward(true, false, s);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, d.icnn.coef, 1.f);
+    if ((rc = launch_pack(e, d.icnn, params, n_images, s))) return rc;
+    if ((rc = launch_step(e, d.icnn, true, &d.dgrid, targets, loss->kind, n_images, nullptr, s, d.dxd))) return rc;
+    launch_reduce(e, d.icnn, n_images, grads, loss_out, s);
+    d.gradients(s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+template <class D>
+int fit_run(D d, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
+            const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist, float* final_logits,
+            int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    const KernelEntry* e;
+    int rc = d.check(model, grid, n_images, workspace, workspace_bytes, &e);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, d.icnn.coef, 1.f);
+    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, d.icnn.Pu, *opt, step0);
+    if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
+    if ((rc = launch_pack(e, d.icnn, params, n_images, s))) return rc;
+    d.begin(s);
+    UpdArgs u = make_upd_args(e, d.icnn, params, opt_state, loss_hist, status, opt, n_images, steps);
+    // opt->logits_at_last_forward: final_logits = the output of the LAST training forward (parameters before the last optimizer
+    // step) - what the reference's IoU gate looks at (path_connected_net.py:939-972) - written by that step's launch itself
+    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
+    for (int it = 0; it < steps; ++it) {
+        d.icnn.set_step(step0 + it);
+        u.slabs = d.icnn.slabs;
+        set_step_consts(u, opt, step0 + it + 1, it);
+        float* logits = gate_logits && it == steps - 1 ? final_logits : nullptr;
+        d.forward(true, it > 0, s);
+        // bench.py's timing hooks (inrfit_timing_*) bracket the plain ICNN fit's launches only: events in the deformed fits would
+        // change what is launched and measured there
+        if constexpr (std::is_same<D, IcnnOnly>::value) {
+            if ((rc = launch_step_timed(e, d.icnn, &d.dgrid, targets, loss->kind, n_images, s, logits))) return rc;
+            if ((rc = launch_icnn_update_timed(e, u, s))) return rc;
+        } else {
+            if ((rc = launch_step(e, d.icnn, true, &d.dgrid, targets, loss->kind, n_images, logits, s, d.dxd))) return rc;
+            d.update(e, u, true, s);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
+    if (final_logits && !gate_logits) {
+        d.forward(false, false, s);
+        return launch_step(e, d.icnn, false, &d.dgrid, nullptr, 0, n_images, final_logits, s);
+    }
+    return INR_OK;
+}
+
+template <class D>
+int joint_step_run(D d, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                   const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out, float* dseg,
+                   float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    const KernelEntry* e;
+    int rc = d.check(model, grid, 1, workspace, workspace_bytes, &e);
+    if (rc) return rc;
+    const long long N = grid->n_points;
+    if (workspace_bytes < align256(d.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
+    float* jws = (float*)((char*)workspace + align256(d.bytes));
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    JointCtx c;
+    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, opt_state + 2 * (size_t)d.icnn.Pu, d.icnn.coef, s, &c))) return rc;
+    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
+    if ((rc = launch_pack(e, d.icnn, params, 1, s))) return rc;
+    d.icnn.set_step(step);
+    d.begin(s);
+    d.forward(true, false, s);
+    if ((rc = launch_step(e, d.icnn, true, &d.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, d.dxd, c.align_seg, c.c_align)))
+        return rc;
+    joint_finish(c, e, d.icnn, loss_out, s);
+    d.update(e, joint_upd_args(e, d.icnn, params, opt_state, status, opt, step, c.gscale), false, s);
+    joint_dseg(c, dseg, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+}  // namespace
+
+extern "C" {
+
+int inrfit_forward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
+                   void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!params || !logits) return INR_EINVAL;
+    if (use_wide(model)) return wide_forward_all(model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
+    return forward_run(IcnnOnly(), model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_cdn_forward(const InrModelDesc* model, const InrFlowDesc* flow, const float* icnn_params, const float* flow_params,
+                       const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+    if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
+    return forward_run(CdnStep(flow, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
+int inrfit_pcn_forward(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params, const float* flow_params,
+                       const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+    if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
+    return forward_run(PcnStep(rnvp, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
+int inrfit_loss_grad(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
+                     const InrLossDesc* loss, int n_images, float* loss_out, float* grads, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+    if (!params || !targets || !loss_out || !grads) return INR_EINVAL;
+    if (const int rc = check_loss(loss)) return rc;
+    if (use_wide(model))
+        return wide_loss_grad_all(model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes, (hipStream_t)stream);
+    return loss_grad_run(IcnnOnly(), model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+}
+
+int inrfit_cdn_loss_grad(const InrModelDesc* model, const InrFlowDesc* flow, const float* icnn_params,
+                         const float* flow_params, const InrGridDesc* grid, const float* targets, const InrLossDesc* loss,
+                         int n_images, float* loss_out, float* icnn_grads, float* flow_grads, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+    if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
+    if (const int rc = check_loss(loss)) return rc;
+    return loss_grad_run(CdnStep(flow, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images, loss_out,
+                         icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params,
+                         const float* flow_params, const InrGridDesc* grid, const float* targets, const InrLossDesc* loss,
+                         int n_images, float* loss_out, float* icnn_grads, float* flow_grads, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+    if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
+    if (const int rc = check_loss(loss)) return rc;
+    return loss_grad_run(PcnStep(rnvp, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images, loss_out,
+                         icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_fit(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
+               const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist,
+               float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!params || !opt_state || !targets || !opt || steps < 0 || step0 < 0) return INR_EINVAL;
+    if (const int rc = check_fit(opt, loss, false)) return rc;
+    if (use_wide(model))
+        return wide_fit(model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status,
+                        workspace, workspace_bytes, (hipStream_t)stream);
+    return fit_run(IcnnOnly(), model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status,
+                   workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_cdn_fit(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
+                   float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* targets,
+                   const InrLossDesc* loss, const InrOptDesc* opt, float wd_on_weight_g, int n_images, int steps, int step0,
+                   float* loss_hist, float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes,
+                   void* stream) {
+    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
+        return INR_EINVAL;
+    if (const int rc = check_fit(opt, loss, true)) return rc;   // the flow's optimizer step is Adam's only
+    return fit_run(CdnStep(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params, icnn_opt_state, grid, targets,
+                   loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
+                   float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* targets,
+                   const InrLossDesc* loss, const InrOptDesc* opt, float flow_weight_decay, int n_images, int steps, int step0,
+                   float* loss_hist, float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes,
+                   void* stream) {
+    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
+        return INR_EINVAL;
+    if (const int rc = check_fit(opt, loss, false)) return rc;
+    return fit_run(PcnStep(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params, icnn_opt_state, grid,
+                   targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
+                   (hipStream_t)stream);
+}
+
 int inrfit_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
                       const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
                       float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    Workspace w;
     if (!params || !opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    int rc = prepare(model, grid, 1, workspace, workspace_bytes, &e, &w);
-    if (rc) return rc;
-    const long long N = grid->n_points;
-    if (workspace_bytes < inrfit_joint_step_workspace_bytes(model, grid)) return INR_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* jws = (float*)((char*)workspace + align256(w.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    JointCtx c;
-    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, opt_state + 2 * (size_t)w.Pu, w.coef, s, &c))) return rc;
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, w, params, 1, s))) return rc;
-    w.set_step(step);
-    if ((rc = launch_step(e, w, true, grid, c.prior_targets, c.prior_loss.kind, 1, logits, s, nullptr, c.align_seg, c.c_align))) return rc;
-    joint_finish(c, e, w, loss_out, s);
-    InrOptDesc o = *opt;
-    o.plateau = 0;
-    UpdArgs u = make_upd_args(e, w, params, opt_state, nullptr, status, &o, 1, 1);
-    u.slabs = w.slabs;
-    u.gscale = c.gscale;
-    set_step_consts(u, &o, step);
-    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, 1), upd_block(e->img.sl_cols), 0, s, u);
-    joint_dseg(c, dseg, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    return joint_step_run(IcnnOnly(), model, params, opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status,
+                          workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_pcn_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
@@ -2545,45 +2578,10 @@ int inrfit_pcn_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, fl
                           const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, float flow_weight_decay,
                           int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    PcnWs w;
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    int rc = check_pcn(model, rnvp, grid, 1, workspace, workspace_bytes, true, &e, &w);
-    if (rc) return rc;
-    const long long N = grid->n_points;
-    if (workspace_bytes < align256(w.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* jws = (float*)((char*)workspace + align256(w.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    JointCtx c;
-    float* hdr = icnn_opt_state + 2 * (size_t)w.icnn.Pu;
-    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, hdr, w.icnn.coef, s, &c))) return rc;
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, w.icnn, icnn_params, 1, s))) return rc;
-    w.icnn.set_step(step);
-    launch_rnvp_fwd(w, flow_params, grid, 1, w.xd, true, s);
-    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, w.dxd, c.align_seg,
-                              c.c_align))) return rc;
-    joint_finish(c, e, w.icnn, loss_out, s);
-    InrOptDesc o = *opt;
-    o.plateau = 0;
-    UpdArgs u = make_upd_args(e, w.icnn, icnn_params, icnn_opt_state, nullptr, status, &o, 1, 1);
-    u.slabs = w.icnn.slabs;
-    u.gscale = c.gscale;
-    set_step_consts(u, &o, step);
-    RnvpUpdArgs ru = make_rnvp_upd_args(w, 1, 0, flow_params, flow_opt_state, nullptr, &o, flow_weight_decay, step, hdr,
-                                        2 * (long long)w.icnn.Pu + INR_OPT_HEADER_FLOATS, status);
-    ru.gscale = c.gscale;
-    if (upd_union_ok(e->img.sl_cols, w.rm.F + 1)) {
-        launch_rnvp_bwd(w, flow_params, grid, 1, s);
-        launch_pcn_update(e, w, u, ru, 1, s);
-    } else {
-        hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, 1), upd_block(e->img.sl_cols), 0, s, u);
-        launch_rnvp_bwd(w, flow_params, grid, 1, s);
-        launch_rnvp_update_args(w, 1, ru, s);
-    }
-    joint_dseg(c, dseg, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    return joint_step_run(PcnStep(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params, icnn_opt_state, grid,
+                          seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace, workspace_bytes,
+                          (hipStream_t)stream);
 }
 
 int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
@@ -2591,47 +2589,11 @@ int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, fl
                           const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, float wd_on_weight_g,
                           int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    CdnWs w;
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    if (!opt || opt->kind != INR_OPT_ADAM) return INR_EINVAL;
-    int rc = check_cdn(model, flow, grid, 1, workspace, workspace_bytes, true, &e, &w);
-    if (rc) return rc;
-    const long long N = grid->n_points;
-    if (workspace_bytes < align256(w.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* jws = (float*)((char*)workspace + align256(w.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    JointCtx c;
-    float* hdr = icnn_opt_state + 2 * (size_t)w.icnn.Pu;
-    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, hdr, w.icnn.coef, s, &c))) return rc;
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, w.icnn, icnn_params, 1, s))) return rc;
-    w.icnn.set_step(step);
-    launch_flow_update(w, flow, 1, 2, flow_params, nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, s);  // effective weights
-    launch_flow_fwd(w, grid, 1, w.xd, s);
-    if ((rc = launch_step(e, w.icnn, true, &w.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, w.dxd, c.align_seg,
-                              c.c_align))) return rc;
-    joint_finish(c, e, w.icnn, loss_out, s);
-    InrOptDesc o = *opt;
-    o.plateau = 0;
-    UpdArgs u = make_upd_args(e, w.icnn, icnn_params, icnn_opt_state, nullptr, status, &o, 1, 1);
-    u.slabs = w.icnn.slabs;
-    u.gscale = c.gscale;
-    set_step_consts(u, &o, step);
-    const long long hdr_stride = 2 * (long long)w.icnn.Pu + INR_OPT_HEADER_FLOATS;
-    if (upd_union_ok(e->img.sl_cols, 2 * flow->num_coupling + 1)) {
-        launch_flow_bwd(w, flow, grid, 1, s);
-        launch_cdn_update(e, u, make_flow_upd_args(w, 0, flow_params, flow_opt_state, nullptr, &o, wd_on_weight_g, step, hdr, hdr_stride,
-                                                   nullptr, c.gscale), flow, 1, s);
-    } else {
-        hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, 1), upd_block(e->img.sl_cols), 0, s, u);
-        launch_flow_bwd(w, flow, grid, 1, s);
-        launch_flow_update(w, flow, 1, 0, flow_params, flow_opt_state, nullptr, &o, wd_on_weight_g, step, hdr, hdr_stride, s, status,
-                           c.gscale);
-    }
-    joint_dseg(c, dseg, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    if (!opt || opt->kind != INR_OPT_ADAM) return INR_EINVAL;   // the flow's optimizer step is Adam's only (checked before the model)
+    return joint_step_run(CdnStep(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params, icnn_opt_state, grid,
+                          seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace, workspace_bytes,
+                          (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2799,13 +2761,7 @@ int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt
     f.gscale = gscale;
     f.loss_out = loss_out;
     hipLaunchKernelGGL(joint_prior_finish_kernel, dim3(1), dim3(256), 0, s, f);
-    InrOptDesc o = *opt;
-    o.plateau = 0;
-    UpdArgs u = make_upd_args(e, w, params, opt_state, nullptr, status, &o, 1, 1);
-    u.slabs = w.slabs;
-    u.gscale = gscale;
-    set_step_consts(u, &o, step);
-    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, 1), upd_block(e->img.sl_cols), 0, s, u);
+    launch_icnn_update(e, joint_upd_args(e, w, params, opt_state, status, opt, step, gscale), s);
     const bool soft = desc->align_rule == INR_ALIGN_SOFT;
     hipLaunchKernelGGL(joint_prior_dseg_kernel, dim3(pa.blocks), dim3(256), 0, s, (const float*)logits, seg, N, m.align_begin, soft ? 1 : 0,
                        soft ? -2.f * desc->beta / (float)n_align : 0.f, dseg);
@@ -2855,11 +2811,11 @@ static void star_upd_consts(StarUpdArgs& u, const InrOptDesc* opt, int t, int t_
     u.eps = opt->eps;
     u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
     u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
-    u.bc1 = 1.0 - pow((double)opt->beta1, (double)t);
-    u.bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)t));
+    bias_corrections(opt, t, &u.bc1, &u.bc2_sqrt);
     u.offset_on = t_off > 0;
-    u.bc1_off = t_off > 0 ? 1.0 - pow((double)opt->beta1, (double)t_off) : 1.0;
-    u.bc2_sqrt_off = t_off > 0 ? (float)sqrt(1.0 - pow((double)opt->beta2, (double)t_off)) : 1.f;
+    u.bc1_off = 1.0;
+    u.bc2_sqrt_off = 1.f;
+    if (t_off > 0) bias_corrections(opt, t_off, &u.bc1_off, &u.bc2_sqrt_off);
 }
 
 int inrfit_star_loss_grad(const InrStarDesc* star, const float* params, const float* coords, const float* labels, int64_t n_pixels,

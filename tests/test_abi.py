@@ -100,3 +100,170 @@ def test_gemm_kernels_keep_four_workgroups_per_cu():
     for k in buf:
         assert k["vgpr_count"] <= 128 and k["group_segment_fixed_size"] <= 40960, k
         assert k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
+
+
+# ---- single-fault table of the ICNN / coupling-flow / RealNVP entry points ------------------------------------------------
+# Each case is a valid call with ONE argument spoiled; the entry point must reject it before its first HIP call (so this runs
+# without a GPU: no case may get as far as a launch).  The code pins the order of the argument checks.
+_FAKE = 0x1000   # a device pointer that is never dereferenced: every case below is rejected on the host
+
+
+def _fault_args(**over):
+    from awesome_amd import _lib as L
+    a = dict(model=(130, 2, 1, 0), flow=(130, 6, L.INR_FLOW_NORMAL_BLOCK), rnvp_c=2, rnvp_flows=4,
+             grid=(L.INR_GRID_SEPARABLE, 16, 16, 256, _FAKE, _FAKE, None, None), loss=(L.INR_LOSS_SE, L.INR_WEIGHT_NONE),
+             opt=L.INR_OPT_ADAM, joint=L.JOINT_FBMS, n=1, steps=1, step0=0, step=1, ws=_FAKE, wsb=1 << 40,
+             params=_FAKE, flow_params=_FAKE, opt_state=_FAKE, flow_opt_state=_FAKE, targets=_FAKE, logits=_FAKE, loss_out=_FAKE,
+             grads=_FAKE, flow_grads=_FAKE, seg=_FAKE, target=_FAKE, dseg=_FAKE)
+    a.update(over)
+    h, c, layers, act0 = a["model"]
+    a["model"] = L.InrModelDesc(L.INR_MODEL_ICNN, h, c, layers, act0, 0.0, 0, 0)
+    a["flow"] = L.InrFlowDesc(*a["flow"])
+    r = L.InrRnvpDesc()
+    r.channels, r.hidden_units, r.n_flows, r.output_scale = a["rnvp_c"], 32, a["rnvp_flows"], 1.0
+    for k in range(3):
+        r.vmin[k], r.vmax[k] = 0.0, 1.0
+    r.new_min, r.new_max = 0.0, 1.0
+    for f in range(L.INR_RNVP_MAX_FLOWS):
+        r.masks[f] = 1 + f % 2
+    a["rnvp"] = r
+    a["grid"] = L.InrGridDesc(*a["grid"], 0)
+    a["loss"] = None if a["loss"] is None else L.InrLossDesc(*a["loss"], 1.0, 0.0, 0.0)
+    a["opt"] = None if a["opt"] is None else L.InrOptDesc(a["opt"], 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, 0, 0, 1.0, 0.0, 0.0, 0.0, 0, 0, 0)
+    jd = L.InrJointLossDesc()
+    jd.kind, jd.weight_mode, jd.ratio, jd.alpha, jd.beta, jd.form = L.INR_LOSS_SE, L.INR_WEIGHT_NONE, 1.0, 1.0, 1.0, a["joint"]
+    a["joint"] = jd
+    return a
+
+
+_ENTRY = {
+    "forward": lambda lib, a: lib.inrfit_forward(a["model"], a["params"], a["grid"], a["n"], a["logits"], a["ws"], a["wsb"], None),
+    "loss_grad": lambda lib, a: lib.inrfit_loss_grad(a["model"], a["params"], a["grid"], a["targets"], a["loss"], a["n"], a["loss_out"],
+                                                     a["grads"], a["ws"], a["wsb"], None),
+    "fit": lambda lib, a: lib.inrfit_fit(a["model"], a["params"], a["opt_state"], a["grid"], a["targets"], a["loss"], a["opt"], a["n"],
+                                         a["steps"], a["step0"], None, None, None, a["ws"], a["wsb"], None),
+    "cdn_forward": lambda lib, a: lib.inrfit_cdn_forward(a["model"], a["flow"], a["params"], a["flow_params"], a["grid"], a["n"],
+                                                         a["logits"], a["ws"], a["wsb"], None),
+    "cdn_loss_grad": lambda lib, a: lib.inrfit_cdn_loss_grad(a["model"], a["flow"], a["params"], a["flow_params"], a["grid"], a["targets"],
+                                                             a["loss"], a["n"], a["loss_out"], a["grads"], a["flow_grads"], a["ws"],
+                                                             a["wsb"], None),
+    "cdn_fit": lambda lib, a: lib.inrfit_cdn_fit(a["model"], a["flow"], a["params"], a["flow_params"], a["opt_state"], a["flow_opt_state"],
+                                                 a["grid"], a["targets"], a["loss"], a["opt"], 0.0, a["n"], a["steps"], a["step0"], None,
+                                                 None, None, a["ws"], a["wsb"], None),
+    "pcn_forward": lambda lib, a: lib.inrfit_pcn_forward(a["model"], a["rnvp"], a["params"], a["flow_params"], a["grid"], a["n"],
+                                                         a["logits"], a["ws"], a["wsb"], None),
+    "pcn_loss_grad": lambda lib, a: lib.inrfit_pcn_loss_grad(a["model"], a["rnvp"], a["params"], a["flow_params"], a["grid"], a["targets"],
+                                                             a["loss"], a["n"], a["loss_out"], a["grads"], a["flow_grads"], a["ws"],
+                                                             a["wsb"], None),
+    "pcn_fit": lambda lib, a: lib.inrfit_pcn_fit(a["model"], a["rnvp"], a["params"], a["flow_params"], a["opt_state"], a["flow_opt_state"],
+                                                 a["grid"], a["targets"], a["loss"], a["opt"], 0.0, a["n"], a["steps"], a["step0"], None,
+                                                 None, None, a["ws"], a["wsb"], None),
+    "joint_step": lambda lib, a: lib.inrfit_joint_step(a["model"], a["params"], a["opt_state"], a["grid"], a["seg"], a["target"], a["joint"],
+                                                       a["opt"], a["step"], None, a["dseg"], None, None, a["ws"], a["wsb"], None),
+    "pcn_joint_step": lambda lib, a: lib.inrfit_pcn_joint_step(a["model"], a["rnvp"], a["params"], a["flow_params"], a["opt_state"],
+                                                               a["flow_opt_state"], a["grid"], a["seg"], a["target"], a["joint"], a["opt"],
+                                                               0.0, a["step"], None, a["dseg"], None, None, a["ws"], a["wsb"], None),
+    "cdn_joint_step": lambda lib, a: lib.inrfit_cdn_joint_step(a["model"], a["flow"], a["params"], a["flow_params"], a["opt_state"],
+                                                               a["flow_opt_state"], a["grid"], a["seg"], a["target"], a["joint"], a["opt"],
+                                                               0.0, a["step"], None, a["dseg"], None, None, a["ws"], a["wsb"], None),
+}
+
+_EINVAL, _EUNSUPPORTED, _EWORKSPACE = -1, -2, -3
+_SEP3_NO_TS = (0, 16, 16, 256, _FAKE, _FAKE, None, None)     # separable C = 3 grid without its t axis
+_BAD_MODE = (7, 16, 16, 256, _FAKE, _FAKE, None, None)
+_NO_COORDS = (1, 16, 16, 256, None, None, None, None)        # explicit grid without coordinates
+_NEG_SIDES = (0, -16, -16, 256, _FAKE, _FAKE, None, None)    # width x height = n_points, but the sides are negative
+_FAULTS = [
+    # the plain ICNN
+    ("forward", dict(params=None), _EINVAL),
+    ("forward", dict(logits=None), _EINVAL),
+    ("forward", dict(model=(1777, 2, 1, 0)), _EUNSUPPORTED),
+    ("forward", dict(ws=None), _EINVAL),
+    ("forward", dict(model=(256, 2, 1, 0), ws=None), _EINVAL),   # the layer-by-layer path's own checks
+    ("forward", dict(grid=_BAD_MODE), _EINVAL),
+    ("forward", dict(grid=_NO_COORDS), _EINVAL),
+    ("forward", dict(grid=_NEG_SIDES), _EINVAL),
+    ("forward", dict(n=0), _EINVAL),
+    ("forward", dict(wsb=16), _EWORKSPACE),
+    ("forward", dict(model=(130, 2, 1, 7)), _EINVAL),            # act0
+    ("loss_grad", dict(targets=None), _EINVAL),
+    ("loss_grad", dict(loss=None), _EINVAL),
+    ("loss_grad", dict(loss=(9, 0)), _EINVAL),
+    ("loss_grad", dict(loss=(0, 9)), _EINVAL),
+    ("loss_grad", dict(model=(256, 2, 1, 0), loss=None), _EINVAL),
+    ("loss_grad", dict(model=(1777, 2, 1, 0)), _EUNSUPPORTED),
+    ("loss_grad", dict(wsb=16), _EWORKSPACE),
+    ("fit", dict(opt=None), _EINVAL),
+    ("fit", dict(opt=7), _EINVAL),
+    ("fit", dict(opt_state=None), _EINVAL),
+    ("fit", dict(steps=-1), _EINVAL),
+    ("fit", dict(step0=-1), _EINVAL),
+    ("fit", dict(loss=(2, 0)), _EINVAL),                         # INR_LOSS_EXTERNAL
+    ("fit", dict(model=(256, 2, 1, 0), loss=(2, 0)), _EINVAL),
+    ("fit", dict(model=(1777, 2, 1, 0)), _EUNSUPPORTED),
+    ("fit", dict(grid=_BAD_MODE), _EINVAL),
+    ("fit", dict(wsb=16), _EWORKSPACE),
+    ("joint_step", dict(dseg=None), _EINVAL),
+    ("joint_step", dict(seg=None), _EINVAL),
+    ("joint_step", dict(model=(1777, 2, 1, 0)), _EUNSUPPORTED),
+    ("joint_step", dict(grid=_BAD_MODE), _EINVAL),
+    ("joint_step", dict(wsb=16), _EWORKSPACE),
+    ("joint_step", dict(wsb=16, opt=None), _EWORKSPACE),         # the optimizer is checked after the workspace here
+    # the coupling flow (ConvexDiffeomorphismNet)
+    ("cdn_forward", dict(flow_params=None), _EINVAL),
+    ("cdn_forward", dict(flow=(130, 3, 0)), _EUNSUPPORTED),
+    ("cdn_forward", dict(flow=(130, 6, 5)), _EUNSUPPORTED),
+    ("cdn_forward", dict(model=(130, 3, 1, 0)), _EUNSUPPORTED),  # the flow is 2-D only
+    ("cdn_forward", dict(model=(1777, 2, 1, 0)), _EUNSUPPORTED),
+    ("cdn_forward", dict(ws=None), _EINVAL),
+    ("cdn_forward", dict(grid=_BAD_MODE), _EINVAL),
+    ("cdn_forward", dict(grid=_NO_COORDS), _EINVAL),
+    ("cdn_forward", dict(wsb=16), _EWORKSPACE),
+    ("cdn_loss_grad", dict(flow_grads=None), _EINVAL),
+    ("cdn_loss_grad", dict(loss=None), _EINVAL),
+    ("cdn_loss_grad", dict(flow=(0, 6, 0)), _EUNSUPPORTED),
+    ("cdn_loss_grad", dict(wsb=16), _EWORKSPACE),
+    ("cdn_fit", dict(opt=None), _EINVAL),
+    ("cdn_fit", dict(opt=1), _EINVAL),                           # Adamax: Adam only
+    ("cdn_fit", dict(flow_opt_state=None), _EINVAL),
+    ("cdn_fit", dict(loss=(2, 0)), _EINVAL),
+    ("cdn_fit", dict(model=(130, 3, 1, 0)), _EUNSUPPORTED),
+    ("cdn_fit", dict(grid=_BAD_MODE), _EINVAL),
+    ("cdn_fit", dict(wsb=16), _EWORKSPACE),
+    ("cdn_joint_step", dict(dseg=None), _EINVAL),
+    ("cdn_joint_step", dict(opt=1), _EINVAL),
+    ("cdn_joint_step", dict(opt=None, model=(1777, 2, 1, 0)), _EINVAL),   # the optimizer is checked before the model here
+    ("cdn_joint_step", dict(flow=(130, 3, 0)), _EUNSUPPORTED),
+    ("cdn_joint_step", dict(wsb=16), _EWORKSPACE),
+    # the RealNVP deformation (PathConnectedNet)
+    ("pcn_forward", dict(flow_params=None), _EINVAL),
+    ("pcn_forward", dict(rnvp_flows=0), _EUNSUPPORTED),
+    ("pcn_forward", dict(rnvp_c=3), _EINVAL),                    # the ICNN's C must match the RealNVP's
+    ("pcn_forward", dict(model=(1777, 2, 1, 0)), _EUNSUPPORTED),
+    ("pcn_forward", dict(model=(130, 3, 1, 0), rnvp_c=3, grid=_SEP3_NO_TS), _EINVAL),
+    ("pcn_forward", dict(grid=_NO_COORDS), _EINVAL),
+    ("pcn_forward", dict(ws=None), _EINVAL),
+    ("pcn_forward", dict(wsb=16), _EWORKSPACE),
+    ("pcn_loss_grad", dict(grads=None), _EINVAL),
+    ("pcn_loss_grad", dict(loss=(0, 9)), _EINVAL),
+    ("pcn_loss_grad", dict(rnvp_flows=99), _EUNSUPPORTED),
+    ("pcn_loss_grad", dict(wsb=16), _EWORKSPACE),
+    ("pcn_fit", dict(opt=7), _EINVAL),
+    ("pcn_fit", dict(opt_state=None), _EINVAL),
+    ("pcn_fit", dict(loss=(2, 0)), _EINVAL),
+    ("pcn_fit", dict(rnvp_c=3), _EINVAL),
+    ("pcn_fit", dict(grid=_BAD_MODE), _EINVAL),
+    ("pcn_fit", dict(wsb=16), _EWORKSPACE),
+    ("pcn_joint_step", dict(dseg=None), _EINVAL),
+    ("pcn_joint_step", dict(rnvp_flows=0), _EUNSUPPORTED),
+    ("pcn_joint_step", dict(model=(130, 3, 1, 0), rnvp_c=3, grid=_SEP3_NO_TS), _EINVAL),
+    ("pcn_joint_step", dict(wsb=16), _EWORKSPACE),
+]
+
+
+@pytest.mark.parametrize("entry,fault,code", _FAULTS, ids=[f"{e}-{'-'.join(f)}" for e, f, _ in _FAULTS])
+def test_single_fault_codes(entry, fault, code):
+    """Every ICNN / coupling-flow / RealNVP entry point returns the same code for an input with one fault, checked on the host."""
+    from awesome_amd import _lib
+    lib = _lib.load()
+    assert _ENTRY[entry](lib, _fault_args(**fault)) == code
