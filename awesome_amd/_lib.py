@@ -83,6 +83,11 @@ class InrCnnSegDesc(C.Structure):   # inrfit_cnnseg_*: the convexity benchmark's
                 ("coef", C.c_float * 3), ("channel_group", C.c_int32 * 8)]
 
 
+class InrFcSegDesc(C.Structure):   # inrfit_fcseg_*: the convexity benchmark's FCNet segmentation step
+    _fields_ = [("in_channels", C.c_int32), ("image_channels", C.c_int32), ("width", C.c_int32), ("depth", C.c_int32),
+                ("inversion", C.c_int32), ("g", C.c_float), ("n_rows", C.c_int64), ("data_count", C.c_int64)]
+
+
 class InrStarDesc(C.Structure):
     _fields_ = [("n_hidden", C.c_int32)]
 
@@ -193,6 +198,13 @@ EXPORTS = {
     "inrfit_cnnseg_step": (C.c_int, [C.POINTER(InrCnnSegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
+    "inrfit_fcseg_param_count": (C.c_int64, [C.POINTER(InrFcSegDesc)]),
+    "inrfit_fcseg_workspace_bytes": (C.c_int64, [C.POINTER(InrFcSegDesc)]),
+    "inrfit_fcseg_forward": (C.c_int, [C.POINTER(InrFcSegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_fcseg_step": (C.c_int, [C.POINTER(InrFcSegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
     "inrfit_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -143,7 +143,10 @@ class JointTrainer:
     a supported CNNNet (awesome_amd.cnnseg: 3x3, width 16, depth <= 3, 'rgbxy', one output) with a BCELoss or
     GradientPenaltyLoss(BCELoss, mean) segmentation criterion takes its whole step in HIP as well: inrfit_cnnseg_forward (s and the
     segmentation share, penalties included), inrfit_joint_prior_step, inrfit_cnnseg_step (the network's gradient of both shares into
-    one flat .grad buffer), then the torch optimizer's step.  Any other network or criterion keeps the torch segmentation share."""
+    one flat .grad buffer), then the torch optimizer's step.  In pixel-mode steps (input_mode='pixel', prior_arg_mode 'xy_c_preattached'
+    or 'param_clean_grid') the same holds for a supported FCNet (awesome_amd.fcseg: width 16, depth <= 3, 'rgb' / 'rgbxy' rows of at
+    most 8 channels, one output) with a plain mean BCELoss: inrfit_fcseg_forward, inrfit_joint_prior_step, inrfit_fcseg_step.  Any
+    other network or criterion keeps the torch segmentation share."""
 
     def __init__(self, wrapper: torch.nn.Module, bank: PriorBank, criterion: Callable, optimizer: torch.optim.Optimizer,
                  fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch",
@@ -366,7 +369,10 @@ class JointTrainer:
         g = plan["group"]
         pixel = getattr(w, "input_mode", "image") == "pixel"
         if pixel:       # WrapperModule._forward_pixels: _input (img, n, F) or (n, F), the coordinates are its first two features
-            if w.prior_arg_mode != "xy_c_preattached":
+            # the coordinates: the input's first two features (xy_c_preattached) or the clean-xy rows, the third input (param_clean_grid)
+            if w.prior_arg_mode not in ("xy_c_preattached", "param_clean_grid"):
+                return None
+            if w.prior_arg_mode == "param_clean_grid" and (len(inputs) < 3 or not isinstance(inputs[2], torch.Tensor)):
                 return None
             x0, rest = inputs[0], tuple(inputs[1:])
             if x0.dim() == 2:
@@ -386,14 +392,19 @@ class JointTrainer:
         if form is None or form.pixel != pixel or labels.numel() != (form.data_count or n):
             return None
         kw = {"_input": list(inputs)} if self.forward_additional_loss_args else {}
-        cnn = None if pixel or not self.fused_segmentation else self._cnnseg_plan(form, xi, ai, labels, kw)
+        cnn = None
+        if self.fused_segmentation:
+            cnn = self._fcseg_plan(form, xi, ai, labels) if pixel else self._cnnseg_plan(form, xi, ai, labels, kw)
         self._hand_over("fused")
         self.optimizer.zero_grad()
         if cnn is not None:       # the segmentation share in HIP: s and g (crit + penalties) now, the network's gradient below
-            from . import cnnseg as CS
+            if pixel:                 # an FCNet on pixel rows (awesome_amd.fcseg), else a CNNNet on the image (awesome_amd.cnnseg)
+                from . import fcseg as CS
+            else:
+                from . import cnnseg as CS
             net, desc, image, feat = cnn
             fwd = CS.forward(net, desc, image, feat, labels)
-            seg = fwd.seg.view(1, desc.height, desc.width_px)
+            seg = fwd.seg.view(-1, 1) if pixel else fwd.seg.view(1, desc.height, desc.width_px)
             seg_term = fwd.loss
             self._cnnseg_side_effects(crit)
         else:
@@ -434,7 +445,7 @@ class JointTrainer:
             CS.assign_grads(net, self._cnn_grads)
             self.optimizer.step()
             prior = torch.sigmoid(res.prior_logits)
-            return res.loss[0], torch.cat([seg, prior.view_as(seg)], dim=0)[None]
+            return res.loss[0], torch.cat([seg, prior.view_as(seg)], dim=-1 if pixel else 0)[None]
         if self.check_finite == "step":
             self.raise_if_failed()
         roots, grads = [], []
@@ -487,11 +498,39 @@ class JointTrainer:
                             g=form.g)
         return net, desc, image, feat
 
+    def _fcseg_plan(self, form, xi, ai, labels):
+        """fused_segmentation: (net, InrFcSegDesc, image rows, feature rows) when this pixel-mode step's segmentation share has a HIP
+        form (awesome_amd.fcseg), else None (the torch share)."""
+        from . import fcseg as FS
+        from .measures.losses import AwesomeLoss, AwesomeLossJoint
+        w, crit = self.wrapper, self.criterion
+        net = getattr(w, "segmentation_module", None)
+        if not getattr(w, "use_segmentation_sigmoid", True) or not FS.net_supported(net):
+            return None
+        if not isinstance(crit, (AwesomeLoss, AwesomeLossJoint)) or FS.criterion_form(crit.criterion) is None:
+            return None
+        image, seg_args, _ = w.get_segmentation_module_args(xi, ai, {})
+        if not isinstance(image, torch.Tensor) or image.dim() != 2 or image.dtype != torch.float32 or not image.is_cuda:
+            return None
+        n = image.shape[0]
+        feat = None
+        if net.in_type == "rgbxy":
+            if len(seg_args) < 1 or not isinstance(seg_args[0], torch.Tensor):
+                return None
+            feat = seg_args[0]
+            if feat.dim() != 2 or feat.shape[0] != n or not feat.is_cuda:
+                return None
+        if n < 2 or image.shape[1] + (0 if feat is None else feat.shape[1]) != net.in_chn:
+            return None       # (one row: process_segmentation_output drops the dimension, the torch path's shapes differ)
+        desc = FS.make_desc(net, image.shape[1], n, data_count=form.data_count,
+                            inversion=bool(getattr(w, "use_segmentation_output_inversion", False)), g=form.g)
+        return net, desc, image, feat
+
     @staticmethod
     def _cnnseg_side_effects(crit) -> None:
         """What convexity_seg_share (the class's __call__) leaves behind."""
-        from .measures.losses import AwesomeImageLossJoint
-        if isinstance(crit, AwesomeImageLossJoint):
+        from .measures.losses import AwesomeImageLossJoint, AwesomeLossJoint
+        if isinstance(crit, (AwesomeImageLossJoint, AwesomeLossJoint)):
             crit.criterion.apply_gradient_penalty = True
 
     # -- the step ------------------------------------------------------------------------------------------------------------

@@ -30,6 +30,7 @@
 #include "wide.h"
 #include "star.h"
 #include "cnnseg.h"
+#include "fcseg.h"
 
 #include <type_traits>
 #include <vector>
@@ -2931,6 +2932,142 @@ const char* inrfit_strerror(int code) {
         case INR_ENODEVICE: return "no gfx950 device";
         default: return "unknown error";
     }
+}
+
+}  // extern "C"
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// FCNet segmentation step (csrc/fcseg.h)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct FcWs {
+    int P, blocks;
+    long long count;
+    float *slab, *loss;
+    long long bytes;
+};
+
+static bool fc_desc_ok(const InrFcSegDesc* d) {
+    return d && d->width == FC_WIDTH && d->depth >= 0 && d->depth <= FC_MAX_DEPTH && d->in_channels >= 1 && d->in_channels <= FC_MAX_IN &&
+           d->image_channels >= 0 && d->image_channels <= d->in_channels && d->n_rows >= 1 && d->n_rows < (1LL << 40) &&
+           d->data_count >= 0 && d->data_count <= d->n_rows;
+}
+
+static long long fc_param_count(const InrFcSegDesc* d) {
+    return (long long)fc_b_off(d->in_channels, d->depth, d->depth + 1) + 1;
+}
+
+static FcWs fc_layout(const InrFcSegDesc* d, void* base) {
+    FcWs w{};
+    w.P = (int)fc_param_count(d);
+    const long long chunks = (d->n_rows + FC_BLOCK - 1) / FC_BLOCK;
+    w.blocks = (int)(chunks < FC_MAX_BLOCKS ? chunks : FC_MAX_BLOCKS);
+    w.count = d->data_count > 0 ? d->data_count : d->n_rows;
+    w.slab = (float*)base;
+    const long long slab_bytes = ((long long)w.blocks * (w.P + 1) * 4 + 255) / 256 * 256;
+    w.loss = (float*)((char*)base + slab_bytes);
+    w.bytes = slab_bytes + 256;
+    return w;
+}
+
+static int fc_check(const InrFcSegDesc* d, const float* const* wts, const float* const* bs, const float* image, const float* feat,
+                    void* ws, long long ws_bytes, FcWs* w) {
+    if (!d || !wts || !bs || !ws) return INR_EINVAL;
+    if (!fc_desc_ok(d)) return INR_EUNSUPPORTED;
+    if ((d->image_channels > 0 && !image) || (d->image_channels < d->in_channels && !feat)) return INR_EINVAL;
+    for (int l = 0; l < d->depth + 2; ++l)
+        if (!wts[l] || !bs[l]) return INR_EINVAL;
+    *w = fc_layout(d, ws);
+    if (ws_bytes < w->bytes) return INR_EWORKSPACE;
+    return INR_OK;
+}
+
+template <bool BWD>
+static void fc_launch_rows(int depth, int blocks, hipStream_t s, const FcArgs& a) {
+    const dim3 grid(blocks), block(FC_BLOCK);
+    switch (depth) {
+        case 0: hipLaunchKernelGGL((fc_rows_kernel<0, BWD>), grid, block, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((fc_rows_kernel<1, BWD>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((fc_rows_kernel<2, BWD>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((fc_rows_kernel<3, BWD>), grid, block, 0, s, a); break;
+    }
+}
+
+static FcArgs fc_args(const FcWs& w, const InrFcSegDesc* d, const float* const* wts, const float* const* bs, const float* image,
+                      const float* feat, const float* target, const float* dseg, float* logits, float* seg) {
+    FcArgs a{};
+    for (int l = 0; l < d->depth + 2; ++l) {
+        a.w[l] = wts[l];
+        a.b[l] = bs[l];
+    }
+    a.image = image;
+    a.feat = feat;
+    a.target = target;
+    a.dseg = dseg;
+    a.logits = logits;
+    a.seg = seg;
+    a.slab = w.slab;
+    a.n = d->n_rows;
+    a.count = w.count;
+    a.F = d->in_channels;
+    a.ic = d->image_channels;
+    a.inversion = d->inversion;
+    a.P = w.P;
+    a.seed_scale = (float)((double)d->g / (double)w.count);
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t inrfit_fcseg_param_count(const InrFcSegDesc* desc) {
+    InrFcSegDesc d;
+    if (!desc) return -1;
+    d = *desc;
+    if (d.n_rows < 1) d.n_rows = 1;       // (the count does not depend on the rows)
+    if (d.data_count < 0 || d.data_count > d.n_rows) d.data_count = 0;
+    return fc_desc_ok(&d) ? fc_param_count(&d) : -1;
+}
+
+int64_t inrfit_fcseg_workspace_bytes(const InrFcSegDesc* desc) { return fc_desc_ok(desc) ? fc_layout(desc, nullptr).bytes : -1; }
+
+int inrfit_fcseg_forward(const InrFcSegDesc* desc, const float* const* weights, const float* const* biases, const float* image_rows,
+                         const float* feature_rows, const float* target, float* logits, float* seg, float* loss_out, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+    FcWs w;
+    int rc = fc_check(desc, weights, biases, image_rows, feature_rows, workspace, workspace_bytes, &w);
+    if (rc) return rc;
+    if (target && !loss_out) return INR_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    FcArgs a = fc_args(w, desc, weights, biases, image_rows, feature_rows, target, nullptr, logits, seg);
+    a.P = 0;            // forward: the slab holds the BCE sums only
+    a.stride = 1;
+    fc_launch_rows<false>(desc->depth, w.blocks, s, a);
+    if (target) {
+        FcReduceArgs r{w.slab, w.blocks, 1, 0, desc->g, (float)w.count, nullptr, nullptr, loss_out, w.loss};
+        hipLaunchKernelGGL(fc_reduce_kernel, dim3(1), dim3(FC_REDUCE_BLOCK), 0, s, r);
+    }
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+int inrfit_fcseg_step(const InrFcSegDesc* desc, const float* const* weights, const float* const* biases, const float* image_rows,
+                      const float* feature_rows, const float* target, const float* dseg, int reuse_forward, float* logits, float* seg,
+                      float* loss_out, float* grads, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    FcWs w;
+    int rc = fc_check(desc, weights, biases, image_rows, feature_rows, workspace, workspace_bytes, &w);
+    if (rc) return rc;
+    if (!target || !grads || !status) return INR_EINVAL;
+    (void)reuse_forward;   // the rows' forward is part of the one step launch either way (include/inrfit.h)
+    hipStream_t s = (hipStream_t)stream;
+    FcArgs a = fc_args(w, desc, weights, biases, image_rows, feature_rows, target, dseg, logits, seg);
+    a.stride = w.P + 1;
+    fc_launch_rows<true>(desc->depth, w.blocks, s, a);
+    FcReduceArgs r{w.slab, w.blocks, w.P + 1, w.P, desc->g, (float)w.count, grads, status, loss_out, w.loss};
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3(1), dim3(FC_REDUCE_BLOCK), 0, s, r);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
 }  // extern "C"

@@ -152,6 +152,81 @@ class SyntheticPriorDataset(PriorDataset):
         return (image, feat, xy), target
 
 
+class SyntheticPixelDataset(SyntheticPriorDataset):
+    """The synthetic inputs for the pixel mode of the convexity configs (`dataset_args.dimension: 2d`, AwesomeDataset
+    .get_dimension_based_data, awesome/dataset/awesome_dataset.py:198-217, 296-326).  Indexing gives SyntheticPriorDataset's image
+    items (what the per-image prior fits read); `pixel_item(i)` is the training item of the joint epochs:
+
+        ((rgb rows (n, 3), feature rows (n, 2), clean-xy rows (n, 2)), target (n_scr, 1))
+
+    in the reference's order: the scribbled pixels first (row-major, as a boolean mask selects them), then ceil(n_scr (1 / p - 1))
+    distinct pixels drawn with the seed `split_seed` (also row-major), p = scribble_percentage.  The image is synthetic RGB: one
+    colour per class plus seeded noise; the scribbles are `n_scribble` seeded pixels labelled with the clean mask in the unaries'
+    convention (object = 0, background = 1); the features are the pixel's coordinates (the 'rgbxy' input of the FCNet configs)."""
+
+    dimension = "2d"
+
+    def __init__(self, n_images: int = 1, size: int = 256, kind: str = "blob", seed0: int = 0, prior_model_type=None,
+                 prior_model_args=None, scribble_percentage: float = 0.8, n_scribble: int = 0, split_seed: int = 42,
+                 dimension: str = "2d", **kwargs):
+        kwargs.pop("features", None)
+        super().__init__(n_images=n_images, size=size, kind=kind, seed0=seed0, prior_model_type=prior_model_type,
+                         prior_model_args=prior_model_args, features="xy", **kwargs)
+        if dimension != "2d":
+            raise ValueError(f"SyntheticPixelDataset is the 2d (pixel) form of the dataset; dimension {dimension!r} is SyntheticPriorDataset")
+        if not 0.0 < float(scribble_percentage) <= 1.0:
+            raise ValueError("scribble_percentage must be in (0, 1]")
+        self.scribble_percentage, self.split_seed = float(scribble_percentage), int(split_seed)
+        n = int(n_scribble) if n_scribble else max(4, (self.size * self.size) // 8)
+        n = min(n, self.size * self.size)
+        # the losses recover the scribble count as floor(total * p): keep a count for which that round trip is exact
+        while n > 1 and int((n + self._n_random(n)) * self.scribble_percentage // 1) != n:
+            n -= 1
+        self.n_scribble = n
+
+    def _n_random(self, n_scr: int) -> int:
+        if self.scribble_percentage >= 1.0:
+            return 0
+        return int(np.ceil(n_scr * (1.0 / self.scribble_percentage) - n_scr))
+
+    def rgb(self, i: int) -> torch.Tensor:
+        """(S * S, 3) float32 in [0, 1]."""
+        rng = np.random.RandomState(20_000 + self._inner.seed0 + int(i))
+        obj = (self._inner.ground_truth(int(i)) <= 0.5).numpy().reshape(-1, 1)
+        colour = np.where(obj, np.array([[0.8, 0.3, 0.2]]), np.array([[0.2, 0.4, 0.7]]))
+        return torch.from_numpy(np.clip(colour + rng.normal(scale=0.1, size=colour.shape), 0.0, 1.0).astype(np.float32))
+
+    def pixel_rows(self, i: int):
+        """Every pixel of image i as rows: (rgb (S*S, 3), features (S*S, 2), clean xy (S*S, 2)) - the evaluation input."""
+        xy = self._xy.reshape(2, -1).t().contiguous()
+        return self.rgb(i), xy.clone(), xy
+
+    def pixel_item(self, i: int):
+        rgb, feat, xy = self.pixel_rows(i)
+        n_pix = rgb.shape[0]
+        rng = np.random.RandomState(30_000 + self._inner.seed0 + int(i))
+        scr = np.zeros(n_pix, dtype=bool)
+        scr[rng.choice(n_pix, size=self.n_scribble, replace=False)] = True
+        target = (self._inner.ground_truth(int(i)) > 0.5).float().reshape(-1)[torch.from_numpy(scr)][:, None]
+        sel = [np.flatnonzero(scr)]
+        n_rand = self._n_random(self.n_scribble)
+        if n_rand > 0:
+            if n_rand > n_pix:
+                raise ValueError("Could not draw enough random pixels")
+            rng = np.random.RandomState(self.split_seed)
+            mask = np.zeros(n_pix, dtype=bool)
+            for _ in range(1000):            # randint may draw a pixel twice: draw until enough distinct ones are marked
+                need = n_rand - int(mask.sum())
+                if need <= 0:
+                    break
+                mask[rng.randint(0, n_pix, size=need)] = True
+            if int(mask.sum()) < n_rand:
+                raise ValueError("Could not draw enough random pixels after 1000 iterations.")
+            sel.append(np.flatnonzero(mask))
+        idx = torch.from_numpy(np.concatenate(sel))
+        return (rgb[idx], feat[idx], xy[idx]), target
+
+
 class SyntheticUnariesDataset:
     """Minimal stand-in for the reference's prior datasets on the hot path: item i is `(grid_desc, unaries_i)` where
     unaries follow the reference convention (fg = 0).  `kind`: 'disc' (C1), 'blob' (C2/C3, seed = index + seed0) or

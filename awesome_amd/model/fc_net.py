@@ -4,7 +4,11 @@ Reference: FCNet (awesome/model/fc_net.py:10-59) = Linear(in_chn, width), ReLU, 
 out_chn), fed by concat_input(in_type, image, grid) (awesome/model/cnn_net.py).  With in_type='xy' its input is the coordinate
 grid alone and it is the ICNN of awesome_amd/csrc without skip connections and without the convexity clamp: it runs on the same
 HIP kernels with the skip weights held at zero (`InrOptDesc.freeze_skips`) and `clamp = 0`.  Same `model.*` state_dict keys and
-layer creation order as the reference (a seeded construction yields the reference's initial weights)."""
+layer creation order as the reference (a seeded construction yields the reference's initial weights).
+
+With in_type='rgb' / 'rgbxy' it is the segmentation network of the convexity benchmark's FCNet configs (`input: rgbxy`, width 16, depth
+3) on pixel rows: `forward(image, grid)` is plain torch on concat_input, as CNNNet.forward is, and the fused joint step runs the
+supported shapes through the HIP step of awesome_amd.fcseg instead."""
 from __future__ import annotations
 
 from typing import Dict, List
@@ -13,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import icnn as K
+from .cnn_net import concat_input
 from .convex_net import _IcnnFunction, _IcnnModule
 from .pretrainable_module import PriorFitMixin
 
@@ -46,21 +51,34 @@ class FCNet(nn.Module, PriorFitMixin):
     def enforce_convexity(self) -> None:   # nothing is constrained in the "no prior" network
         return None
 
-    def __init__(self, in_chn: int = 2, out_chn: int = 1, width: int = 130, depth: int = 1, in_type: str = "xy", **kwargs):
+    def __init__(self, in_chn: int = 2, out_chn: int = 1, width: int = 130, depth: int = 1, in_type: str = "xy", input: str = None,
+                 **kwargs):
         super().__init__()
-        if in_type != "xy":
-            raise ValueError("the HIP path implements the coordinate network (in_type='xy'); image inputs belong to the "
-                             "segmentation backbones, which are out of scope (SURVEY.md §8)")
+        if input is not None:          # the config's name for in_type
+            in_type = input
+        if in_type not in ("xy", "rgb", "rgbxy"):
+            raise ValueError(f"in_type must be one of: rgb, xy, rgbxy but was: {in_type}")
         if out_chn != 1:
             raise ValueError("scalar output only (out_chn=1)")
-        self.in_chn, self.out_chn, self.in_type, self.depth = in_chn, out_chn, in_type, depth
-        self.spec = K.IcnnSpec(width, in_chn, depth)
-        self.model = nn.Sequential(nn.Linear(in_chn, width), nn.ReLU(), *[linear_relu(width) for _ in range(depth)],
-                                   nn.Linear(width, out_chn))
+        self.in_chn, self.out_chn, self.in_type, self.depth, self.width = in_chn, out_chn, in_type, depth, width
+        if in_type == "xy":            # the coordinate network on the ICNN kernels
+            self.spec = K.IcnnSpec(width, in_chn, depth)
+        else:                          # a segmentation network on image rows: no coordinate-fit engine
+            self.fit_options = None
+        if in_type == "xy":            # (layers drawn in module order: the seeded initial weights this form has always had here)
+            self.model = nn.Sequential(nn.Linear(in_chn, width), nn.ReLU(), *[linear_relu(width) for _ in range(depth)],
+                                       nn.Linear(width, out_chn))
+        else:                          # the reference's order: the hidden blocks are created first (fc_net.py:48-55)
+            linear_blocks = [linear_relu(width) for _ in range(depth)]
+            self.model = nn.Sequential(nn.Linear(in_chn, width), nn.ReLU(), *linear_blocks, nn.Linear(width, out_chn))
 
     # ---- flat views: the ICNN layout with zero skip weights ---------------------------------------------------------------
     def _linears(self) -> List[nn.Linear]:
         return [self.model[0]] + [self.model[2 + k][0] for k in range(self.depth)] + [self.model[2 + self.depth]]
+
+    def linear_layers(self) -> List[nn.Linear]:
+        """The linear layers in order (layer 0 .. depth + 1)."""
+        return self._linears()
 
     def flat_parameters(self) -> torch.Tensor:
         lin = self._linears()
@@ -85,7 +103,10 @@ class FCNet(nn.Module, PriorFitMixin):
         self.load_state_dict({k: v.to(self.model[0].weight.device) for k, v in self.unpack_flat(flat).items()})
 
     def forward(self, image: torch.Tensor, grid: torch.Tensor = None, *args, **kwargs) -> torch.Tensor:
-        """(image, grid) like the reference; only the grid is used (in_type='xy'): (B,C,H,W) -> (B,1,H,W) or (N,C) -> (N,1)."""
+        """(image, grid) like the reference.  in_type='xy': only the grid is used, (B,C,H,W) -> (B,1,H,W) or (N,C) -> (N,1) on the
+        ICNN kernels.  'rgb' / 'rgbxy': the reference's forward, model(concat_input(...)) on rows (..., C) -> (..., 1), plain torch."""
+        if self.in_type != "xy":
+            return self.model(concat_input(self.in_type, image, grid))
         x = grid if grid is not None else image
         if not x.is_cuda:
             raise RuntimeError("awesome_amd modules run on the MI355X only (no CPU fallback); move module and input to cuda")

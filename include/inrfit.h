@@ -544,6 +544,43 @@ int inrfit_cnnseg_step(const InrCnnSegDesc* desc, const float* const* weights, c
                        const float* features, const float* target, const float* dseg, int reuse_forward, float* logits, float* seg,
                        float* loss_out, float* grads, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the convexity benchmark's fully connected segmentation network (awesome/model/fc_net.py FCNet, csrc/fcseg.h) -------------------
+ * Linear(in_channels, width), ReLU, depth x [Linear(width, width), ReLU], Linear(width, 1) on n_rows pixel rows, fp32.  A row's input is
+ * the concatenation [image_rows[r][0 .. image_channels) | feature_rows[r][0 .. in_channels - image_channels)], read from the two
+ * row-major tensors as they are.  s = sigmoid(f), or 1 - sigmoid(f) with `inversion`.  The share of the joint loss it is trained with
+ * (a plain mean BCELoss on the first data_count rows, log clamped at -100, times g):
+ *     loss = g mean_{r < data_count} BCE(s_r, target_r)                    (data_count = 0: all n_rows)
+ * Supported: width 16, 0 <= depth <= 3, 1 <= in_channels <= 8, any n_rows >= 1 (INR_EUNSUPPORTED otherwise).
+ * weights / biases: host arrays of depth + 2 device pointers, the layers' torch tensors ([out][in] and [out]). */
+typedef struct InrFcSegDesc {
+    int32_t in_channels;
+    int32_t image_channels;
+    int32_t width;
+    int32_t depth;
+    int32_t inversion;
+    float g;
+    int64_t n_rows;
+    int64_t data_count;
+} InrFcSegDesc;
+
+/* gradient layout: the module's parameters() order, w_0 | b_0 | w_1 | b_1 | ...; the count does not depend on n_rows */
+int64_t inrfit_fcseg_param_count(const InrFcSegDesc* desc);
+int64_t inrfit_fcseg_workspace_bytes(const InrFcSegDesc* desc);
+/* Forward: logits [n_rows] = f, seg [n_rows] = s (either may be null).  With `target` [data_count or n_rows] (else null) also the loss
+ * above into loss_out[0] (one device float, the seg_term inrfit_joint_prior_step can take).  With target = null this is the evaluation
+ * forward over a whole image's rows: one launch. */
+int inrfit_fcseg_forward(const InrFcSegDesc* desc, const float* const* weights, const float* const* biases, const float* image_rows,
+                         const float* feature_rows, const float* target, float* logits, float* seg, float* loss_out, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+/* One step, two launches: grads [param_count] = d (loss + sum_r dseg[r] s[r]) / d parameters, dseg [n_rows] or null; loss_out, logits,
+ * seg as above (each may be null).  The rows' forward is recomputed inside the step's one launch over the rows (its activations never
+ * leave registers: that is cheaper than reading them back), so reuse_forward changes nothing but documents, as for
+ * inrfit_cnnseg_step, that inrfit_fcseg_forward ran with the same arguments and logits / seg are not needed again.  A non-finite loss
+ * or gradient zeroes grads and sets *status = 1 (else 0).  Reductions are fixed-order: results are bit-reproducible.  No host sync. */
+int inrfit_fcseg_step(const InrFcSegDesc* desc, const float* const* weights, const float* const* biases, const float* image_rows,
+                      const float* feature_rows, const float* target, const float* dseg, int reuse_forward, float* logits, float* seg,
+                      float* loss_out, float* grads, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 const char* inrfit_strerror(int code);
 
 #pragma GCC visibility pop

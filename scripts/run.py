@@ -141,7 +141,16 @@ def main(cfg):
                              num_epochs, criterion, opt_type, opt_args, out_dir)
 
     # ---- per-image priors through the reference's interface: dataset with a PriorCache -> WrapperModule -> agent._pretrain ----
-    ds = SyntheticPriorDataset(prior_model_type=model_type, prior_model_args=model_args, **dataset_args)
+    # dataset_args.dimension: 2d - the pixel mode of the convexity configs: the joint epochs train on pixel rows (scribbles first, then
+    # random pixels), the per-image prior fits read the same dataset's image items
+    pixel_mode = dataset_args.get("dimension", "3d") == "2d"
+    if pixel_mode:
+        from awesome_amd.dataset import SyntheticPixelDataset
+        dataset_args.setdefault("scribble_percentage", float(cfg.get("scribble_percentage", 0.8) or 0.8))
+        ds = SyntheticPixelDataset(prior_model_type=model_type, prior_model_args=model_args, **dataset_args)
+    else:
+        dataset_args.pop("dimension", None)
+        ds = SyntheticPriorDataset(prior_model_type=model_type, prior_model_args=model_args, **dataset_args)
     ds.__prior_cache__.key_seed = seed          # image k starts from the same parameters on 1 rank and on 8
     mine = list(parallel.shard_range(len(ds), rank, world))
     wrapper = WrapperModule(ForwardModule(), model_type(**model_args), use_segmentation_output_inversion=True).to(device)
@@ -289,12 +298,18 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
                              "they are); pass --segmentation-model-type with an importable torch module type")
         seg_type = dynamic_import(seg_name) if isinstance(seg_name, str) else seg_name
         seg_args = dict(cfg.get("segmentation_model_args") or {})
-        from awesome_amd.model import CNNNet
-        if isinstance(seg_type, type) and issubclass(seg_type, CNNNet):
-            seg_args = segmentation_model_args(cfg, seg_args, ds[mine[0]])
+        from awesome_amd.model import CNNNet, FCNet
+        pixel_mode = getattr(ds, "dimension", "3d") == "2d"
+        if isinstance(seg_type, type) and issubclass(seg_type, (CNNNet, FCNet)):
+            first = ((mine[0], None), ds.pixel_item(mine[0])) if pixel_mode else ds[mine[0]]
+            seg_args = segmentation_model_args(cfg, seg_args, first)
         seg = seg_type(**seg_args).to(device)
         prior = wrapper.prior_module
-        jw = WrapperModule(seg, prior, use_segmentation_output_inversion=True).to(device)
+        if pixel_mode:       # awesome_runner.py:147-162: the 2d configs' wrapper reads pixel rows, the prior the clean coordinates
+            jw = WrapperModule(seg, prior, use_segmentation_output_inversion=True, input_mode="pixel",
+                               prior_arg_mode="param_clean_grid").to(device)
+        else:
+            jw = WrapperModule(seg, prior, use_segmentation_output_inversion=True).to(device)
         bank = PriorBank(lambda: model_type(**model_args).to(device), n_images=len(mine), device=device, keys=mine)
         cache0 = ds.__prior_cache__
         for k in mine:
@@ -321,7 +336,10 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
                         group["lr"] = group["lr"] * float(cfg.get("reduce_lr_in_extra_penalty_hook_factor", 0.05))
             acc = torch.zeros((), device=device)
             for k in mine:
-                (_, _), ((image, feat, xy), target) = ds[k]
+                if pixel_mode:
+                    (image, feat, xy), target = ds.pixel_item(k)
+                else:
+                    (_, _), ((image, feat, xy), target) = ds[k]
                 loss, _ = trainer.perform_step(k, (image[None].to(device), feat[None].to(device), xy[None].to(device)),
                                                target[None].to(device))
                 fused_steps[k] = fused_steps.get(k, 0) + (trainer._path == "fused")
@@ -335,13 +353,16 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
 
 
 def segmentation_model_args(cfg, args, item):
-    """AwesomeRunner.get_sisbosi_segmentation_model_args (awesome/run/awesome_runner.py:43-73) on this build's item format
-    ((image, features, xy_clean), target): `input` becomes `in_type`; in_chn = image channels (3 for RGB) + the channel count of the
+    """AwesomeRunner.get_sisbosi_segmentation_model_args (awesome/run/awesome_runner.py:43-73) on this build's item formats
+    ((image, features, xy_clean), target), planar images or pixel rows, for CNNNet and FCNet: `input` becomes `in_type`; in_chn = image channels (3 for RGB) + the channel count of the
     item's second input for 'rgbxy', one of the two for 'rgb' / 'xy'; out_chn = 1 for binary classification."""
     args = dict(args)
     mode = args.pop("input", "rgbxy")
     (_, _), ((image, feat, _), _) = item
-    c_img, c_feat = int(image.shape[-3]) if image.dim() >= 3 else 1, int(feat.shape[-3]) if feat.dim() >= 3 else 1
+    if image.dim() == 2:      # a pixel item: rows (n, channels)
+        c_img, c_feat = int(image.shape[-1]), int(feat.shape[-1])
+    else:
+        c_img, c_feat = int(image.shape[-3]) if image.dim() >= 3 else 1, int(feat.shape[-3]) if feat.dim() >= 3 else 1
     if "in_chn" not in args:
         chn = {"rgb": c_img, "rgbxy": c_img + c_feat, "xy": c_feat}
         if mode not in chn:
