@@ -1,0 +1,129 @@
+"""What awesome_amd.cnnseg and awesome_amd.fcseg share: the two segmentation networks differ in their layer list, their element
+counts and their entry-point names (inrfit_cnnseg_* / inrfit_fcseg_*, include/inrfit.h), not in how the host drives them."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Callable, Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib as L
+from .icnn import _check_dev, _stream_ptr
+
+
+def _plain_bce(c) -> bool:
+    return type(c) is torch.nn.BCELoss and c.weight is None and c.reduction == "mean"
+
+
+def layer_ptrs(layers):
+    w = (C.c_void_p * len(layers))(*[m.weight.data_ptr() for m in layers])
+    b = (C.c_void_p * len(layers))(*[m.bias.data_ptr() for m in layers])
+    return C.cast(w, C.c_void_p), C.cast(b, C.c_void_p), (w, b)       # (the arrays stay alive with the caller's reference)
+
+
+def assign_grads(net, grads: Tensor) -> None:
+    """Every parameter's .grad becomes its view of the flat gradient buffer (parameters() order)."""
+    off = 0
+    for p in net.parameters():
+        k = p.numel()
+        p.grad = grads[off:off + k].view_as(p)
+        off += k
+    assert off == grads.numel()
+
+
+@dataclass
+class SegResult:
+    logits: Optional[Tensor]   # [n] f
+    seg: Optional[Tensor]      # [n] s
+    loss: Optional[Tensor]     # [1] g (crit + penalties); None: fcseg's forward without a target
+    grads: Optional[Tensor] = None    # [P] in parameters() order
+    status: Optional[Tensor] = None   # [1] int32: 1 = non-finite loss or gradient (grads zeroed)
+
+
+def _ptr(t: Optional[Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+_ws_cache = {}
+
+
+@dataclass(frozen=True)
+class SegDriver:
+    """The host side of one inrfit_<name>_{param_count, workspace_bytes, forward, step} family."""
+    name: str                  # 'cnnseg' / 'fcseg'
+    net_name: str              # for messages
+    layers: Callable           # net -> its conv / linear layers, first to last
+    inputs: Callable           # (desc, image, features) -> the two checked tensors (None: the desc has no such channels)
+    n_points: Callable         # desc -> elements of f and s
+    n_target: Callable         # desc -> elements of the target
+    ws_key: Callable           # desc -> what the workspace size depends on
+    loss_without_target: bool  # whether forward(target=None) still hands the kernel a loss cell
+
+    def _entry(self, op: str):
+        return getattr(L.load(), f"inrfit_{self.name}_{op}")
+
+    def param_count(self, desc) -> int:
+        n = self._entry("param_count")(C.byref(desc))
+        if n < 0:
+            raise L.InrfitError(f"inrfit_{self.name}_param_count: unsupported {self.net_name} shape")
+        return int(n)
+
+    def workspace(self, desc, dev) -> Tensor:
+        """One workspace per (shape, device).  Unlike joint._workspace this cache must NOT reallocate under L.POISON:
+        step(reuse_forward=True) reads what forward left in the workspace, a fresh NaN-filled one would lose it."""
+        key = (self.name, self.ws_key(desc), str(dev))
+        ws = _ws_cache.get(key)
+        if ws is None:
+            nbytes = int(self._entry("workspace_bytes")(C.byref(desc)))
+            if nbytes < 0:
+                raise L.InrfitError(f"inrfit_{self.name}_workspace_bytes: unsupported {self.net_name} shape")
+            ws = _ws_cache[key] = L.scratch(nbytes // 4 + 64, dtype=torch.float32, device=dev)
+        return ws
+
+    def _checked(self, desc, image, features, target, dseg=None):
+        image, features = self.inputs(desc, image, features)
+        if target is not None:
+            target = _check_dev(target.detach().float(), "target")
+            assert target.numel() == self.n_target(desc), (tuple(target.shape), self.n_target(desc))
+        if dseg is not None:
+            dseg = _check_dev(dseg.detach(), "dseg")
+            assert dseg.numel() == self.n_points(desc)
+        return image, features, target, dseg
+
+    def forward(self, net, desc, image, features, target=None) -> SegResult:
+        dev = (image if image is not None else features).device
+        n = self.n_points(desc)
+        image, features, target, _ = self._checked(desc, image, features, target)
+        w, b, _keep = layer_ptrs(self.layers(net))
+        logits = L.scratch(n, dtype=torch.float32, device=dev)
+        seg = L.scratch(n, dtype=torch.float32, device=dev)
+        loss = L.scratch(1, dtype=torch.float32, device=dev) if target is not None or self.loss_without_target else None
+        ws = self.workspace(desc, dev)
+        rc = self._entry("forward")(C.byref(desc), w, b, _ptr(image), _ptr(features), _ptr(target), logits.data_ptr(), seg.data_ptr(),
+                                    _ptr(loss), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
+        L.check(rc, f"inrfit_{self.name}_forward")
+        return SegResult(logits, seg, loss)
+
+    def step(self, net, desc, image, features, target, dseg=None, reuse_forward=False, grads=None) -> SegResult:
+        dev = (image if image is not None else features).device
+        n = self.n_points(desc)
+        image, features, target, dseg = self._checked(desc, image, features, target, dseg)
+        P = self.param_count(desc)
+        if grads is None:
+            grads = L.scratch(P, dtype=torch.float32, device=dev)
+        assert grads.numel() == P and grads.is_contiguous() and grads.dtype == torch.float32
+        w, b, _keep = layer_ptrs(self.layers(net))
+        logits = seg = None
+        if not reuse_forward:
+            logits = L.scratch(n, dtype=torch.float32, device=dev)
+            seg = L.scratch(n, dtype=torch.float32, device=dev)
+        loss = L.scratch(1, dtype=torch.float32, device=dev)
+        status = L.scratch(1, dtype=torch.int32, device=dev)      # (always written)
+        ws = self.workspace(desc, dev)
+        rc = self._entry("step")(C.byref(desc), w, b, _ptr(image), _ptr(features), target.data_ptr(), _ptr(dseg),
+                                 int(bool(reuse_forward)), _ptr(logits), _ptr(seg), loss.data_ptr(), grads.data_ptr(),
+                                 status.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
+        L.check(rc, f"inrfit_{self.name}_step")
+        return SegResult(logits, seg, loss, grads, status)

@@ -104,49 +104,146 @@ def _loss_takes_input(loss: Callable) -> bool:
     return False
 
 
+def _normalise_item(inputs: Sequence[Any], input_mode: str = "image", prior_arg_mode: Optional[str] = None):
+    """One training item at batch size 1, as the fused routes take it: (xi, ai, n, pixel), or None for what they refuse.
+    image: xi (1, C, H, W), every tensor of ai 4-d, n = H W.  pixel (WrapperModule._forward_pixels): `inputs[0]` is (1, n, F) or
+    (n, F) and xi its (n, F) rows, ai the other inputs' rows; the prior's coordinates are xi's first two features
+    ('xy_c_preattached') or the clean-xy rows, the third input ('param_clean_grid')."""
+    if input_mode == "pixel":
+        if prior_arg_mode not in ("xy_c_preattached", "param_clean_grid"):
+            return None
+        if prior_arg_mode == "param_clean_grid" and (len(inputs) < 3 or not isinstance(inputs[2], torch.Tensor)):
+            return None
+        x0, rest = inputs[0], tuple(inputs[1:])
+        if x0.dim() == 2:
+            x0 = x0[None]
+            rest = tuple(a[None] if isinstance(a, torch.Tensor) and a.dim() == 2 else a for a in rest)
+        if x0.dim() != 3 or x0.shape[0] != 1:
+            return None
+        xi, ai = x0[0], tuple(a[0] if isinstance(a, torch.Tensor) else a for a in rest)
+        return xi, ai, xi.shape[0], True
+    xi = inputs[0] if inputs[0].dim() == 4 else inputs[0][None]
+    if xi.shape[0] != 1:
+        return None
+    ai = tuple(a if not isinstance(a, torch.Tensor) or a.dim() == 4 else a[None] for a in inputs[1:])
+    return xi, ai, xi.shape[-2] * xi.shape[-1], False
+
+
+def _prior_grid(prior_args, pixel: bool):
+    """The prior's coordinates (WrapperModule.get_prior_args) as the kernels' explicit grid, (2, n) float32."""
+    from . import icnn as K
+    coords = prior_args[0]
+    if pixel:
+        coords = coords.reshape(-1, coords.shape[-1]).t()                  # (n, 2) -> (2, n)
+    else:
+        coords = coords[0] if coords.dim() == 4 else coords
+        coords = coords.reshape(coords.shape[0], -1)                       # (2, H, W) -> (2, H W)
+    return K.Grid.explicit(coords.to(torch.float32).contiguous())
+
+
+# The segmentation share of the convexity route, g crit(seg, t): two implementations of the same two operations.
+#   forward() -> (seg, seg_term)           seg: image (1, H, W) / pixel (n, 1); seg_term: the share's device scalar
+#   backward(seg, seg_term, dseg, check)   the gradient of seg_term + sum(dseg * seg) into the network's .grad.  `check(status)` is
+#                                          JointTrainer._check_finite: called once, with the share's status word (None: it has
+#                                          none), before anything reaches .grad
+class _TorchSegShare:
+    """In torch, for any network and criterion: the class's own view of the segmentation channel (convexity_seg_share), one backward
+    through the network for both shares."""
+
+    def __init__(self, trainer: "JointTrainer", form, xi, ai, labels, kw):
+        self.trainer, self.form, self.xi, self.ai, self.labels, self.kw = trainer, form, xi, ai, labels, kw
+
+    def forward(self):
+        from .measures.losses import convexity_seg_share
+        seg = self.trainer.wrapper.segmentation_output(self.xi, self.ai)     # autograd attached
+        return seg, convexity_seg_share(self.trainer.criterion, self.form, seg[None], self.labels, **self.kw)
+
+    def backward(self, seg, seg_term, dseg, check) -> None:
+        check(None)
+        roots, grads = [], []
+        if seg_term.requires_grad:
+            roots.append(seg_term)
+            grads.append(None)
+        if dseg is not None and seg.requires_grad:
+            roots.append(seg)
+            grads.append(dseg.view_as(seg))
+        if roots:
+            torch.autograd.backward(roots, grads)
+
+
+class _HipSegShare:
+    """In HIP (fused_segmentation), `CS` = awesome_amd.cnnseg for a CNNNet on the image or awesome_amd.fcseg for an FCNet on pixel
+    rows: CS.forward (s and the share, penalties included) now, CS.step(reuse_forward=True) for the network's gradient of both shares
+    into the trainer's flat buffer after the prior's step.  `plan`: what JointTrainer._cnnseg_plan / _fcseg_plan returned."""
+
+    def __init__(self, trainer: "JointTrainer", CS, plan, labels, pixel: bool):
+        self.trainer, self.CS, self.labels = trainer, CS, labels
+        self.net, self.desc, self.image, self.feat = plan
+        self.seg_shape = (-1, 1) if pixel else (1, self.desc.height, self.desc.width_px)
+
+    def forward(self):
+        from .measures.losses import AwesomeImageLossJoint, AwesomeLossJoint
+        fwd = self.CS.forward(self.net, self.desc, self.image, self.feat, self.labels)
+        crit = self.trainer.criterion
+        if isinstance(crit, (AwesomeImageLossJoint, AwesomeLossJoint)):       # what convexity_seg_share (the class's __call__)
+            crit.criterion.apply_gradient_penalty = True                      # leaves behind
+        return fwd.seg.view(self.seg_shape), fwd.loss
+
+    def backward(self, seg, seg_term, dseg, check) -> None:
+        CS = self.CS
+        grads = self.trainer._seg_grad_buffer(CS.param_count(self.desc), self.image.device)
+        out = CS.step(self.net, self.desc, self.image, self.feat, self.labels, dseg=dseg, reuse_forward=True, grads=grads)
+        # a non-finite loss or gradient: the network's gradient is zero (the optimizer still steps its moments, as torch would
+        # on a zero gradient) and the failure is latched like the prior's
+        check(out.status)
+        CS.assign_grads(self.net, grads)
+
+
 class JointTrainer:
     """One optimisation step of the joint segmentation + prior training (TorchAgent._perform_step, :428-551) on device-resident
     priors.  `wrapper` is a WrapperModule(segmentation_module, prior_module); `bank` holds one parameter row per image of the
     prior module; `criterion(output, labels)` e.g. FBMSJointLoss.  `optimizer`: ONE torch optimizer over the segmentation module's
     parameters and the prior module's Parameter objects, as the reference builds it (torch_agent.py:812-839).
 
-    Two implementations of the same step:
+    `perform_step` tries these routes in this order, each at batch size 1 (what a PriorManager swap implies):
 
-    * **fused** (default whenever it applies): the segmentation module runs in torch; everything behind its output - prior forward on
-      the image's bank row, sigmoid, the composite loss, d loss / d seg, the prior's backward from the activations of that same pass,
-      Adam / Adamax and enforce_convexity on the row in place - is ONE C-ABI call (`inrfit_joint_step` and its path-connected
-      variants, awesome_amd.joint).  The torch optimizer then steps the segmentation parameters only (the prior's Parameters never
-      receive a .grad, which torch.optim skips); the prior's hyper-parameters are read from their param group every step, so host
-      LR schedulers keep working.  Applies to: batch size 1 (what a PriorManager swap implies), FBMSJointLoss / AwesomeImageLoss
-      (before its extra penalty; with it on too when `fused_extra_penalty=True`, unaries targets without a noneclass) with fusable
-      criteria, Adam or Adamax without amsgrad, a prior with a device form (ICNN, PathConnectedNet, ConvexDiffeomorphismNet; these
-      two only without weight decay, which torch would also apply to their 1x1 / linear layer).
-    * **autograd**: WrapperModule forward -> criterion -> loss.backward() through the HIP autograd bridges -> optimizer.step() ->
-      enforce_convexity(); any criterion, any optimizer.
+    joint      takes  image items; FBMSJointLoss, or AwesomeImageLoss on unaries targets without a noneclass (with its extra
+                      penalty on only under `fused_extra_penalty`: the step kernel then evaluates both data terms, the weighted
+                      criterion against the targets and the align term against [seg > 0.5], in one pass); an ICNN,
+                      PathConnectedNet or ConvexDiffeomorphismNet prior (these two without weight decay)
+               calls  the segmentation module in torch, then ONE entry point for everything behind its output - prior forward on
+                      the image's bank row, sigmoid, the composite loss, d loss / d seg, the prior's backward, Adam / Adamax and
+                      enforce_convexity in place: inrfit_joint_step / inrfit_pcn_joint_step / inrfit_cdn_joint_step
+                      (awesome_amd.joint); seg.backward(dseg)
+               else   `convexity` where that applies and the criterion has no such desc; `autograd` for everything else it
+                      refuses: batch > 1, the step that initialises ActNorm
+    convexity  takes  (`fused_convexity_losses`) AwesomeImageLoss, AwesomeImageLossJoint, AwesomeLoss, AwesomeLossJoint on an ICNN
+                      prior, in every phase, with ANY segmentation criterion; image items, and pixel items (input_mode='pixel')
+                      under prior_arg_mode 'xy_c_preattached' / 'param_clean_grid'
+               calls  the segmentation share g crit(seg, t) (one of the two below), inrfit_joint_prior_step (the prior's masked
+                      data term and hard / soft align term, the row's step, d(prior's share) / d seg:
+                      measures.losses.convexity_joint_form), the share's backward
+               else   `autograd`: batch > 1, a prior criterion without a kernel form, a step without scribble pixels
+      torch share     any network and criterion: segmentation_output, convexity_seg_share (the class's own evaluation,
+                      GradientPenaltyLoss's second-order penalty included), torch.autograd.backward([seg_term, seg], [None, dseg])
+      HIP share       (`fused_segmentation`) image items: a CNNNet awesome_amd.cnnseg supports (3x3, width 16, depth <= 3, 'rgbxy',
+                      one output) with BCELoss or GradientPenaltyLoss(BCELoss, mean): inrfit_cnnseg_forward, the prior's step,
+                      inrfit_cnnseg_step.  Pixel items: an FCNet awesome_amd.fcseg supports (width 16, depth <= 3, 'rgb' / 'rgbxy'
+                      rows of at most 8 channels, one output) with a plain mean BCELoss: inrfit_fcseg_forward, the prior's step,
+                      inrfit_fcseg_step.  Either network's gradient of both shares lands in one flat .grad buffer.  Any other
+                      network or criterion: the torch share
+    autograd   takes  any item, criterion and optimizer
+               calls  WrapperModule forward -> criterion -> loss.backward() through the HIP autograd bridges -> optimizer.step()
+                      -> enforce_convexity()
+
+    `joint` and `convexity` are the fused implementation (`fused`, the default whenever `_plan_fused` finds one: Adam or Adamax
+    without amsgrad, one param group for the prior, a prior with a fused device form, a criterion one of the two routes knows).
+    After their call the torch optimizer steps the segmentation parameters only (the prior's Parameters never receive a .grad,
+    which torch.optim skips); the prior's hyper-parameters are read from their param group every step, so host LR schedulers keep
+    working.  The criterion's desc is read every step too, so the runner's extra-penalty hook takes effect at once.
 
     The reference shares ONE optimizer state over all images' priors (it has one prior model whose VALUES are swapped): that is
-    `shared_prior_moments=True`, the default; False keeps Adam moments and step counts per image (fused path only).
-
-    `fused_extra_penalty` (opt-in, default False): AwesomeImageLoss steps with `extra_penalty` on (the runner's hook flips it in
-    mid-run) also take the fused path, where the prior's step kernel evaluates both of its data terms - the weighted criterion
-    against the targets and the align term against [seg > 0.5] - in one pass.  Off, those steps take the autograd path.
-
-    `fused_convexity_losses` (opt-in, default False): the convexity benchmark's losses (AwesomeImageLoss, AwesomeImageLossJoint,
-    AwesomeLoss, AwesomeLossJoint) on an ICNN prior take a fused path in every phase, wherever the step above refuses them, for ANY
-    segmentation criterion (GradientPenaltyLoss's second-order penalty included): the segmentation share g crit(seg, t) is evaluated
-    in torch exactly as the class does, and `inrfit_joint_prior_step` evaluates the prior's share (its masked data term and the hard
-    / soft align term), steps the row and returns d(prior's share) / d seg (measures.losses.convexity_joint_form).  Pixel mode
-    (input_mode='pixel', coordinates pre-attached) included; a step whose prior criterion has no kernel form, or without scribble
-    pixels, takes the autograd path.
-
-    `fused_segmentation` (opt-in, default False; needs fused_convexity_losses): in those image-mode steps a segmentation module that is
-    a supported CNNNet (awesome_amd.cnnseg: 3x3, width 16, depth <= 3, 'rgbxy', one output) with a BCELoss or
-    GradientPenaltyLoss(BCELoss, mean) segmentation criterion takes its whole step in HIP as well: inrfit_cnnseg_forward (s and the
-    segmentation share, penalties included), inrfit_joint_prior_step, inrfit_cnnseg_step (the network's gradient of both shares into
-    one flat .grad buffer), then the torch optimizer's step.  In pixel-mode steps (input_mode='pixel', prior_arg_mode 'xy_c_preattached'
-    or 'param_clean_grid') the same holds for a supported FCNet (awesome_amd.fcseg: width 16, depth <= 3, 'rgb' / 'rgbxy' rows of at
-    most 8 channels, one output) with a plain mean BCELoss: inrfit_fcseg_forward, inrfit_joint_prior_step, inrfit_fcseg_step.  Any
-    other network or criterion keeps the torch segmentation share."""
+    `shared_prior_moments=True`, the default; False keeps Adam moments and step counts per image (fused routes only)."""
 
     def __init__(self, wrapper: torch.nn.Module, bank: PriorBank, criterion: Callable, optimizer: torch.optim.Optimizer,
                  fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch",
@@ -163,8 +260,9 @@ class JointTrainer:
         self.fused_extra_penalty = bool(fused_extra_penalty)
         self.fused_convexity_losses = bool(fused_convexity_losses)
         self.fused_segmentation = bool(fused_segmentation)
+        # (both names date from the CNNNet share; they serve the FCNet share, inrfit_fcseg_step, as well)
         self._cnn_grads: Optional[torch.Tensor] = None     # the segmentation network's flat gradient (fused_segmentation)
-        self.cnnseg_status: Optional[torch.Tensor] = None   # status word of the last inrfit_cnnseg_step
+        self.cnnseg_status: Optional[torch.Tensor] = None   # status word of the last inrfit_cnnseg_step / inrfit_fcseg_step
         self._fused_plan = self._plan_fused()
         if fused and self._fused_plan is None:
             raise ValueError("this combination of prior module / criterion / optimizer has no fused joint step")
@@ -292,60 +390,81 @@ class JointTrainer:
             st = self._opt_state[k] = (iopt, fopt)
         return st
 
+    # -- the stages the fused routes share ---------------------------------------------------------------------------------------
+    def _step_state(self, key: Any):
+        """Bump the step count of `key` (of everything under shared_prior_moments) -> (t, ICNN moments, flow moments, the prior's
+        hyper-parameters).  Read from the param group every step: host LR schedulers change them between steps."""
+        plan, g = self._fused_plan, self._fused_plan["group"]
+        kc = None if self.shared_prior_moments else key
+        t = self._t[kc] = self._t.get(kc, 0) + 1
+        iopt, fopt = self._state_for(key, plan)
+        hp = dict(lr=float(g["lr"]), betas=tuple(g.get("betas", (0.9, 0.999))), eps=float(g.get("eps", 1e-8)),
+                  weight_decay=float(g.get("weight_decay", 0.0)))
+        return t, iopt, fopt, hp
+
+    def _latch(self, res) -> None:
+        """A non-finite loss froze the prior's row on the device.  The reference raises ValueError('Loss is nan or inf!') before
+        backward (torch_agent.py:484-487), which needs the loss on the host: check_finite="step" does exactly that (one 4-byte
+        read per step, _check_finite).  The default keeps the step free of host syncs: the failure is latched in `failed`, the
+        caller polls it (scripts/run.py: once per epoch) and raises then - the run is over either way, and a backbone that has
+        produced a NaN cannot be stepped meaningfully (its own backward multiplies any gradient by NaN)."""
+        self.last_status = res.status
+        self.failed |= res.status.reshape(-1)[0] != 0
+
+    def _check_finite(self, seg_status: Optional[torch.Tensor] = None) -> None:
+        """Latch the HIP segmentation share's status word, if this step has one, then raise under check_finite == 'step'."""
+        if seg_status is not None:
+            self.cnnseg_status = seg_status
+            self.failed |= seg_status.reshape(-1)[0] != 0
+        if self.check_finite == "step":
+            self.raise_if_failed()
+
+    def _finish(self, res, seg: torch.Tensor, pixel: bool):
+        """The torch optimizer's step (segmentation parameters only) and the step's (loss, output): [seg, sigmoid(prior)] along the
+        channel axis, image (1, 2, H, W) / pixel (1, n, 2)."""
+        self.optimizer.step()
+        out = torch.cat([seg.detach(), torch.sigmoid(res.prior_logits).view_as(seg)], dim=-1 if pixel else 0)[None]
+        return res.loss[0], out
+
+    # -- route `joint` -----------------------------------------------------------------------------------------------------------
     def _perform_step_fused(self, key: Any, inputs: Sequence[torch.Tensor], labels: torch.Tensor):
-        from . import icnn as K
         from . import joint as J
         plan, w = self._fused_plan, self.wrapper
         desc = self.criterion.joint_desc() if hasattr(self.criterion, "joint_desc") else None
-        g = plan["group"]
         if not self._joint_desc_fusable(desc, plan):
             if self._convexity_applies(plan["family"]):
                 return self._perform_step_prior_share(key, inputs, labels)
             return None
-        xi = inputs[0] if inputs[0].dim() == 4 else inputs[0][None]
-        if xi.shape[0] != 1:
+        item = _normalise_item(inputs)
+        if item is None:
             return None
         if plan["family"] == "pcn" and not all(float(b) > 0 for n, b in w.prior_module.named_buffers() if n.endswith("data_dep_init_done")):
             return None   # ActNorm's data-dependent initialisation happens in the module's first forward: take the autograd step once
-        ai = tuple(a if not isinstance(a, torch.Tensor) or a.dim() == 4 else a[None] for a in inputs[1:])
+        xi, ai, _, _ = item
         self._hand_over("fused")
         self.optimizer.zero_grad()
         seg = w.segmentation_output(xi, ai)                                   # (1, H, W), autograd attached
-        pa, _ = w.get_prior_args(xi, *ai, segm=seg)
-        coords = pa[0]
-        coords = coords[0] if coords.dim() == 4 else coords
-        grid = K.Grid.explicit(coords.reshape(coords.shape[0], -1).to(torch.float32).contiguous())
+        grid = _prior_grid(w.get_prior_args(xi, *ai, segm=seg)[0], False)
         row = self.bank.row(key)
         P = plan["ispec"].n_params
-        kc = None if self.shared_prior_moments else key
-        t = self._t[kc] = self._t.get(kc, 0) + 1
-        iopt, fopt = self._state_for(key, plan)
+        t, iopt, fopt, hp = self._step_state(key)
         segd = seg.detach().reshape(-1).to(torch.float32).contiguous()
         tgt = labels.detach().reshape(-1).to(torch.float32).contiguous()
-        hp = dict(step=t, lr=float(g["lr"]), betas=tuple(g.get("betas", (0.9, 0.999))), eps=float(g.get("eps", 1e-8)))
         if plan["family"] == "icnn":
-            res = J.joint_step(plan["ispec"], row, iopt, grid, segd, tgt, desc, optimizer=plan["kind"],
-                               weight_decay=float(g.get("weight_decay", 0.0)), clamp=True, **hp)
-        elif plan["family"] == "pcn":
-            res = J.pcn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
-                                   optimizer=plan["kind"], flow_weight_decay=0.0, **hp)
+            res = J.joint_step(plan["ispec"], row, iopt, grid, segd, tgt, desc, step=t, optimizer=plan["kind"], clamp=True, **hp)
         else:
-            res = J.cdn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
-                                   weight_decay_on_weight_g=0.0, **hp)
-        self.last_status = res.status
-        # A non-finite loss froze the prior's row on the device.  The reference raises ValueError('Loss is nan or inf!') before
-        # backward (torch_agent.py:484-487), which needs the loss on the host: check_finite="step" does exactly that (one 4-byte
-        # read per step).  The default keeps the step free of host syncs: the failure is latched in `failed`, the caller polls it
-        # (scripts/run.py: once per epoch) and raises then - the run is over either way, and a backbone that has produced a NaN
-        # cannot be stepped meaningfully (its own backward multiplies any gradient by NaN).
-        self.failed |= res.status.reshape(-1)[0] != 0
-        if self.check_finite == "step":
-            self.raise_if_failed()
+            del hp["weight_decay"]      # zero (_joint_desc_fusable): torch would also apply it to their 1x1 / linear layer
+            if plan["family"] == "pcn":
+                res = J.pcn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
+                                       step=t, optimizer=plan["kind"], flow_weight_decay=0.0, **hp)
+            else:
+                res = J.cdn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
+                                       step=t, weight_decay_on_weight_g=0.0, **hp)
+        self._latch(res)
+        self._check_finite()
         if seg.requires_grad:
             seg.backward(res.dseg.view_as(seg))
-        self.optimizer.step()                                                  # segmentation parameters only
-        out = torch.cat([seg.detach(), torch.sigmoid(res.prior_logits).view_as(seg)], dim=0)[None]
-        return res.loss[0], out
+        return self._finish(res, seg, False)
 
     def _joint_desc_fusable(self, desc, plan) -> bool:
         """Whether inrfit_joint_step (and its path-connected variants) take this step's composite loss."""
@@ -358,112 +477,58 @@ class JointTrainer:
                           # step, so gamma / alpha / beta and the hook's switch take effect at once)
         return True
 
+    # -- route `convexity` -------------------------------------------------------------------------------------------------------
     def _perform_step_prior_share(self, key: Any, inputs: Sequence[torch.Tensor], labels: torch.Tensor):
-        """fused_convexity_losses: g crit(seg, t) in torch + inrfit_joint_prior_step for the prior's share, one backward through the
-        segmentation network for both (torch.autograd.backward([seg_term, seg], [None, dseg])).  None -> the autograd step."""
+        """fused_convexity_losses: the segmentation share (torch or HIP) + inrfit_joint_prior_step for the prior's share, one
+        backward through the segmentation network for both.  None -> the autograd step."""
         from . import _lib as L
-        from . import icnn as K
         from . import joint as J
-        from .measures.losses import convexity_joint_form, convexity_seg_share
-        plan, w, crit = self._fused_plan, self.wrapper, self.criterion
-        g = plan["group"]
-        pixel = getattr(w, "input_mode", "image") == "pixel"
-        if pixel:       # WrapperModule._forward_pixels: _input (img, n, F) or (n, F), the coordinates are its first two features
-            # the coordinates: the input's first two features (xy_c_preattached) or the clean-xy rows, the third input (param_clean_grid)
-            if w.prior_arg_mode not in ("xy_c_preattached", "param_clean_grid"):
-                return None
-            if w.prior_arg_mode == "param_clean_grid" and (len(inputs) < 3 or not isinstance(inputs[2], torch.Tensor)):
-                return None
-            x0, rest = inputs[0], tuple(inputs[1:])
-            if x0.dim() == 2:
-                x0 = x0[None]
-                rest = tuple(a[None] if isinstance(a, torch.Tensor) and a.dim() == 2 else a for a in rest)
-            if x0.dim() != 3 or x0.shape[0] != 1:
-                return None
-            xi, ai = x0[0], tuple(a[0] if isinstance(a, torch.Tensor) else a for a in rest)
-            n = xi.shape[0]
-        else:
-            xi = inputs[0] if inputs[0].dim() == 4 else inputs[0][None]
-            if xi.shape[0] != 1:
-                return None
-            ai = tuple(a if not isinstance(a, torch.Tensor) or a.dim() == 4 else a[None] for a in inputs[1:])
-            n = xi.shape[-2] * xi.shape[-1]
-        form = convexity_joint_form(crit, n)
+        from .measures.losses import convexity_joint_form
+        plan, w = self._fused_plan, self.wrapper
+        item = _normalise_item(inputs, getattr(w, "input_mode", "image"), getattr(w, "prior_arg_mode", None))
+        if item is None:
+            return None
+        xi, ai, n, pixel = item
+        form = convexity_joint_form(self.criterion, n)
         if form is None or form.pixel != pixel or labels.numel() != (form.data_count or n):
             return None
         kw = {"_input": list(inputs)} if self.forward_additional_loss_args else {}
-        cnn = None
-        if self.fused_segmentation:
-            cnn = self._fcseg_plan(form, xi, ai, labels) if pixel else self._cnnseg_plan(form, xi, ai, labels, kw)
+        share = self._seg_share(form, xi, ai, labels, pixel, kw)
         self._hand_over("fused")
         self.optimizer.zero_grad()
-        if cnn is not None:       # the segmentation share in HIP: s and g (crit + penalties) now, the network's gradient below
-            if pixel:                 # an FCNet on pixel rows (awesome_amd.fcseg), else a CNNNet on the image (awesome_amd.cnnseg)
-                from . import fcseg as CS
-            else:
-                from . import cnnseg as CS
-            net, desc, image, feat = cnn
-            fwd = CS.forward(net, desc, image, feat, labels)
-            seg = fwd.seg.view(-1, 1) if pixel else fwd.seg.view(1, desc.height, desc.width_px)
-            seg_term = fwd.loss
-            self._cnnseg_side_effects(crit)
-        else:
-            seg = w.segmentation_output(xi, ai)                               # image (1, H, W) / pixel (n, 1), autograd attached
-            seg_term = convexity_seg_share(crit, form, seg[None], labels, **kw)  # the class's own view of the segmentation channel
-        pa, _ = w.get_prior_args(xi, *ai, segm=seg)
-        coords = pa[0]
-        if pixel:
-            coords = coords.reshape(-1, coords.shape[-1]).t()                  # (n, 2) -> (2, n)
-        else:
-            coords = coords[0] if coords.dim() == 4 else coords
-            coords = coords.reshape(coords.shape[0], -1)
-        grid = K.Grid.explicit(coords.to(torch.float32).contiguous())
+        seg, seg_term = share.forward()
+        grid = _prior_grid(w.get_prior_args(xi, *ai, segm=seg)[0], pixel)
         row = self.bank.row(key)
-        kc = None if self.shared_prior_moments else key
-        t = self._t[kc] = self._t.get(kc, 0) + 1
-        iopt, _ = self._state_for(key, plan)
+        t, iopt, _, hp = self._step_state(key)
         segd = seg.detach().reshape(-1).to(torch.float32).contiguous()
         tgt = labels.detach().reshape(-1).to(torch.float32).contiguous()
         st = seg_term.detach().reshape(1).to(torch.float32).contiguous()
-        res = J.joint_prior_step(plan["ispec"], row, iopt, grid, segd, tgt, form.prior_desc(), step=t, lr=float(g["lr"]),
-                                 seg_term=st, optimizer=plan["kind"], betas=tuple(g.get("betas", (0.9, 0.999))),
-                                 eps=float(g.get("eps", 1e-8)), weight_decay=float(g.get("weight_decay", 0.0)), clamp=True)
-        self.last_status = res.status
-        self.failed |= res.status.reshape(-1)[0] != 0                         # see _perform_step_fused
-        if cnn is not None:
-            dseg = res.dseg if form.align_rule == L.ALIGN_SOFT else None      # hard / none: d(prior's share) / d seg = 0
-            P = CS.param_count(desc)
-            if self._cnn_grads is None or self._cnn_grads.numel() != P or self._cnn_grads.device != image.device:
-                self._cnn_grads = torch.empty(P, dtype=torch.float32, device=image.device)
-            out_cnn = CS.step(net, desc, image, feat, labels, dseg=dseg, reuse_forward=True, grads=self._cnn_grads)
-            # a non-finite loss or gradient: the network's gradient is zero (the optimizer still steps its moments, as torch would
-            # on a zero gradient) and the failure is latched like the prior's
-            self.cnnseg_status = out_cnn.status
-            self.failed |= out_cnn.status.reshape(-1)[0] != 0
-            if self.check_finite == "step":
-                self.raise_if_failed()
-            CS.assign_grads(net, self._cnn_grads)
-            self.optimizer.step()
-            prior = torch.sigmoid(res.prior_logits)
-            return res.loss[0], torch.cat([seg, prior.view_as(seg)], dim=-1 if pixel else 0)[None]
-        if self.check_finite == "step":
-            self.raise_if_failed()
-        roots, grads = [], []
-        if seg_term.requires_grad:
-            roots.append(seg_term)
-            grads.append(None)
-        if form.align_rule == L.ALIGN_SOFT and seg.requires_grad:     # hard / none: d(prior's share) / d seg = 0
-            roots.append(seg)
-            grads.append(res.dseg.view_as(seg))
-        if roots:
-            torch.autograd.backward(roots, grads)
-        self.optimizer.step()                                                  # segmentation parameters only
-        prior = torch.sigmoid(res.prior_logits)
-        if pixel:
-            out = torch.cat([seg.detach(), prior.view_as(seg)], dim=-1)[None]
-        else:
-            out = torch.cat([seg.detach(), prior.view_as(seg)], dim=0)[None]
-        return res.loss[0], out
+        res = J.joint_prior_step(plan["ispec"], row, iopt, grid, segd, tgt, form.prior_desc(), step=t, seg_term=st,
+                                 optimizer=plan["kind"], clamp=True, **hp)
+        self._latch(res)
+        dseg = res.dseg if form.align_rule == L.ALIGN_SOFT else None          # hard / none: d(prior's share) / d seg = 0
+        share.backward(seg, seg_term, dseg, self._check_finite)
+        return self._finish(res, seg, pixel)
+
+    def _seg_share(self, form, xi, ai, labels, pixel: bool, kw):
+        """The HIP share where fused_segmentation is on and _cnnseg_plan (image items) / _fcseg_plan (pixel items) accepts the
+        step's network and criterion, else the torch share.  `kw`: the criterion's `_input` keyword, if it takes one."""
+        if self.fused_segmentation:
+            if pixel:
+                from . import fcseg as CS
+                hip = self._fcseg_plan(form, xi, ai, labels)
+            else:
+                from . import cnnseg as CS
+                hip = self._cnnseg_plan(form, xi, ai, labels, kw)
+            if hip is not None:
+                return _HipSegShare(self, CS, hip, labels, pixel)
+        return _TorchSegShare(self, form, xi, ai, labels, kw)
+
+    def _seg_grad_buffer(self, n_params: int, device) -> torch.Tensor:
+        """The HIP share's flat gradient buffer, kept across steps (the parameters' .grad are views of it)."""
+        if self._cnn_grads is None or self._cnn_grads.numel() != n_params or self._cnn_grads.device != device:
+            self._cnn_grads = torch.empty(n_params, dtype=torch.float32, device=device)
+        return self._cnn_grads
 
     def _cnnseg_plan(self, form, xi, ai, labels, kw):
         """fused_segmentation: (net, InrCnnSegDesc, image, features) when this image-mode step's segmentation share has a HIP form
@@ -525,13 +590,6 @@ class JointTrainer:
         desc = FS.make_desc(net, image.shape[1], n, data_count=form.data_count,
                             inversion=bool(getattr(w, "use_segmentation_output_inversion", False)), g=form.g)
         return net, desc, image, feat
-
-    @staticmethod
-    def _cnnseg_side_effects(crit) -> None:
-        """What convexity_seg_share (the class's __call__) leaves behind."""
-        from .measures.losses import AwesomeImageLossJoint, AwesomeLossJoint
-        if isinstance(crit, (AwesomeImageLossJoint, AwesomeLossJoint)):
-            crit.criterion.apply_gradient_penalty = True
 
     # -- the step ------------------------------------------------------------------------------------------------------------
     def perform_step(self, key: Any, inputs: Sequence[torch.Tensor], labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -7,7 +7,6 @@ respect to every weight (a tangent forward and one backward with the masks fixed
 other network or criterion keeps the torch path; that is routing (`net_supported`, `criterion_form` return False / None)."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -15,7 +14,9 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .icnn import _check_dev, _stream_ptr
+from . import _segnet as S
+from ._segnet import _plain_bce, assign_grads  # noqa: F401 (assign_grads: part of this module's surface)
+from .icnn import _check_dev
 
 GROUP_NONE, GROUP_RGB, GROUP_XY, GROUP_FEAT = -1, 0, 1, 2
 
@@ -56,10 +57,6 @@ class SegCriterionForm:
             else:
                 out.append(GROUP_NONE)
         return out
-
-
-def _plain_bce(c) -> bool:
-    return type(c) is torch.nn.BCELoss and c.weight is None and c.reduction == "mean"
 
 
 def criterion_form(criterion, kwargs, image_channels: int, in_channels: int) -> Optional[SegCriterionForm]:
@@ -106,35 +103,6 @@ def make_desc(net, image_channels: int, height: int, width: int, form: SegCriter
     return d
 
 
-def param_count(desc: L.InrCnnSegDesc) -> int:
-    n = L.load().inrfit_cnnseg_param_count(C.byref(desc))
-    if n < 0:
-        raise L.InrfitError("inrfit_cnnseg_param_count: unsupported CNNNet shape")
-    return int(n)
-
-
-_ws_cache = {}
-
-
-def _workspace(desc: L.InrCnnSegDesc, dev) -> Tensor:
-    """One workspace per (shape, device): inrfit_cnnseg_step(reuse_forward=1) reads what inrfit_cnnseg_forward left in it."""
-    key = (desc.in_channels, desc.width, desc.depth, desc.height, desc.width_px, str(dev))
-    ws = _ws_cache.get(key)
-    if ws is None:
-        nbytes = int(L.load().inrfit_cnnseg_workspace_bytes(C.byref(desc)))
-        if nbytes < 0:
-            raise L.InrfitError("inrfit_cnnseg_workspace_bytes: unsupported CNNNet shape")
-        ws = _ws_cache[key] = L.scratch(nbytes // 4 + 64, dtype=torch.float32, device=dev)
-    return ws
-
-
-def _layer_ptrs(net):
-    convs = net.conv_layers()
-    w = (C.c_void_p * len(convs))(*[c.weight.data_ptr() for c in convs])
-    b = (C.c_void_p * len(convs))(*[c.bias.data_ptr() for c in convs])
-    return C.cast(w, C.c_void_p), C.cast(b, C.c_void_p), (w, b)       # (the arrays stay alive with the caller's reference)
-
-
 def _inputs(desc, image: Tensor, features: Optional[Tensor]):
     n = desc.height * desc.width_px
     image = _check_dev(image.detach(), "image")
@@ -147,73 +115,26 @@ def _inputs(desc, image: Tensor, features: Optional[Tensor]):
     return image, features
 
 
-@dataclass
-class CnnSegResult:
-    logits: Optional[Tensor]   # [H W] f
-    seg: Optional[Tensor]      # [H W] s
-    loss: Tensor               # [1] g (crit + penalties)
-    grads: Optional[Tensor] = None    # [P] in parameters() order
-    status: Optional[Tensor] = None   # [1] int32: 1 = non-finite loss or gradient (grads zeroed)
+CnnSegResult = S.SegResult     # logits / seg [H W], loss [1] g (crit + penalties)
+
+# (against fcseg's driver only two fields change what a call does: the target covers every pixel, and a forward without a target
+# still passes a loss cell; the others say where this family keeps the same things)
+_DRIVER = S.SegDriver("cnnseg", "CNNNet", layers=lambda net: net.conv_layers(), inputs=_inputs,
+                      n_points=lambda d: d.height * d.width_px, n_target=lambda d: d.height * d.width_px,
+                      ws_key=lambda d: (d.in_channels, d.width, d.depth, d.height, d.width_px), loss_without_target=True)
+
+
+def param_count(desc: L.InrCnnSegDesc) -> int:
+    return _DRIVER.param_count(desc)
 
 
 def forward(net, desc: L.InrCnnSegDesc, image: Tensor, features: Optional[Tensor], target: Optional[Tensor] = None) -> CnnSegResult:
     """f and s of the network (and with `target` the loss, kept in the workspace for step(..., reuse_forward=True))."""
-    dev = image.device
-    n = desc.height * desc.width_px
-    image, features = _inputs(desc, image, features)
-    if target is not None:
-        target = _check_dev(target.detach().float(), "target")
-        assert target.numel() == n
-    w, b, _keep = _layer_ptrs(net)
-    logits = L.scratch(n, dtype=torch.float32, device=dev)
-    seg = L.scratch(n, dtype=torch.float32, device=dev)
-    loss = L.scratch(1, dtype=torch.float32, device=dev)
-    ws = _workspace(desc, dev)
-    rc = L.load().inrfit_cnnseg_forward(C.byref(desc), w, b, image.data_ptr(), None if features is None else features.data_ptr(),
-                                        None if target is None else target.data_ptr(), logits.data_ptr(), seg.data_ptr(),
-                                        loss.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
-    L.check(rc, "inrfit_cnnseg_forward")
-    return CnnSegResult(logits, seg, loss)
+    return _DRIVER.forward(net, desc, image, features, target)
 
 
 def step(net, desc: L.InrCnnSegDesc, image: Tensor, features: Optional[Tensor], target: Tensor, dseg: Optional[Tensor] = None,
          reuse_forward: bool = False, grads: Optional[Tensor] = None) -> CnnSegResult:
     """The network's gradient of loss + sum(dseg * s) into `grads` ([param_count] float32, allocated when None).  reuse_forward:
     forward(..., target) ran with the same arguments just before (the joint step puts the prior's step in between)."""
-    dev = image.device
-    n = desc.height * desc.width_px
-    image, features = _inputs(desc, image, features)
-    target = _check_dev(target.detach().float(), "target")
-    assert target.numel() == n
-    if dseg is not None:
-        dseg = _check_dev(dseg.detach(), "dseg")
-        assert dseg.numel() == n
-    P = param_count(desc)
-    if grads is None:
-        grads = L.scratch(P, dtype=torch.float32, device=dev)
-    assert grads.numel() == P and grads.is_contiguous() and grads.dtype == torch.float32
-    w, b, _keep = _layer_ptrs(net)
-    logits = seg = None
-    if not reuse_forward:
-        logits = L.scratch(n, dtype=torch.float32, device=dev)
-        seg = L.scratch(n, dtype=torch.float32, device=dev)
-    loss = L.scratch(1, dtype=torch.float32, device=dev)
-    status = L.scratch(1, dtype=torch.int32, device=dev)      # (always written)
-    ws = _workspace(desc, dev)
-    rc = L.load().inrfit_cnnseg_step(C.byref(desc), w, b, image.data_ptr(), None if features is None else features.data_ptr(),
-                                     target.data_ptr(), None if dseg is None else dseg.data_ptr(), int(bool(reuse_forward)),
-                                     None if logits is None else logits.data_ptr(), None if seg is None else seg.data_ptr(),
-                                     loss.data_ptr(), grads.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                     _stream_ptr(dev))
-    L.check(rc, "inrfit_cnnseg_step")
-    return CnnSegResult(logits, seg, loss, grads, status)
-
-
-def assign_grads(net, grads: Tensor) -> None:
-    """Every parameter's .grad becomes its view of the flat gradient buffer (parameters() order)."""
-    off = 0
-    for p in net.parameters():
-        k = p.numel()
-        p.grad = grads[off:off + k].view_as(p)
-        off += k
-    assert off == grads.numel()
+    return _DRIVER.step(net, desc, image, features, target, dseg, reuse_forward, grads)

@@ -58,7 +58,9 @@ _ws_cache = {}
 
 
 def _workspace(key, nbytes_fn, dev) -> Tensor:
-    """One workspace per (model shape, grid size, device): a joint epoch calls the step thousands of times."""
+    """One workspace per (model shape, grid size, device): a joint epoch calls the step thousands of times.  Every call here
+    writes all of its workspace before it reads it, so under L.POISON a fresh NaN-filled one per call is the check that it does;
+    the segmentation networks' cache (_segnet.SegDriver.workspace) carries state between two calls and must not do that."""
     k = (key, str(dev))
     ws = _ws_cache.get(k)
     if ws is None or L.POISON:
@@ -70,61 +72,67 @@ def _workspace(key, nbytes_fn, dev) -> Tensor:
     return ws
 
 
+def _icnn_joint(entry: str, spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
+                n_target: int, desc, extra: tuple, od: L.InrOptDesc, step: int) -> JointStepResult:
+    """inrfit_joint_step / inrfit_joint_prior_step: `extra` is what the entry point takes between its loss desc and its opt desc."""
+    params, seg, target = K._check_dev(params, "params"), K._check_dev(seg, "seg"), K._check_dev(target, "target")
+    dev, n = params.device, grid.n_points
+    assert params.numel() == spec.n_params and seg.numel() == n and target.numel() == n_target
+    assert opt_state.numel() == 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS and opt_state.is_contiguous()
+    md, gd = spec.desc(), grid.desc()
+    lib = L.load()
+    ws = _workspace(("icnn", spec, n), lambda: lib.inrfit_joint_step_workspace_bytes(C.byref(md), C.byref(gd)), dev)
+    loss, dseg, logits, status = _outputs(n, dev)
+    rc = getattr(lib, entry)(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(),
+                             C.byref(desc), *extra, C.byref(od), int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(),
+                             status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
+    L.check(rc, entry)
+    return JointStepResult(loss, dseg, logits, status)
+
+
+def _flow_joint(family: str, ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
+                flow_opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, od: L.InrOptDesc,
+                flow_weight_decay: float, step: int) -> JointStepResult:
+    """inrfit_pcn_joint_step / inrfit_cdn_joint_step: `fspec` is the family's flow (RnvpSpec / FlowSpec)."""
+    dev, n = icnn_params.device, grid.n_points
+    md, fd, gd = ispec.desc(), fspec.desc(), grid.desc()
+    lib = L.load()
+    ws_bytes = getattr(lib, f"inrfit_{family}_workspace_bytes")
+    ws = _workspace((family, ispec, fspec, n),
+                    lambda: ws_bytes(C.byref(md), C.byref(fd), C.byref(gd), 1) + lib.inrfit_joint_loss_workspace_bytes(n) + 4 * n + 1024,
+                    dev)
+    loss, dseg, logits, status = _outputs(n, dev)
+    entry = f"inrfit_{family}_joint_step"
+    rc = getattr(lib, entry)(C.byref(md), C.byref(fd), icnn_params.data_ptr(), flow_params.data_ptr(), icnn_opt_state.data_ptr(),
+                             flow_opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(), C.byref(desc), C.byref(od),
+                             float(flow_weight_decay), int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(),
+                             status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
+    L.check(rc, entry)
+    return JointStepResult(loss, dseg, logits, status)
+
+
 def joint_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
                desc: L.InrJointLossDesc, step: int, lr: float, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8,
                weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
     """ICNN prior (ConvexNet / ConvexNextNet).  `params` [P] and `opt_state` [2P + 8] are updated IN PLACE."""
-    params, seg, target = K._check_dev(params, "params"), K._check_dev(seg, "seg"), K._check_dev(target, "target")
-    dev, n = params.device, grid.n_points
-    assert params.numel() == spec.n_params and seg.numel() == n and target.numel() == n
-    assert opt_state.numel() == 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS and opt_state.is_contiguous()
-    md, gd, od = spec.desc(), grid.desc(), _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp)
-    lib = L.load()
-    ws = _workspace(("icnn", spec, n), lambda: lib.inrfit_joint_step_workspace_bytes(C.byref(md), C.byref(gd)), dev)
-    loss, dseg, logits, status = _outputs(n, dev)
-    rc = lib.inrfit_joint_step(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(),
-                               C.byref(desc), C.byref(od), int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(),
-                               status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_joint_step")
-    return JointStepResult(loss, dseg, logits, status)
+    return _icnn_joint("inrfit_joint_step", spec, params, opt_state, grid, seg, target, grid.n_points, desc, (),
+                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
 
 
 def pcn_joint_step(ispec: K.IcnnSpec, rspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor, flow_opt_state: Tensor,
                    grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, step: int, lr: float,
                    optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8, flow_weight_decay: float = 0.0) -> JointStepResult:
     """PathConnectedNet prior (ICNN behind the RealNVP deformation); every tensor is one row, updated in place."""
-    dev, n = icnn_params.device, grid.n_points
-    md, rd, gd, od = ispec.desc(), rspec.desc(), grid.desc(), _opt_desc(optimizer, lr, betas, eps, 0.0, True)
-    lib = L.load()
-    ws = _workspace(("pcn", ispec, rspec, n),
-                    lambda: lib.inrfit_pcn_workspace_bytes(C.byref(md), C.byref(rd), C.byref(gd), 1) + lib.inrfit_joint_loss_workspace_bytes(n)
-                    + 4 * n + 1024, dev)
-    loss, dseg, logits, status = _outputs(n, dev)
-    rc = lib.inrfit_pcn_joint_step(C.byref(md), C.byref(rd), icnn_params.data_ptr(), flow_params.data_ptr(), icnn_opt_state.data_ptr(),
-                                   flow_opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(), C.byref(desc),
-                                   C.byref(od), float(flow_weight_decay), int(step), loss.data_ptr(), dseg.data_ptr(),
-                                   logits.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_pcn_joint_step")
-    return JointStepResult(loss, dseg, logits, status)
+    return _flow_joint("pcn", ispec, rspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
+                       _opt_desc(optimizer, lr, betas, eps, 0.0, True), flow_weight_decay, step)
 
 
 def cdn_joint_step(ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor, flow_opt_state: Tensor,
                    grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, step: int, lr: float,
                    betas=(0.9, 0.999), eps: float = 1e-8, weight_decay_on_weight_g: float = 0.0) -> JointStepResult:
     """ConvexDiffeomorphismNet prior (ICNN behind the weight-normed coupling flow); Adam only, like its pretrain loop."""
-    dev, n = icnn_params.device, grid.n_points
-    md, fd, gd, od = ispec.desc(), fspec.desc(), grid.desc(), _opt_desc("adam", lr, betas, eps, 0.0, True)
-    lib = L.load()
-    ws = _workspace(("cdn", ispec, fspec, n),
-                    lambda: lib.inrfit_cdn_workspace_bytes(C.byref(md), C.byref(fd), C.byref(gd), 1) + lib.inrfit_joint_loss_workspace_bytes(n)
-                    + 4 * n + 1024, dev)
-    loss, dseg, logits, status = _outputs(n, dev)
-    rc = lib.inrfit_cdn_joint_step(C.byref(md), C.byref(fd), icnn_params.data_ptr(), flow_params.data_ptr(), icnn_opt_state.data_ptr(),
-                                   flow_opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(), C.byref(desc),
-                                   C.byref(od), float(weight_decay_on_weight_g), int(step), loss.data_ptr(), dseg.data_ptr(),
-                                   logits.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_cdn_joint_step")
-    return JointStepResult(loss, dseg, logits, status)
+    return _flow_joint("cdn", ispec, fspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
+                       _opt_desc("adam", lr, betas, eps, 0.0, True), weight_decay_on_weight_g, step)
 
 
 def joint_prior_desc(kind: str = "bce", weight_mode: str = "none", ratio: float = 1.0, noneclass=None, data_count: int = 0,
@@ -140,21 +148,10 @@ def joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: 
     """ICNN prior, the prior's share only (include/inrfit.h: inrfit_joint_prior_step).  `target` holds desc.data_count values (all
     points when 0); `seg_term` is None or a one-element float32 device tensor, the caller's segmentation share.  `params` [P] and
     `opt_state` [2P + 8] are updated IN PLACE.  loss: composite, data term, mean align term before beta, gradient scale."""
-    params, seg, target = K._check_dev(params, "params"), K._check_dev(seg, "seg"), K._check_dev(target, "target")
-    dev, n = params.device, grid.n_points
-    assert params.numel() == spec.n_params and seg.numel() == n
-    assert target.numel() == (desc.data_count if desc.data_count > 0 else n)
-    assert opt_state.numel() == 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS and opt_state.is_contiguous()
     if seg_term is not None:
         seg_term = K._check_dev(seg_term, "seg_term")
         assert seg_term.numel() == 1
-    md, gd, od = spec.desc(), grid.desc(), _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp)
-    lib = L.load()
-    ws = _workspace(("icnn", spec, n), lambda: lib.inrfit_joint_step_workspace_bytes(C.byref(md), C.byref(gd)), dev)
-    loss, dseg, logits, status = _outputs(n, dev)
-    rc = lib.inrfit_joint_prior_step(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), seg.data_ptr(),
-                                     target.data_ptr(), C.byref(desc), None if seg_term is None else seg_term.data_ptr(), C.byref(od),
-                                     int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                     ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_joint_prior_step")
-    return JointStepResult(loss, dseg, logits, status)
+    return _icnn_joint("inrfit_joint_prior_step", spec, params, opt_state, grid, seg, target,
+                       desc.data_count if desc.data_count > 0 else grid.n_points, desc,
+                       (None if seg_term is None else seg_term.data_ptr(),),
+                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
