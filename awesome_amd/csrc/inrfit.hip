@@ -1717,6 +1717,10 @@ static int rnvp_set_lds() {
     ok &= hipFuncSetAttribute((const void*)rnvp_fwd_kernel<2, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
     ok &= hipFuncSetAttribute((const void*)rnvp_bwd_points_kernel<2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
     ok &= hipFuncSetAttribute((const void*)rnvp_bwd_points_kernel<2, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
+    ok &= hipFuncSetAttribute((const void*)rnvp_bwd_points_kernel<2, 1, 1, RnvpBwdDinArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
+    ok &= hipFuncSetAttribute((const void*)rnvp_bwd_points_kernel<2, 2, 1, RnvpBwdDinArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
+    ok &= hipFuncSetAttribute((const void*)rnvp_bwd_points_kernel<3, 1, 1, RnvpBwdDinArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
+    ok &= hipFuncSetAttribute((const void*)rnvp_bwd_points_kernel<3, 2, 1, RnvpBwdDinArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
     ok &= hipFuncSetAttribute((const void*)rnvp_inverse_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
     ok &= hipFuncSetAttribute((const void*)rnvp_inverse_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
     rc = ok ? INR_OK : INR_ENODEVICE;
@@ -1783,10 +1787,13 @@ void launch_rnvp_fwd(const PcnWs& w, const float* rp, const InrGridDesc* grid, i
     }
 }
 
-static void launch_rnvp_bwd(const PcnWs& w, const float* rp, const InrGridDesc* grid, int n_images, hipStream_t s) {
+// seed: the gradient at the deformed coordinates when it is not the ICNN's (w.dxd); din: also d / d input coordinates (both:
+// inrfit_rnvp_backward, whose workspace has one lane per point in the backward walk - w.sb.U == 1)
+static void launch_rnvp_bwd(const PcnWs& w, const float* rp, const InrGridDesc* grid, int n_images, hipStream_t s,
+                            const float* seed = nullptr, float* din = nullptr) {
     RnvpBwdArgs a{};
     a.RE = w.RE;   // packed by the forward of this step
-    a.dxd = w.dxd;
+    a.dxd = seed ? seed : w.dxd;
     a.zs = w.zs;
     a.ps = w.ps;
     a.slab1 = w.slab1;
@@ -1796,7 +1803,18 @@ static void launch_rnvp_bwd(const PcnWs& w, const float* rp, const InrGridDesc* 
     a.S1 = w.S1;
     const dim3 g1(w.sb.blocks, n_images), b1(w.sb.threads);
     const size_t lds = (size_t)(w.rm.LDSF + 4 * w.S1) * sizeof(float);
-    if (w.rm.C == 2) {
+    if (din != nullptr) {
+        RnvpBwdDinArgs da{};
+        static_cast<RnvpBwdArgs&>(da) = a;
+        da.din = din;
+        if (w.rm.C == 2) {
+            if (w.sb.Q == 2) hipLaunchKernelGGL((rnvp_bwd_points_kernel<2, 2, 1, RnvpBwdDinArgs>), g1, b1, lds, s, da);
+            else hipLaunchKernelGGL((rnvp_bwd_points_kernel<2, 1, 1, RnvpBwdDinArgs>), g1, b1, lds, s, da);
+        } else {
+            if (w.sb.Q == 2) hipLaunchKernelGGL((rnvp_bwd_points_kernel<3, 2, 1, RnvpBwdDinArgs>), g1, b1, lds, s, da);
+            else hipLaunchKernelGGL((rnvp_bwd_points_kernel<3, 1, 1, RnvpBwdDinArgs>), g1, b1, lds, s, da);
+        }
+    } else if (w.rm.C == 2) {
         if (w.sb.Q == 2) hipLaunchKernelGGL((rnvp_bwd_points_kernel<2, 2>), g1, b1, lds, s, a);
         else if (w.sb.U == 2) hipLaunchKernelGGL((rnvp_bwd_points_kernel<2, 1, 2>), g1, b1, lds, s, a);
         else if (w.sb.U == 4) hipLaunchKernelGGL((rnvp_bwd_points_kernel<2, 1, 4>), g1, b1, lds, s, a);
@@ -1881,6 +1899,40 @@ void launch_rnvp_grads(const PcnWs& w, int n_images, float* rp, float* grads_out
     launch_rnvp_update_args(w, n_images, make_rnvp_upd_args(w, n_images, 1, rp, nullptr, grads_out, nullptr, 0.f, 0, nullptr, 0, nullptr), s);
 }
 
+// ---- the RealNVP in front of the layer-by-layer ICNN (wide.h): shapes without a fused kernel ---------------------------------------
+// An ICNN-form shape of the layer-by-layer path: relu layer 0, one output, square layers (the encode shapes stay refused).
+static bool pcn_wide_shape(const InrModelDesc* m) { return use_wide(m) && m->act0 == INR_ACT_RELU && !wide_desc_general(m); }
+
+// workspace: the RealNVP's buffers for all images (carve_pcn without an ICNN) | logits [N] | dL/dlogits [N] | ONE image's
+// layer-by-layer workspace | the loss coefficients of every image
+struct PcnWideWs {
+    PcnWs p;
+    WideMap m;
+    WideWs w;
+    float *logit, *dy, *coef;
+    long long bytes;
+};
+
+static PcnWideWs carve_pcn_wide(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* base) {
+    PcnWideWs q;
+    q.p = carve_pcn(nullptr, r, grid, n_images, base);
+    q.m = make_wide_map(model);
+    const long long N = grid->n_points;
+    char* b = (char*)base;
+    long long off = q.p.bytes;
+    q.logit = (float*)(b + off); off += align256(N * 4);
+    q.dy = (float*)(b + off); off += align256(N * 4);
+    q.w = carve_wide(q.m, N, false, b + off);
+    off += q.w.bytes;
+    q.coef = (float*)(b + off); off += wide_align((long long)n_images * 2 * 4);
+    q.bytes = off;
+    return q;
+}
+
+static int64_t pcn_wide_bytes(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images) {
+    return carve_pcn_wide(model, r, grid, n_images, nullptr).bytes;
+}
+
 }  // namespace
 
 int64_t inrfit_rnvp_param_count(const InrRnvpDesc* rnvp) {
@@ -1892,7 +1944,10 @@ int64_t inrfit_pcn_workspace_bytes(const InrModelDesc* model, const InrRnvpDesc*
     if (!rnvp_ok(rnvp)) return INR_EUNSUPPORTED;
     if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
     const KernelEntry* e = model ? find_entry(model) : nullptr;
-    if (model && !e) return INR_EUNSUPPORTED;
+    if (model && !e) {
+        if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
+        return pcn_wide_bytes(model, rnvp, grid, n_images);   // the layer-by-layer ICNN behind the RealNVP
+    }
     return carve_pcn(e, rnvp, grid, n_images, nullptr).bytes;
 }
 
@@ -1944,6 +1999,24 @@ int inrfit_rnvp_forward(const InrRnvpDesc* rnvp, const float* flow_params, const
     int rc = check_pcn(nullptr, rnvp, grid, n_images, workspace, workspace_bytes, false, &e, &w);
     if (rc) return rc;
     launch_rnvp_fwd(w, flow_params, grid, n_images, out_coords, false, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+int inrfit_rnvp_backward(const InrRnvpDesc* rnvp, const float* flow_params, const InrGridDesc* grid, const float* dout_coords,
+                         int n_images, float* flow_grads, float* din_coords, void* workspace, int64_t workspace_bytes, void* stream) {
+    const KernelEntry* e;
+    PcnWs w;
+    if (!flow_params || !dout_coords || !flow_grads) return INR_EINVAL;
+    int rc = check_pcn(nullptr, rnvp, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    if (rc) return rc;
+    if (w.sb.U != 1) {   // (a forced U-lanes-per-point shape: the seeded walk runs one lane per point; fewer slab rows than carved)
+        w.sb = FlowShape{1, 1, 256, (int)((grid->n_points + 255) / 256)};
+        w.blocks1 = w.sb.blocks;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    launch_rnvp_fwd(w, flow_params, grid, n_images, w.xd, true, s);   // the forward is recomputed: the state in front of every flow
+    launch_rnvp_bwd(w, flow_params, grid, n_images, s, dout_coords, din_coords);
+    launch_rnvp_grads(w, n_images, const_cast<float*>(flow_params), flow_grads, s);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
@@ -2473,6 +2546,162 @@ int joint_step_run(D d, const InrModelDesc* model, float* params, float* opt_sta
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------------
+// PathConnectedNet over an ICNN of the layer-by-layer path (n_hidden > 130 or more than two hidden layers): the RealNVP's
+// kernels on all images, then per image wide_forward / wide_backward on the deformed coordinates as an explicit grid with
+// dcoords = dxd, then the RealNVP's backward seeded from dxd.  Everything stays on the stream.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// dL/dlogit of the data term from the logits wide_out_kernel wrote (the same expressions as its own dy, which it keeps in registers):
+// what wide_dx_kernel starts dL/dcoords from (s_o dL/dlogit)
+__global__ __launch_bounds__(256) void pcn_wide_dy_kernel(const float* __restrict__ logit, const float* __restrict__ target,
+                                                          const float* __restrict__ coef, int loss_kind, long long N,
+                                                          float* __restrict__ dy) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    const float y = logit[p], tg = target[p];
+    const float pr = 1.f / (1.f + expf(-y));
+    const float cw = tg < 0.5f ? coef[0] : coef[1];
+    float d;
+    if (loss_kind == INR_LOSS_SE) {
+        d = 2.f * (pr - tg) * pr * (1.f - pr) * cw;
+    } else {
+        const float pq = pr * (1.f - pr);
+        d = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
+    }
+    dy[p] = d;
+}
+
+static int check_pcn_wide(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* workspace,
+                          int64_t workspace_bytes, PcnWideWs* q) {
+    if (!rnvp_ok(r)) return INR_EUNSUPPORTED;
+    if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
+    if (model->in_features != r->channels) return INR_EINVAL;
+    if (!workspace || !grid_ok(grid, n_images, 0x7fffffffLL / WIDE_MAX_HIDDEN * 64)) return INR_EINVAL;
+    if (grid->mode == INR_GRID_SEPARABLE && r->channels == 3 && !grid->ts) return INR_EINVAL;   // the separable grid's t axis
+    *q = carve_pcn_wide(model, r, grid, n_images, workspace);
+    if (workspace_bytes < q->bytes) return INR_EWORKSPACE;
+    return rnvp_set_lds();
+}
+
+static int pcn_wide_forward(const InrModelDesc* model, const InrRnvpDesc* r, const float* ip, const float* fp, const InrGridDesc* grid,
+                            int n_images, float* logits, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    PcnWideWs q;
+    int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
+    if (rc) return rc;
+    launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, false, s);
+    for (int img = 0; img < n_images; ++img)
+        if ((rc = wide_forward(q.m, q.w, model, ip + (size_t)img * q.m.P, &q.p.dgrid, img, nullptr, 0, false,
+                               logits + (size_t)img * grid->n_points, s)))
+            return rc;
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+// forward + backward of image `img` on the deformed grid: gradients and the loss into q.w.grads, dL/dxd into q.p.dxd
+static int pcn_wide_image(PcnWideWs& q, const InrModelDesc* model, const float* p, int img, const float* target, int loss_kind,
+                          hipStream_t s) {
+    const long long N = q.p.dgrid.n_points;
+    const bool ext = loss_kind == INR_LOSS_EXTERNAL;
+    q.w.coef = q.coef + 2 * img;
+    int rc = wide_forward(q.m, q.w, model, p, &q.p.dgrid, img, target, loss_kind, true, ext ? nullptr : q.logit, s);
+    if (rc) return rc;
+    if (!ext)
+        hipLaunchKernelGGL(pcn_wide_dy_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const float*)q.logit, target,
+                           (const float*)q.w.coef, loss_kind, N, q.dy);
+    return wide_backward(q.m, q.w, model, p, N, s, ext ? target : q.dy, q.p.dxd + (size_t)img * q.m.C * N);
+}
+
+static int pcn_wide_loss_grad(const InrModelDesc* model, const InrRnvpDesc* r, const float* ip, const float* fp, const InrGridDesc* grid,
+                              const float* targets, const InrLossDesc* loss, int n_images, float* loss_out, float* icnn_grads,
+                              float* flow_grads, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    PcnWideWs q;
+    int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
+    if (rc) return rc;
+    const long long N = grid->n_points;
+    launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, true, s);
+    if (loss->kind != INR_LOSS_EXTERNAL) hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, q.coef, 1.f);
+    for (int img = 0; img < n_images; ++img) {
+        if ((rc = pcn_wide_image(q, model, ip + (size_t)img * q.m.P, img, targets + (size_t)img * N, loss->kind, s))) return rc;
+        if (hipMemcpyAsync(icnn_grads + (size_t)img * q.m.P, q.w.grads, sizeof(float) * q.m.P, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
+        if (hipMemcpyAsync(loss_out + img, q.w.grads + q.m.P, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
+    }
+    launch_rnvp_bwd(q.p, fp, grid, n_images, s);
+    launch_rnvp_grads(q.p, n_images, const_cast<float*>(fp), flow_grads, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+// One optimizer step: RealNVP forward (all images) | per image: wide_forward, dL/dlogits, wide_backward with dcoords = dxd,
+// icnn_update_kernel on the one-slab view (it writes the next learning rate and the "frozen" flag into the image's header) |
+// the RealNVP's backward seeded from dxd | its update, which reads this step's learning rate and the flag from the ICNN headers.
+static int pcn_wide_fit(const InrModelDesc* model, const InrRnvpDesc* r, float* ip, float* fp, float* iopt, float* fopt,
+                        const InrGridDesc* grid, const float* targets, const InrLossDesc* loss, const InrOptDesc* opt, float wd_flow,
+                        int n_images, int steps, int step0, float* loss_hist, float* final_logits, int32_t* status, void* workspace,
+                        int64_t workspace_bytes, hipStream_t s) {
+    PcnWideWs q;
+    int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
+    if (rc) return rc;
+    const WideMap& m = q.m;
+    const long long N = grid->n_points;
+    const long long ost = 2 * (long long)m.P + INR_OPT_HEADER_FLOATS;
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, q.coef, 1.f);
+    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, iopt, m.P, *opt, step0);
+    if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
+    UpdArgs u{};   // the one-"slab" view of the gradient vector (wide_fit)
+    u.img.identity = 1;
+    u.img.H = m.h; u.img.C = m.C; u.img.L = m.L; u.img.P = m.P; u.img.sl_cols = m.P + 1;
+    u.opt = *opt;
+    u.P = u.Pu = m.P;
+    u.hu = m.h;
+    u.PS = (m.P + 1 + 31) / 32 * 32;
+    u.wgs = 1;
+    u.n_images = 1;
+    u.hist_stride = steps;
+    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
+    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
+    u.slabs = q.w.grads;
+    for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = u.freeze_lo[k] = u.freeze_hi[k] = 0;
+    for (int k = 0; k < m.L; ++k) {
+        u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.kin(k);
+        u.freeze_lo[k] = m.p_s(k); u.freeze_hi[k] = m.p_s(k) + m.h * m.C;
+    }
+    u.clamp_lo[UPD_RANGES - 1] = m.p_wo(); u.clamp_hi[UPD_RANGES - 1] = m.p_wo() + m.O * m.hl();
+    u.freeze_lo[UPD_RANGES - 1] = m.p_so(); u.freeze_hi[UPD_RANGES - 1] = m.p_so() + m.O * m.C;
+    u.input_hi = m.p_w(0);
+    const dim3 ugrid = upd_grid(m.P + 1, 1), ublock = upd_block(m.P + 1);
+    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
+    for (int it = 0; it < steps; ++it) {
+        set_step_consts(u, opt, step0 + it + 1, it);
+        launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, true, s, false, it > 0);   // (it > 0: the update refreshed the packed image)
+        for (int img = 0; img < n_images; ++img) {
+            float* p = ip + (size_t)img * m.P;
+            if ((rc = pcn_wide_image(q, model, p, img, targets + (size_t)img * N, loss->kind, s))) return rc;
+            if (gate_logits && it == steps - 1 &&
+                hipMemcpyAsync(final_logits + (size_t)img * N, q.logit, sizeof(float) * N, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return INR_ELAUNCH;
+            u.params = p;
+            u.opt_state = iopt + (size_t)img * ost;
+            u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps : nullptr;
+            u.status = status ? status + img : nullptr;
+            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
+        }
+        launch_rnvp_bwd(q.p, fp, grid, n_images, s);
+        RnvpUpdArgs ru = make_rnvp_upd_args(q.p, n_images, 0, fp, fopt, nullptr, opt, wd_flow, u.t, iopt + 2 * (size_t)m.P, ost, status);
+        ru.RE = q.p.RE;   // the next step's forward reuses it
+        launch_rnvp_update_args(q.p, n_images, ru, s);
+    }
+    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
+    if (final_logits && !gate_logits) {
+        launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, false, s);
+        for (int img = 0; img < n_images; ++img)
+            if ((rc = wide_forward(m, q.w, model, ip + (size_t)img * m.P, &q.p.dgrid, img, nullptr, 0, false, final_logits + (size_t)img * N, s)))
+                return rc;
+    }
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+}  // namespace
+
 extern "C" {
 
 int inrfit_forward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
@@ -2494,6 +2723,8 @@ int inrfit_pcn_forward(const InrModelDesc* model, const InrRnvpDesc* rnvp, const
                        const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
                        void* stream) {
     if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
+    if (pcn_wide_shape(model))
+        return pcn_wide_forward(model, rnvp, icnn_params, flow_params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
     return forward_run(PcnStep(rnvp, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
                        (hipStream_t)stream);
 }
@@ -2525,6 +2756,9 @@ int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, con
                          int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
     if (const int rc = check_loss(loss)) return rc;
+    if (pcn_wide_shape(model))
+        return pcn_wide_loss_grad(model, rnvp, icnn_params, flow_params, grid, targets, loss, n_images, loss_out, icnn_grads, flow_grads,
+                                  workspace, workspace_bytes, (hipStream_t)stream);
     return loss_grad_run(PcnStep(rnvp, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images, loss_out,
                          icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2561,6 +2795,10 @@ int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* ic
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
         return INR_EINVAL;
     if (const int rc = check_fit(opt, loss, false)) return rc;
+    if (pcn_wide_shape(model))
+        return pcn_wide_fit(model, rnvp, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, targets, loss, opt,
+                            flow_weight_decay, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
+                            (hipStream_t)stream);
     return fit_run(PcnStep(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params, icnn_opt_state, grid,
                    targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
                    (hipStream_t)stream);

@@ -633,8 +633,16 @@ __device__ __forceinline__ void rnvp_flow_backward_m(const RnvpBwdArgs& a, const
     }
 }
 
-template <int C, int Q, int U = 1>
-__global__ __launch_bounds__(256) void rnvp_bwd_points_kernel(const RnvpBwdArgs a) {
+// inrfit_rnvp_backward's instantiations take RnvpBwdDinArgs: the walk is seeded by the caller (dxd) and its tail also carries the
+// gradient through MinMax.transform and the 1x1 linear to the input coordinates, din = g (nmax - nmin)/(max - min) a.  The fit's
+// instantiations (Args = RnvpBwdArgs) compile to the code they had before the parameter existed.
+struct RnvpBwdDinArgs : RnvpBwdArgs {
+    float* din;   // [n_images][C][N]
+};
+
+template <int C, int Q, int U = 1, class Args = RnvpBwdArgs>
+__global__ __launch_bounds__(256) void rnvp_bwd_points_kernel(const Args a) {
+    constexpr bool DIN = std::is_same<Args, RnvpBwdDinArgs>::value;
     const int img = blockIdx.y;
     const int N = (int)a.N, F = a.m.F;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -705,6 +713,9 @@ __global__ __launch_bounds__(256) void rnvp_bwd_points_kernel(const RnvpBwdArgs 
                 const float gv = g[q][c] * (a.m.nmax - a.m.nmin) / (a.m.vmax[c] - a.m.vmin[c]);
                 da[c] += gv * x[c];
                 db[c] += gv;
+                if constexpr (DIN) {
+                    if (valid[q]) a.din[((size_t)img * C + c) * N + p[q]] = gv * img_rec.f(c);
+                }
             }
         }
 #pragma unroll

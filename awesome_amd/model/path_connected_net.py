@@ -173,6 +173,33 @@ class _PcnFunction(torch.autograd.Function):
         return (None, None, None, None, *outs)
 
 
+class _RnvpFunction(torch.autograd.Function):
+    """deformed coordinates (C, N) = flow_net(linear(coords)) on the HIP path; backward = `inrfit_rnvp_backward`: gradients w.r.t. the
+    flow parameters, the 1x1 linear and the input coordinates for a given d loss / d deformed coordinates."""
+
+    @staticmethod
+    def forward(ctx, coords: torch.Tensor, rspec, *params: torch.Tensor):
+        fp = torch.cat([p.reshape(-1) for p in params]).to(torch.float32)[None].contiguous()
+        grid = K.Grid.explicit(coords)
+        ctx.rspec, ctx.grid = rspec, grid
+        ctx.shapes = [p.shape for p in params]
+        ctx.save_for_backward(fp)
+        return R.rnvp_forward(rspec, fp, grid)[0]
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        (fp,) = ctx.saved_tensors
+        want_x = ctx.needs_input_grad[0]
+        res = R.rnvp_backward(ctx.rspec, fp, ctx.grid, dout.contiguous()[None], want_dcoords=want_x)
+        gf, dx = (res[0], res[1][0]) if want_x else (res, None)
+        outs, off = [], 0
+        for shp in ctx.shapes:
+            n = math.prod(shp) if len(shp) else 1
+            outs.append(gf[0, off:off + n].reshape(shp))
+            off += n
+        return (dx, None, *outs)
+
+
 class PathConnectedNet(nn.Module, PriorFitMixin):
     """convex_net(flow_net(linear(x)))  (path_connected_net.py:53-85).  `pretrain` / `pretrain_load_state`: PriorFitMixin
     (the reference's :472-509, 730-1019 on `inrfit_pcn_fit`)."""
@@ -414,13 +441,18 @@ class PathConnectedNet(nn.Module, PriorFitMixin):
             return torch.stack([run(p).reshape(1, h, w) for p in planes], 0)
         return run(planes[0])[:, None]
 
-    def get_deformation(self, x: torch.Tensor) -> torch.Tensor:
-        """path_connected_net.py:124-128: flow_net(linear(x)) in the layout of x (no autograd)."""
+    def get_deformation(self, x: torch.Tensor, differentiable: bool = False) -> torch.Tensor:
+        """path_connected_net.py:124-128: flow_net(linear(x)) in the layout of x.  By default without autograd; with
+        `differentiable` the result carries a grad_fn (`inrfit_rnvp_forward` / `inrfit_rnvp_backward`): gradients reach the flow
+        parameters, the 1x1 linear and x."""
         planes, bhw = self._planar(x)
-        self._actnorm_init_if_needed(torch.cat(planes, dim=1))
+        self._actnorm_init_if_needed(torch.cat(planes, dim=1).detach())
         _, rspec, _, flow = self._ordered_params()
-        fp = self._flat(flow)
-        outs = [R.rnvp_forward(rspec, fp, K.Grid.explicit(p))[0] for p in planes]
+        if differentiable:
+            outs = [_RnvpFunction.apply(p.contiguous(), rspec, *flow) for p in planes]
+        else:
+            fp = self._flat(flow)
+            outs = [R.rnvp_forward(rspec, fp, K.Grid.explicit(p))[0] for p in planes]
         if bhw is not None:
             b, h, w = bhw
             return torch.stack([o.reshape(-1, h, w) for o in outs], 0)

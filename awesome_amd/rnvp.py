@@ -1,6 +1,7 @@
 """Host-side driver of the HIP RealNVP kernels and of the fused PathConnectedNet fit (include/inrfit.h, InrRnvpDesc part).
 
   rnvp_forward  <- PathConnectedNet.get_deformation                 (awesome/model/path_connected_net.py:124-128)
+  rnvp_backward <- its autograd backward (get_deformation(differentiable=True))
   pcn_forward   <- PathConnectedNet.forward                         (:79-85)
   pcn_loss_grad <- criterion(sigmoid(model(grid)), unaries).backward()  w.r.t. every parameter
   pcn_fit       <- the inner loop of _prior_based_pretrain          (:937-962, Adamax + param groups :922-929)
@@ -164,6 +165,24 @@ def rnvp_forward(rspec: RnvpSpec, flow_params: Tensor, grid: K.Grid) -> Tensor:
                                       K._stream_ptr(fp.device))
     L.check(rc, "inrfit_rnvp_forward")
     return out
+
+
+def rnvp_backward(rspec: RnvpSpec, flow_params: Tensor, grid: K.Grid, dout: Tensor, want_dcoords: bool = False):
+    """The vector-Jacobian product of rnvp_forward: dout [n_images, C, N] (d loss / d deformed coordinates) -> flow gradients
+    [n_images, RP] in the flat layout (linear.weight / linear.bias included); with want_dcoords also d loss / d input coordinates
+    [n_images, C, N].  Returns flow_grads or (flow_grads, dcoords)."""
+    fp = K._check_dev(flow_params, "flow_params")
+    n = fp.shape[0]
+    dout = K._check_dev(dout, "dout").reshape(n, rspec.channels, grid.n_points)
+    gf = L.scratch_like(fp)
+    din = L.scratch(n, rspec.channels, grid.n_points, dtype=torch.float32, device=fp.device) if want_dcoords else None
+    ws = _ws(None, rspec, grid, n)
+    rd, gd = rspec.desc(), grid.desc()
+    rc = L.load().inrfit_rnvp_backward(C.byref(rd), fp.data_ptr(), C.byref(gd), dout.data_ptr(), n, gf.data_ptr(),
+                                       din.data_ptr() if din is not None else None, ws.data_ptr(), ws.numel() * 4,
+                                       K._stream_ptr(fp.device))
+    L.check(rc, "inrfit_rnvp_backward")
+    return (gf, din) if want_dcoords else gf
 
 
 def rnvp_inverse(rspec: RnvpSpec, flow_params: Tensor, coords: Tensor) -> Tensor:

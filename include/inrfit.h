@@ -293,6 +293,13 @@ int inrfit_rnvp_actnorm_init(const InrRnvpDesc* rnvp, float* flow_params, const 
 /* out_coords[n_images][C][n_points]: PathConnectedNet.get_deformation (path_connected_net.py:124-128). */
 int inrfit_rnvp_forward(const InrRnvpDesc* rnvp, const float* flow_params, const InrGridDesc* grid, int n_images,
                         float* out_coords, void* workspace, int64_t workspace_bytes, void* stream);
+/* The vector-Jacobian product of inrfit_rnvp_forward (the forward is recomputed inside, as inrfit_backward does for the ICNN):
+ * dout_coords [n_images][C][n_points], planar like out_coords -> flow_grads [n_images][RP] in the flat flow layout (linear.weight /
+ * linear.bias included) and, when din_coords is not NULL, d / d input coordinates [n_images][C][n_points] (through MinMax and the
+ * 1x1 linear).  With inrfit_backward(dcoords) this is the autograd bridge of get_deformation -> ConvexNextNet compositions.
+ * Workspace: inrfit_pcn_workspace_bytes(NULL, rnvp, grid, n_images). */
+int inrfit_rnvp_backward(const InrRnvpDesc* rnvp, const float* flow_params, const InrGridDesc* grid, const float* dout_coords,
+                         int n_images, float* flow_grads, float* din_coords, void* workspace, int64_t workspace_bytes, void* stream);
 /* out_coords[n_images][C][n_points] = linear^-1(flow_net^-1(in_coords)): PathConnectedNet.inverse (path_connected_net.py:87-122).
  * in_coords is channel-planar [C][n_points] per image; in_image_stride (floats) = 0 shares one input among all images. */
 int inrfit_rnvp_inverse(const InrRnvpDesc* rnvp, const float* flow_params, const float* in_coords, int64_t in_image_stride,
@@ -303,7 +310,13 @@ int inrfit_rnvp_inverse(const InrRnvpDesc* rnvp, const float* flow_params, const
 int inrfit_rnvp_fit_identity(const InrRnvpDesc* rnvp, float* flow_params, float* flow_opt_state, const InrGridDesc* grid,
                              const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist, void* workspace,
                              int64_t workspace_bytes, void* stream);
-/* logits[n_images][n_points]: PathConnectedNet.forward (:79-85). */
+/* logits[n_images][n_points]: PathConnectedNet.forward (:79-85).
+ * ICNN shapes of inrfit_pcn_forward / _loss_grad / _fit / _workspace_bytes: every shape with a fused kernel, and every ICNN-form
+ * shape of the layer-by-layer path (n_hidden > 130 or more than two hidden layers; relu layer 0, one output, n_features = n_hidden):
+ * there one optimizer step is the RealNVP forward, the layer-by-layer forward / backward on the deformed coordinates (which also
+ * returns dL/dcoords), the ICNN update, the RealNVP backward seeded from dL/dcoords and the RealNVP update - all on the stream, same
+ * semantics (one learning rate from the ICNN header, a non-finite loss freezes both halves of the image).  The encode shapes and
+ * n_hidden > 1024 stay INR_EUNSUPPORTED; inrfit_pcn_joint_step takes the fused shapes only. */
 int inrfit_pcn_forward(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params, const float* flow_params,
                        const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
                        void* stream);
