@@ -179,6 +179,19 @@ EXPORTS = {
                                         C.POINTER(InrGridDesc), C.c_void_p, C.c_void_p, C.POINTER(InrJointLossDesc),
                                         C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_wide_joint_step_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrGridDesc)]),
+    "inrfit_pcn_wide_joint_step_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrRnvpDesc),
+                                                               C.POINTER(InrGridDesc)]),
+    "inrfit_wide_joint_step": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p,
+                                         C.c_void_p, C.POINTER(InrJointLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_wide_joint_prior_step": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p,
+                                               C.c_void_p, C.POINTER(InrJointPriorDesc), C.c_void_p, C.POINTER(InrOptDesc), C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_pcn_wide_joint_step": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrRnvpDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p, C.c_void_p,
+                                             C.POINTER(InrJointLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_star_param_count": (C.c_int64, [C.POINTER(InrStarDesc)]),
     "inrfit_star_workspace_bytes": (C.c_int64, [C.POINTER(InrStarDesc), C.c_int64]),
     "inrfit_star_forward": (C.c_int, [C.POINTER(InrStarDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,

@@ -129,6 +129,12 @@ def _normalise_item(inputs: Sequence[Any], input_mode: str = "image", prior_arg_
     return xi, ai, xi.shape[-2] * xi.shape[-1], False
 
 
+def _layer_by_layer_joint(ispec) -> bool:
+    """An ICNN shape the layer-by-layer joint steps take (inrfit_wide_joint_step and its kin): the library serves it, it has no
+    fused kernel, and it is an ICNN-form shape (relu layer 0, one output, n_features = n_hidden) - not an encode net's."""
+    return ispec.supported() and not ispec.fused() and not ispec.general and ispec.act0 == "relu"
+
+
 def _prior_grid(prior_args, pixel: bool):
     """The prior's coordinates (WrapperModule.get_prior_args) as the kernels' explicit grid, (2, n) float32."""
     from . import icnn as K
@@ -215,6 +221,9 @@ class JointTrainer:
                       the image's bank row, sigmoid, the composite loss, d loss / d seg, the prior's backward, Adam / Adamax and
                       enforce_convexity in place: inrfit_joint_step / inrfit_pcn_joint_step / inrfit_cdn_joint_step
                       (awesome_amd.joint); seg.backward(dseg)
+                      (an ICNN of the layer-by-layer path - n_hidden > 130 or more than two hidden layers - alone or behind a
+                      PathConnectedNet's RealNVP: only under `fused_layer_by_layer`, then inrfit_wide_joint_step /
+                      inrfit_pcn_wide_joint_step, and inrfit_wide_joint_prior_step on the `convexity` route; else `autograd`)
                else   `convexity` where that applies and the criterion has no such desc; `autograd` for everything else it
                       refuses: batch > 1, the step that initialises ActNorm
     convexity  takes  (`fused_convexity_losses`) AwesomeImageLoss, AwesomeImageLossJoint, AwesomeLoss, AwesomeLossJoint on an ICNN
@@ -247,7 +256,8 @@ class JointTrainer:
 
     def __init__(self, wrapper: torch.nn.Module, bank: PriorBank, criterion: Callable, optimizer: torch.optim.Optimizer,
                  fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch",
-                 fused_extra_penalty: bool = False, fused_convexity_losses: bool = False, fused_segmentation: bool = False):
+                 fused_extra_penalty: bool = False, fused_convexity_losses: bool = False, fused_segmentation: bool = False,
+                 fused_layer_by_layer: bool = False):
         if fused_segmentation and not fused_convexity_losses:
             raise ValueError("fused_segmentation runs inside the convexity losses' fused step: it needs fused_convexity_losses=True")
         if check_finite not in ("step", "epoch"):
@@ -260,6 +270,7 @@ class JointTrainer:
         self.fused_extra_penalty = bool(fused_extra_penalty)
         self.fused_convexity_losses = bool(fused_convexity_losses)
         self.fused_segmentation = bool(fused_segmentation)
+        self.fused_layer_by_layer = bool(fused_layer_by_layer)
         # (both names date from the CNNNet share; they serve the FCNet share, inrfit_fcseg_step, as well)
         self._cnn_grads: Optional[torch.Tensor] = None     # the segmentation network's flat gradient (fused_segmentation)
         self.cnnseg_status: Optional[torch.Tensor] = None   # status word of the last inrfit_cnnseg_step / inrfit_fcseg_step
@@ -355,14 +366,20 @@ class JointTrainer:
                 ispec, dspec = prior._specs()
             except NotImplementedError:   # no fused form of this composite at all ('resnet' flow backbone): autograd step
                 return None
-            if not ispec.fused():         # its ICNN runs layer by layer: the composite's autograd bridges, no fused joint step
-                return None
             family = "pcn" if type(dspec).__name__ == "RnvpSpec" else "cdn"
+            wide = not ispec.fused()
+            # its ICNN runs layer by layer: the composite's autograd bridges - unless asked for (fused_layer_by_layer) and the
+            # composite is a PathConnectedNet (inrfit_pcn_wide_joint_step; ConvexDiffeomorphismNet has no such step)
+            if wide and not (self.fused_layer_by_layer and family == "pcn" and _layer_by_layer_joint(ispec)):
+                return None
             if kind != "adam" and family == "cdn":
                 return None
         elif hasattr(prior, "spec"):
             ispec, dspec, family = prior.spec, None, "icnn"
-            if not ispec.fused():   # n_hidden > 130 or L > 2: inrfit_joint_step has no kernel (INR_EUNSUPPORTED); autograd step
+            wide = not ispec.fused()
+            # n_hidden > 130 or L > 2: inrfit_joint_step has no kernel (INR_EUNSUPPORTED); autograd step - unless asked
+            # for (fused_layer_by_layer: inrfit_wide_joint_step / inrfit_wide_joint_prior_step)
+            if wide and not (self.fused_layer_by_layer and _layer_by_layer_joint(ispec)):
                 return None
             if getattr(prior, "fit_options", None):   # FCNet / encode nets: frozen ranges, no clamp - not part of the joint configs
                 return None
@@ -371,7 +388,7 @@ class JointTrainer:
         if not hasattr(self.criterion, "joint_desc") or self.criterion.joint_desc() is None:
             if not self._convexity_applies(family):
                 return None
-        return dict(kind=kind, group=groups[0], family=family, ispec=ispec, dspec=dspec)
+        return dict(kind=kind, group=groups[0], family=family, ispec=ispec, dspec=dspec, wide=wide)
 
     def _convexity_applies(self, family: str) -> bool:
         """fused_convexity_losses: one of the convexity benchmark's losses on an ICNN prior (inrfit_joint_prior_step)."""
@@ -451,12 +468,14 @@ class JointTrainer:
         segd = seg.detach().reshape(-1).to(torch.float32).contiguous()
         tgt = labels.detach().reshape(-1).to(torch.float32).contiguous()
         if plan["family"] == "icnn":
-            res = J.joint_step(plan["ispec"], row, iopt, grid, segd, tgt, desc, step=t, optimizer=plan["kind"], clamp=True, **hp)
+            step_fn = J.wide_joint_step if plan["wide"] else J.joint_step
+            res = step_fn(plan["ispec"], row, iopt, grid, segd, tgt, desc, step=t, optimizer=plan["kind"], clamp=True, **hp)
         else:
             del hp["weight_decay"]      # zero (_joint_desc_fusable): torch would also apply it to their 1x1 / linear layer
             if plan["family"] == "pcn":
-                res = J.pcn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
-                                       step=t, optimizer=plan["kind"], flow_weight_decay=0.0, **hp)
+                step_fn = J.pcn_wide_joint_step if plan["wide"] else J.pcn_joint_step
+                res = step_fn(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
+                              step=t, optimizer=plan["kind"], flow_weight_decay=0.0, **hp)
             else:
                 res = J.cdn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
                                        step=t, weight_decay_on_weight_g=0.0, **hp)
@@ -503,8 +522,9 @@ class JointTrainer:
         segd = seg.detach().reshape(-1).to(torch.float32).contiguous()
         tgt = labels.detach().reshape(-1).to(torch.float32).contiguous()
         st = seg_term.detach().reshape(1).to(torch.float32).contiguous()
-        res = J.joint_prior_step(plan["ispec"], row, iopt, grid, segd, tgt, form.prior_desc(), step=t, seg_term=st,
-                                 optimizer=plan["kind"], clamp=True, **hp)
+        step_fn = J.wide_joint_prior_step if plan["wide"] else J.joint_prior_step
+        res = step_fn(plan["ispec"], row, iopt, grid, segd, tgt, form.prior_desc(), step=t, seg_term=st,
+                      optimizer=plan["kind"], clamp=True, **hp)
         self._latch(res)
         dseg = res.dseg if form.align_rule == L.ALIGN_SOFT else None          # hard / none: d(prior's share) / d seg = 0
         share.backward(seg, seg_term, dseg, self._check_finite)

@@ -1194,6 +1194,37 @@ static int wide_loss_grad_all(const InrModelDesc* model, const float* params, co
     return INR_OK;
 }
 
+// the optimizer step of the layer-by-layer path = icnn_update_kernel on a one-"slab" view of the gradient vector (column = parameter,
+// column P = the loss): the arguments every such loop shares (params, opt_state, loss_hist and status are set per image; t, the bias
+// corrections and hist_idx per step)
+static UpdArgs wide_upd_args(const WideMap& m, const float* grads, const InrOptDesc* opt, int steps) {
+    UpdArgs u{};
+    u.img.identity = 1;
+    u.img.H = m.h; u.img.C = m.C; u.img.L = m.L; u.img.P = m.P; u.img.sl_cols = m.P + 1;
+    u.opt = *opt;
+    u.P = u.Pu = m.P;
+    u.hu = m.h;
+    u.PS = (m.P + 1 + 31) / 32 * 32;
+    u.wgs = 1;
+    u.n_images = 1;
+    u.hist_stride = steps;
+    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
+    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
+    u.slabs = grads;
+    for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = u.freeze_lo[k] = u.freeze_hi[k] = 0;
+    for (int k = 0; k < m.L; ++k) {
+        u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.kin(k);
+        u.freeze_lo[k] = m.p_s(k); u.freeze_hi[k] = m.p_s(k) + m.h * m.C;
+    }
+    u.clamp_lo[UPD_RANGES - 1] = m.p_wo(); u.clamp_hi[UPD_RANGES - 1] = m.p_wo() + m.O * m.hl();
+    u.freeze_lo[UPD_RANGES - 1] = m.p_so(); u.freeze_hi[UPD_RANGES - 1] = m.p_so() + m.O * m.C;
+    u.input_hi = m.p_w(0);   // input.weight | input.bias (L = 0: everything in front of the output layer)
+    return u;
+}
+static void launch_wide_update(const WideMap& m, const UpdArgs& u, hipStream_t s) {
+    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(m.P + 1, 1), upd_block(m.P + 1), 0, s, u);
+}
+
 static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
                     const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist,
                     float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
@@ -1207,30 +1238,8 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
     hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef, 1.f);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, m.P, *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    // the optimizer step = icnn_update_kernel on a one-"slab" view of the gradient vector (column = parameter, column P = the loss)
-    UpdArgs u{};
-    u.img.identity = 1;
-    u.img.H = m.h; u.img.C = m.C; u.img.L = m.L; u.img.P = m.P; u.img.sl_cols = m.P + 1;
-    u.opt = *opt;
-    u.P = u.Pu = m.P;
-    u.hu = m.h;
-    u.PS = (m.P + 1 + 31) / 32 * 32;
-    u.wgs = 1;
-    u.n_images = 1;
-    u.hist_stride = steps;
-    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
-    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
-    u.slabs = w.grads;
-    for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = u.freeze_lo[k] = u.freeze_hi[k] = 0;
-    for (int k = 0; k < m.L; ++k) {
-        u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.kin(k);
-        u.freeze_lo[k] = m.p_s(k); u.freeze_hi[k] = m.p_s(k) + m.h * m.C;
-    }
-    u.clamp_lo[UPD_RANGES - 1] = m.p_wo(); u.clamp_hi[UPD_RANGES - 1] = m.p_wo() + m.O * m.hl();
-    u.freeze_lo[UPD_RANGES - 1] = m.p_so(); u.freeze_hi[UPD_RANGES - 1] = m.p_so() + m.O * m.C;
-    u.input_hi = m.p_w(0);   // input.weight | input.bias (L = 0: everything in front of the output layer)
+    UpdArgs u = wide_upd_args(m, w.grads, opt, steps);
     const bool need_dz0 = !(m.general() && opt->freeze_input);   // frozen features: dZ_0 has no use
-    const dim3 ugrid = upd_grid(m.P + 1, 1), ublock = upd_block(m.P + 1);
     const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
     for (int it = 0; it < steps; ++it) {
         set_step_consts(u, opt, step0 + it + 1, it);
@@ -1244,7 +1253,7 @@ static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, 
             u.opt_state = opt_state + (size_t)img * (2 * (size_t)m.P + INR_OPT_HEADER_FLOATS);
             u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps : nullptr;
             u.status = status ? status + img : nullptr;
-            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
+            launch_wide_update(m, u, s);
         }
     }
     if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
@@ -2262,14 +2271,20 @@ struct JointCtx {
     float c_align;
 };
 
-int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float* seg, const float* target, long long N, int step,
-                float* prior_logits, float* jws, float* icnn_hdr, float* coef, hipStream_t s, JointCtx* c) {
-    int rc = check_joint_desc(desc);
-    if (rc) return rc;
+// the loss, optimizer and step arguments of a joint step
+int check_joint_step(const InrJointLossDesc* desc, const InrOptDesc* opt, int step) {
+    if (const int rc = check_joint_desc(desc)) return rc;
     if (!opt || (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) || step < 1) return INR_EINVAL;
     if (desc->form == INR_JOINT_AWESOME_PIXEL) return INR_EUNSUPPORTED;            // pixel mode has no dense-grid prior pass
     // the AWESOME_IMAGE prior term runs inside the step kernel, which reads unaries (fg < 0.5) and has no pixel mask
     if (desc->form == INR_JOINT_AWESOME_IMAGE && (desc->target_rule != 0 || desc->use_noneclass)) return INR_EUNSUPPORTED;
+    return INR_OK;
+}
+
+int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float* seg, const float* target, long long N, int step,
+                float* prior_logits, float* jws, float* icnn_hdr, float* coef, hipStream_t s, JointCtx* c) {
+    int rc = check_joint_step(desc, opt, step);
+    if (rc) return rc;
     // seg-side sums over the single image: output = seg (channel stride unused), PRIOR = false
     if ((rc = make_joint_args(seg, target, 1, N, desc, nullptr, jws, &c->jl))) return rc;
     c->gscale = c->jl.res + JL_RES;
@@ -2296,17 +2311,21 @@ int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float
     return INR_OK;
 }
 
-static void joint_finish(const JointCtx& c, const KernelEntry* e, const Workspace& w, float* loss_out, hipStream_t s) {
+// the prior's loss column: the step kernel's gradient slabs, or the layer-by-layer path's one-slab gradient vector (wgs = 1, loss_col = P)
+static void joint_finish(const JointCtx& c, const float* slabs, int wgs, int PS, int loss_col, float* loss_out, hipStream_t s) {
     JointFinArgs f{};
     f.jl = c.jl;
-    f.slabs = w.slabs;
-    f.wgs = w.wgs;
-    f.PS = w.PS;
-    f.loss_col = e->img.sl_cols - 1;
+    f.slabs = slabs;
+    f.wgs = wgs;
+    f.PS = PS;
+    f.loss_col = loss_col;
     f.gscale = c.gscale;
     f.loss_out = loss_out;
     if (c.align_seg) hipLaunchKernelGGL(joint_align_partial_kernel, dim3(c.jl.blocks), dim3(256), 0, s, c.jl, (const float*)c.logits);
     hipLaunchKernelGGL(joint_step_finish_kernel, dim3(1), dim3(256), 0, s, f);
+}
+static void joint_finish(const JointCtx& c, const KernelEntry* e, const Workspace& w, float* loss_out, hipStream_t s) {
+    joint_finish(c, w.slabs, w.wgs, w.PS, e->img.sl_cols - 1, loss_out, s);
 }
 
 static void joint_dseg(const JointCtx& c, float* dseg, hipStream_t s) {
@@ -2553,43 +2572,35 @@ int joint_step_run(D d, const InrModelDesc* model, float* params, float* opt_sta
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// dL/dlogit of the data term from the logits wide_out_kernel wrote (the same expressions as its own dy, which it keeps in registers):
-// what wide_dx_kernel starts dL/dcoords from (s_o dL/dlogit)
+// dL/dlogit of the data term from the logits wide_out_kernel wrote (wide_data_term, the expressions of its own dy, which it keeps in
+// registers): what wide_dx_kernel starts dL/dcoords from (s_o dL/dlogit).  JOINT: the data term of a joint step.
+template <bool JOINT>
 __global__ __launch_bounds__(256) void pcn_wide_dy_kernel(const float* __restrict__ logit, const float* __restrict__ target,
                                                           const float* __restrict__ coef, int loss_kind, long long N,
-                                                          float* __restrict__ dy) {
+                                                          float* __restrict__ dy, const WideJoint jn) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= N) return;
-    const float y = logit[p], tg = target[p];
-    const float pr = 1.f / (1.f + expf(-y));
-    const float cw = tg < 0.5f ? coef[0] : coef[1];
-    float d;
-    if (loss_kind == INR_LOSS_SE) {
-        d = 2.f * (pr - tg) * pr * (1.f - pr) * cw;
-    } else {
-        const float pq = pr * (1.f - pr);
-        d = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
-    }
+    float l = 0.f, d = 0.f;
+    wide_data_term<JOINT>(target, coef, loss_kind, jn, p, logit[p], l, d);
     dy[p] = d;
 }
 
 static int check_pcn_wide(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* workspace,
-                          int64_t workspace_bytes, PcnWideWs* q) {
+                          int64_t workspace_bytes, PcnWideWs* q) {   // arguments only: rnvp_set_lds() is the caller's next step
     if (!rnvp_ok(r)) return INR_EUNSUPPORTED;
     if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
     if (model->in_features != r->channels) return INR_EINVAL;
     if (!workspace || !grid_ok(grid, n_images, 0x7fffffffLL / WIDE_MAX_HIDDEN * 64)) return INR_EINVAL;
     if (grid->mode == INR_GRID_SEPARABLE && r->channels == 3 && !grid->ts) return INR_EINVAL;   // the separable grid's t axis
     *q = carve_pcn_wide(model, r, grid, n_images, workspace);
-    if (workspace_bytes < q->bytes) return INR_EWORKSPACE;
-    return rnvp_set_lds();
+    return workspace_bytes < q->bytes ? INR_EWORKSPACE : INR_OK;
 }
 
 static int pcn_wide_forward(const InrModelDesc* model, const InrRnvpDesc* r, const float* ip, const float* fp, const InrGridDesc* grid,
                             int n_images, float* logits, void* workspace, int64_t workspace_bytes, hipStream_t s) {
     PcnWideWs q;
     int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
-    if (rc) return rc;
+    if (rc || (rc = rnvp_set_lds())) return rc;
     launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, false, s);
     for (int img = 0; img < n_images; ++img)
         if ((rc = wide_forward(q.m, q.w, model, ip + (size_t)img * q.m.P, &q.p.dgrid, img, nullptr, 0, false,
@@ -2599,16 +2610,21 @@ static int pcn_wide_forward(const InrModelDesc* model, const InrRnvpDesc* r, con
 }
 
 // forward + backward of image `img` on the deformed grid: gradients and the loss into q.w.grads, dL/dxd into q.p.dxd
+// `logits` [N]: where the output pass leaves them (q.logit, or the caller's); `jn`: the data term of a joint step, or null
 static int pcn_wide_image(PcnWideWs& q, const InrModelDesc* model, const float* p, int img, const float* target, int loss_kind,
-                          hipStream_t s) {
+                          float* logits, const WideJoint* jn, hipStream_t s) {
     const long long N = q.p.dgrid.n_points;
     const bool ext = loss_kind == INR_LOSS_EXTERNAL;
     q.w.coef = q.coef + 2 * img;
-    int rc = wide_forward(q.m, q.w, model, p, &q.p.dgrid, img, target, loss_kind, true, ext ? nullptr : q.logit, s);
+    int rc = wide_forward(q.m, q.w, model, p, &q.p.dgrid, img, target, loss_kind, true, ext ? nullptr : logits, s, jn);
     if (rc) return rc;
-    if (!ext)
-        hipLaunchKernelGGL(pcn_wide_dy_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const float*)q.logit, target,
-                           (const float*)q.w.coef, loss_kind, N, q.dy);
+    const dim3 dygrid((unsigned)((N + 255) / 256));
+    if (jn)
+        hipLaunchKernelGGL(pcn_wide_dy_kernel<true>, dygrid, dim3(256), 0, s, (const float*)logits, target, (const float*)q.w.coef, loss_kind, N,
+                           q.dy, *jn);
+    else if (!ext)
+        hipLaunchKernelGGL(pcn_wide_dy_kernel<false>, dygrid, dim3(256), 0, s, (const float*)logits, target, (const float*)q.w.coef, loss_kind,
+                           N, q.dy, WideJoint{});
     return wide_backward(q.m, q.w, model, p, N, s, ext ? target : q.dy, q.p.dxd + (size_t)img * q.m.C * N);
 }
 
@@ -2617,12 +2633,12 @@ static int pcn_wide_loss_grad(const InrModelDesc* model, const InrRnvpDesc* r, c
                               float* flow_grads, void* workspace, int64_t workspace_bytes, hipStream_t s) {
     PcnWideWs q;
     int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
-    if (rc) return rc;
+    if (rc || (rc = rnvp_set_lds())) return rc;
     const long long N = grid->n_points;
     launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, true, s);
     if (loss->kind != INR_LOSS_EXTERNAL) hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, q.coef, 1.f);
     for (int img = 0; img < n_images; ++img) {
-        if ((rc = pcn_wide_image(q, model, ip + (size_t)img * q.m.P, img, targets + (size_t)img * N, loss->kind, s))) return rc;
+        if ((rc = pcn_wide_image(q, model, ip + (size_t)img * q.m.P, img, targets + (size_t)img * N, loss->kind, q.logit, nullptr, s))) return rc;
         if (hipMemcpyAsync(icnn_grads + (size_t)img * q.m.P, q.w.grads, sizeof(float) * q.m.P, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
         if (hipMemcpyAsync(loss_out + img, q.w.grads + q.m.P, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
     }
@@ -2640,42 +2656,21 @@ static int pcn_wide_fit(const InrModelDesc* model, const InrRnvpDesc* r, float* 
                         int64_t workspace_bytes, hipStream_t s) {
     PcnWideWs q;
     int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
-    if (rc) return rc;
+    if (rc || (rc = rnvp_set_lds())) return rc;
     const WideMap& m = q.m;
     const long long N = grid->n_points;
     const long long ost = 2 * (long long)m.P + INR_OPT_HEADER_FLOATS;
     hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, q.coef, 1.f);
     hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, iopt, m.P, *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    UpdArgs u{};   // the one-"slab" view of the gradient vector (wide_fit)
-    u.img.identity = 1;
-    u.img.H = m.h; u.img.C = m.C; u.img.L = m.L; u.img.P = m.P; u.img.sl_cols = m.P + 1;
-    u.opt = *opt;
-    u.P = u.Pu = m.P;
-    u.hu = m.h;
-    u.PS = (m.P + 1 + 31) / 32 * 32;
-    u.wgs = 1;
-    u.n_images = 1;
-    u.hist_stride = steps;
-    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
-    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
-    u.slabs = q.w.grads;
-    for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = u.freeze_lo[k] = u.freeze_hi[k] = 0;
-    for (int k = 0; k < m.L; ++k) {
-        u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.kin(k);
-        u.freeze_lo[k] = m.p_s(k); u.freeze_hi[k] = m.p_s(k) + m.h * m.C;
-    }
-    u.clamp_lo[UPD_RANGES - 1] = m.p_wo(); u.clamp_hi[UPD_RANGES - 1] = m.p_wo() + m.O * m.hl();
-    u.freeze_lo[UPD_RANGES - 1] = m.p_so(); u.freeze_hi[UPD_RANGES - 1] = m.p_so() + m.O * m.C;
-    u.input_hi = m.p_w(0);
-    const dim3 ugrid = upd_grid(m.P + 1, 1), ublock = upd_block(m.P + 1);
+    UpdArgs u = wide_upd_args(m, q.w.grads, opt, steps);
     const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
     for (int it = 0; it < steps; ++it) {
         set_step_consts(u, opt, step0 + it + 1, it);
         launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, true, s, false, it > 0);   // (it > 0: the update refreshed the packed image)
         for (int img = 0; img < n_images; ++img) {
             float* p = ip + (size_t)img * m.P;
-            if ((rc = pcn_wide_image(q, model, p, img, targets + (size_t)img * N, loss->kind, s))) return rc;
+            if ((rc = pcn_wide_image(q, model, p, img, targets + (size_t)img * N, loss->kind, q.logit, nullptr, s))) return rc;
             if (gate_logits && it == steps - 1 &&
                 hipMemcpyAsync(final_logits + (size_t)img * N, q.logit, sizeof(float) * N, hipMemcpyDeviceToDevice, s) != hipSuccess)
                 return INR_ELAUNCH;
@@ -2683,7 +2678,7 @@ static int pcn_wide_fit(const InrModelDesc* model, const InrRnvpDesc* r, float* 
             u.opt_state = iopt + (size_t)img * ost;
             u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps : nullptr;
             u.status = status ? status + img : nullptr;
-            hipLaunchKernelGGL(icnn_update_kernel, ugrid, ublock, 0, s, u);
+            launch_wide_update(m, u, s);
         }
         launch_rnvp_bwd(q.p, fp, grid, n_images, s);
         RnvpUpdArgs ru = make_rnvp_upd_args(q.p, n_images, 0, fp, fopt, nullptr, opt, wd_flow, u.t, iopt + 2 * (size_t)m.P, ost, status);
@@ -2700,9 +2695,148 @@ static int pcn_wide_fit(const InrModelDesc* model, const InrRnvpDesc* r, float* 
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
+// ---- the fused joint step on the layer-by-layer path: joint_begin | (RealNVP forward) | wide_forward with the joint data term
+// (its loss column = the prior's whole share, with the UNCLIPPED coefficient) | wide_backward (-> dxd) | the finish kernel
+// (gscale) | icnn_update_kernel on the one-slab view x gscale | (RealNVP backward seeded from dxd, its update x gscale: this step's
+// learning rate and the frozen flag from the ICNN header) | d loss / d seg.  Nothing is read on the host.
+// A frozen step hands the backbone a zero gradient: d loss / d seg of a non-finite loss has no meaning, and the kernels that write it
+// (joint_loss_grad_kernel<true>, joint_prior_dseg_kernel) do not look at the status.  gscale is the finish kernel's: NaN = frozen.
+__global__ __launch_bounds__(256) void joint_dseg_gate_kernel(const float* __restrict__ gscale, long long N, float* __restrict__ dseg) {
+    if (isfinite(gscale[0])) return;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long long)gridDim.x * 256) dseg[e] = 0.f;
+}
+static void joint_dseg_gate(const float* gscale, long long N, float* dseg, int blocks, hipStream_t s) {
+    hipLaunchKernelGGL(joint_dseg_gate_kernel, dim3(blocks), dim3(256), 0, s, gscale, N, dseg);
+}
+
+static WideJoint wide_joint_of(const JointCtx& c, long long N) {
+    WideJoint j{};
+    j.seg = c.align_seg;   // AWESOME_IMAGE with the extra penalty: hard align over every point
+    j.c_align = c.c_align;
+    j.data_count = N;
+    return j;
+}
+
+// the ICNN update of a joint step on the one-slab view (joint_upd_args)
+static UpdArgs wide_joint_upd_args(const WideMap& m, const float* grads, float* params, float* opt_state, int32_t* status,
+                                   const InrOptDesc* opt, int step, const float* gscale) {
+    InrOptDesc o = *opt;
+    o.plateau = 0;
+    UpdArgs u = wide_upd_args(m, grads, &o, 1);
+    u.params = params;
+    u.opt_state = opt_state;
+    u.status = status;
+    u.gscale = gscale;
+    set_step_consts(u, &o, step);
+    return u;
+}
+
+// shape, grid and workspace of inrfit_wide_joint_step / inrfit_wide_joint_prior_step: the layer-by-layer workspace of one image, then
+// the joint step's (joint_ws_bytes) at *jws
+static int wide_joint_prepare(const InrModelDesc* model, const InrGridDesc* grid, void* workspace, int64_t workspace_bytes, WideMap* m,
+                              WideWs* w, float** jws) {
+    if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
+    float* coef;
+    if (const int rc = wide_prepare(model, grid, 1, workspace, workspace_bytes, m, w, &coef, nullptr)) return rc;
+    const long long wb = align256(wide_total_bytes(*m, grid->n_points, false, 1));
+    if (workspace_bytes < wb + joint_ws_bytes(grid->n_points)) return INR_EWORKSPACE;
+    w->coef = coef;
+    *jws = (float*)((char*)workspace + wb);
+    return INR_OK;
+}
+
+static int wide_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                           const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
+                           float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    WideMap m;
+    WideWs w;
+    float* jws;
+    int rc = wide_joint_prepare(model, grid, workspace, workspace_bytes, &m, &w, &jws);
+    if (rc) return rc;
+    const long long N = grid->n_points;
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    JointCtx c;
+    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, opt_state + 2 * (size_t)m.P, w.coef, s, &c))) return rc;
+    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
+    const WideJoint jn = wide_joint_of(c, N);
+    if ((rc = wide_forward(m, w, model, params, grid, 0, c.prior_targets, c.prior_loss.kind, true, logits, s, &jn))) return rc;
+    if ((rc = wide_backward(m, w, model, params, N, s))) return rc;
+    const UpdArgs u = wide_joint_upd_args(m, w.grads, params, opt_state, status, opt, step, c.gscale);
+    joint_finish(c, w.grads, 1, u.PS, m.P, loss_out, s);
+    launch_wide_update(m, u, s);
+    joint_dseg(c, dseg, s);
+    joint_dseg_gate(c.gscale, N, dseg, c.jl.blocks, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+static int pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* r, float* ip, float* fp, float* iopt, float* fopt,
+                               const InrGridDesc* grid, const float* seg, const float* target, const InrJointLossDesc* desc,
+                               const InrOptDesc* opt, float wd_flow, int step, float* loss_out, float* dseg, float* prior_logits,
+                               int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    PcnWideWs q;
+    int rc = check_pcn_wide(model, r, grid, 1, workspace, workspace_bytes, &q);
+    if (rc) return rc;
+    const WideMap& m = q.m;
+    const long long N = grid->n_points;
+    if (workspace_bytes < align256(q.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
+    if ((rc = check_joint_step(desc, opt, step))) return rc;
+    if ((rc = rnvp_set_lds())) return rc;   // (every argument first, then the device)
+    float* jws = (float*)((char*)workspace + align256(q.bytes));
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    float* hdr = iopt + 2 * (size_t)m.P;
+    JointCtx c;
+    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, hdr, q.coef, s, &c))) return rc;
+    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
+    launch_rnvp_fwd(q.p, fp, grid, 1, q.p.xd, true, s);
+    const WideJoint jn = wide_joint_of(c, N);
+    if ((rc = pcn_wide_image(q, model, ip, 0, c.prior_targets, c.prior_loss.kind, logits, &jn, s))) return rc;   // (dxd: unscaled)
+    const UpdArgs u = wide_joint_upd_args(m, q.w.grads, ip, iopt, status, opt, step, c.gscale);
+    joint_finish(c, q.w.grads, 1, u.PS, m.P, loss_out, s);   // in front of both updates: they read gscale
+    launch_wide_update(m, u, s);                             // (writes the frozen flag of this step into the header)
+    launch_rnvp_bwd(q.p, fp, grid, 1, s);
+    RnvpUpdArgs ru = make_rnvp_upd_args(q.p, 1, 0, fp, fopt, nullptr, &u.opt, wd_flow, step, hdr,
+                                        2 * (long long)m.P + INR_OPT_HEADER_FLOATS, status);
+    ru.gscale = c.gscale;
+    launch_rnvp_update_args(q.p, 1, ru, s);
+    joint_dseg(c, dseg, s);
+    joint_dseg_gate(c.gscale, N, dseg, c.jl.blocks, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t inrfit_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrGridDesc* grid) {
+    if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
+    if (!grid || grid->n_points <= 0) return INR_EINVAL;
+    return align256(wide_total_bytes(make_wide_map(model), grid->n_points, false, 1)) + joint_ws_bytes(grid->n_points);
+}
+
+int64_t inrfit_pcn_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrRnvpDesc* rnvp, const InrGridDesc* grid) {
+    if (!rnvp_ok(rnvp) || !pcn_wide_shape(model)) return INR_EUNSUPPORTED;
+    if (!grid || grid->n_points <= 0) return INR_EINVAL;
+    return align256(pcn_wide_bytes(model, rnvp, grid, 1)) + joint_ws_bytes(grid->n_points);
+}
+
+int inrfit_wide_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                           const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
+                           float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!params || !opt_state || !seg || !target || !dseg) return INR_EINVAL;
+    return wide_joint_step(model, params, opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace,
+                           workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
+                               float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* seg,
+                               const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, float flow_weight_decay,
+                               int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
+    return pcn_wide_joint_step(model, rnvp, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc, opt,
+                               flow_weight_decay, step, loss_out, dseg, prior_logits, status, workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
 
 int inrfit_forward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
                    void* workspace, int64_t workspace_bytes, void* stream) {
@@ -2932,56 +3066,58 @@ __global__ __launch_bounds__(256) void joint_prior_dseg_kernel(const float* __re
 
 }  // namespace
 
-int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
-                            const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
-                            int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
-                            int64_t workspace_bytes, void* stream) {
-    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
+namespace {
+
+// argument checks of inrfit_joint_prior_step / inrfit_wide_joint_prior_step in front of the shape's own
+static int check_joint_prior(const InrJointPriorDesc* desc, const InrOptDesc* opt, int step) {
     if (!opt || (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) || step < 1) return INR_EINVAL;
     if (desc->kind != INR_LOSS_SE && desc->kind != INR_LOSS_BCE) return INR_EINVAL;
     if (desc->weight_mode < INR_WEIGHT_NONE || desc->weight_mode > INR_WEIGHT_SSSDMS) return INR_EINVAL;
     if (desc->align_rule < INR_ALIGN_NONE || desc->align_rule > INR_ALIGN_SOFT) return INR_EINVAL;
-    const KernelEntry* e;
-    Workspace w;
-    int rc = prepare(model, grid, 1, workspace, workspace_bytes, &e, &w);   // no fused kernel for this shape: INR_EUNSUPPORTED
-    if (rc) return rc;
-    const long long N = grid->n_points;
-    const long long data_count = desc->data_count > 0 ? desc->data_count : N;
-    if (desc->data_count < 0 || data_count > N) return INR_EINVAL;
-    const bool align = desc->align_rule != INR_ALIGN_NONE;
-    if (align && (desc->align_begin < 0 || desc->align_begin >= N)) return INR_EINVAL;
-    if (workspace_bytes < inrfit_joint_step_workspace_bytes(model, grid)) return INR_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* jws = (float*)((char*)workspace + align256(w.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
-    float* hdr = opt_state + 2 * (size_t)w.Pu;
-    const long long n_align = align ? N - desc->align_begin : 0;
-    hipLaunchKernelGGL(joint_prep_kernel, dim3(1), dim3(64), 0, s, hdr, opt->lr, step, w.coef, 0.f, 0);
+    return INR_OK;
+}
+
+// the ranges of the two terms over the N points
+struct PriorRanges {
+    long long data_count, align_begin, n_align;
+    bool align;
+};
+static int prior_ranges(const InrJointPriorDesc* desc, long long N, PriorRanges* r) {
+    r->data_count = desc->data_count > 0 ? desc->data_count : N;
+    if (desc->data_count < 0 || r->data_count > N) return INR_EINVAL;
+    r->align = desc->align_rule != INR_ALIGN_NONE;
+    if (r->align && (desc->align_begin < 0 || desc->align_begin >= N)) return INR_EINVAL;
+    r->align_begin = r->align ? desc->align_begin : 0;
+    r->n_align = r->align ? N - desc->align_begin : 0;
+    return INR_OK;
+}
+
+// header, class coefficients and status in front of the prior's pass
+static int joint_prior_begin(const InrJointPriorDesc* desc, const PriorRanges& r, const InrOptDesc* opt, int step, const float* target,
+                             float* hdr, float* coef, int32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(joint_prep_kernel, dim3(1), dim3(64), 0, s, hdr, opt->lr, step, coef, 0.f, 0);
     const InrLossDesc pl{desc->kind, desc->weight_mode, desc->ratio, 0.f, 0.f};
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(1), dim3(256), 0, s, target, data_count, pl, w.coef, desc->c_data, desc->use_noneclass,
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(1), dim3(256), 0, s, target, r.data_count, pl, coef, desc->c_data, desc->use_noneclass,
                        desc->noneclass);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, w, params, 1, s))) return rc;
-    w.set_step(step);
-    StepMask m;
-    m.data_count = data_count;
-    m.use_noneclass = desc->use_noneclass ? 1 : 0;
-    m.noneclass = desc->noneclass;
-    m.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
-    m.align_begin = align ? desc->align_begin : 0;
-    if ((rc = launch_step(e, w, true, grid, target, desc->kind, 1, logits, s, nullptr, align ? seg : nullptr,
-                          align ? desc->beta / (float)n_align : 0.f, m))) return rc;
+    return INR_OK;
+}
+
+// behind the prior's pass: loss_out[1] and [2] on their own, then the finish kernel (gscale) on the pass's loss column; -> the blocks
+// of the point-wise launches
+static int joint_prior_finish(const InrJointPriorDesc* desc, const PriorRanges& r, const float* logits, const float* seg, const float* target,
+                              const float* coef, long long N, float* jws, const float* slabs, int wgs, int PS, int loss_col,
+                              const float* seg_term, float* gscale, float* loss_out, hipStream_t s) {
     PriorShareArgs pa{};
     pa.logits = logits;
     pa.seg = seg;
     pa.targets = target;
-    pa.coef = w.coef;
+    pa.coef = coef;
     pa.N = N;
-    pa.data_count = data_count;
-    pa.align_begin = m.align_begin;
+    pa.data_count = r.data_count;
+    pa.align_begin = r.align_begin;
     pa.kind = desc->kind;
-    pa.use_noneclass = m.use_noneclass;
+    pa.use_noneclass = desc->use_noneclass ? 1 : 0;
     pa.align_rule = desc->align_rule;
     pa.noneclass = desc->noneclass;
     pa.part = jws;
@@ -2991,19 +3127,96 @@ int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt
     PriorFinArgs f{};
     f.part = jws;
     f.blocks = pa.blocks;
-    f.slabs = w.slabs;
-    f.wgs = w.wgs;
-    f.PS = w.PS;
-    f.loss_col = e->img.sl_cols - 1;
+    f.slabs = slabs;
+    f.wgs = wgs;
+    f.PS = PS;
+    f.loss_col = loss_col;
     f.seg_term = seg_term;
-    f.n_align = (float)n_align;
+    f.n_align = (float)r.n_align;
     f.gscale = gscale;
     f.loss_out = loss_out;
     hipLaunchKernelGGL(joint_prior_finish_kernel, dim3(1), dim3(256), 0, s, f);
-    launch_icnn_update(e, joint_upd_args(e, w, params, opt_state, status, opt, step, gscale), s);
+    return pa.blocks;
+}
+
+static void joint_prior_dseg(const InrJointPriorDesc* desc, const PriorRanges& r, int blocks, const float* logits, const float* seg,
+                             long long N, float* dseg, hipStream_t s) {
     const bool soft = desc->align_rule == INR_ALIGN_SOFT;
-    hipLaunchKernelGGL(joint_prior_dseg_kernel, dim3(pa.blocks), dim3(256), 0, s, (const float*)logits, seg, N, m.align_begin, soft ? 1 : 0,
-                       soft ? -2.f * desc->beta / (float)n_align : 0.f, dseg);
+    hipLaunchKernelGGL(joint_prior_dseg_kernel, dim3(blocks), dim3(256), 0, s, logits, seg, N, r.align_begin, soft ? 1 : 0,
+                       soft ? -2.f * desc->beta / (float)r.n_align : 0.f, dseg);
+}
+
+}  // namespace
+
+int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                            const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
+                            int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
+    int rc = check_joint_prior(desc, opt, step);
+    if (rc) return rc;
+    const KernelEntry* e;
+    Workspace w;
+    if ((rc = prepare(model, grid, 1, workspace, workspace_bytes, &e, &w))) return rc;   // no fused kernel for this shape: INR_EUNSUPPORTED
+    const long long N = grid->n_points;
+    PriorRanges r;
+    if ((rc = prior_ranges(desc, N, &r))) return rc;
+    if (workspace_bytes < inrfit_joint_step_workspace_bytes(model, grid)) return INR_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float* jws = (float*)((char*)workspace + align256(w.bytes));
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
+    if ((rc = joint_prior_begin(desc, r, opt, step, target, opt_state + 2 * (size_t)w.Pu, w.coef, status, s))) return rc;
+    if ((rc = launch_pack(e, w, params, 1, s))) return rc;
+    w.set_step(step);
+    StepMask m;
+    m.data_count = r.data_count;
+    m.use_noneclass = desc->use_noneclass ? 1 : 0;
+    m.noneclass = desc->noneclass;
+    m.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
+    m.align_begin = r.align_begin;
+    if ((rc = launch_step(e, w, true, grid, target, desc->kind, 1, logits, s, nullptr, r.align ? seg : nullptr,
+                          r.align ? desc->beta / (float)r.n_align : 0.f, m))) return rc;
+    const int blocks = joint_prior_finish(desc, r, logits, seg, target, w.coef, N, jws, w.slabs, w.wgs, w.PS, e->img.sl_cols - 1, seg_term,
+                                          gscale, loss_out, s);
+    launch_icnn_update(e, joint_upd_args(e, w, params, opt_state, status, opt, step, gscale), s);
+    joint_prior_dseg(desc, r, blocks, logits, seg, N, dseg, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+int inrfit_wide_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                                 const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
+                                 int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
+    int rc = check_joint_prior(desc, opt, step);
+    if (rc) return rc;
+    WideMap m;
+    WideWs w;
+    float* jws;
+    if ((rc = wide_joint_prepare(model, grid, workspace, workspace_bytes, &m, &w, &jws))) return rc;   // a fused or an encode shape: INR_EUNSUPPORTED
+    const long long N = grid->n_points;
+    PriorRanges r;
+    if ((rc = prior_ranges(desc, N, &r))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
+    if ((rc = joint_prior_begin(desc, r, opt, step, target, opt_state + 2 * (size_t)m.P, w.coef, status, s))) return rc;
+    WideJoint jn{};
+    jn.seg = r.align ? seg : nullptr;
+    jn.c_align = r.align ? desc->beta / (float)r.n_align : 0.f;
+    jn.data_count = r.data_count;
+    jn.align_begin = r.align_begin;
+    jn.use_noneclass = desc->use_noneclass ? 1 : 0;
+    jn.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
+    jn.noneclass = desc->noneclass;
+    if ((rc = wide_forward(m, w, model, params, grid, 0, target, desc->kind, true, logits, s, &jn))) return rc;
+    if ((rc = wide_backward(m, w, model, params, N, s))) return rc;
+    const UpdArgs u = wide_joint_upd_args(m, w.grads, params, opt_state, status, opt, step, gscale);
+    const int blocks = joint_prior_finish(desc, r, logits, seg, target, w.coef, N, jws, w.grads, 1, u.PS, m.P, seg_term, gscale, loss_out, s);
+    launch_wide_update(m, u, s);
+    joint_prior_dseg(desc, r, blocks, logits, seg, N, dseg, s);
+    joint_dseg_gate(gscale, N, dseg, blocks, s);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 

@@ -164,6 +164,49 @@ __global__ __launch_bounds__(256) void wide_layer0_kernel(InrGridDesc gd, int im
 //   dZ_L[p][j] = dy w_o[j] [z_L[p][j] > 0]  (the row is still in the cache);
 //   and the block's share of the output layer's gradients (dw_o | db_o | ds_o)[j] = sum_p dy[p] Z_L,ext[p][j], summed over the block's
 //   points in a fixed order -> part[block][hs_valid] (wide_reduce_kernel adds the blocks in order).
+// The data term of a joint step (the fused step kernels' StepArgs / StepMask, icnn_step.h): the first data_count points carry the
+// criterion against `target` (which holds data_count values; soft targets are FBMS's SE against seg with coefficient 1 / N), a
+// target equal to `noneclass` drops the point, and from align_begin on a second term c_align (p - ind)^2 is added with
+// ind = [seg > 0.5] (strict: a NaN in seg counts as 0) or seg itself (align_soft).  seg = null: no align term.
+struct WideJoint {
+    const float* seg;       // [N] or null
+    float c_align;
+    long long data_count, align_begin;
+    int use_noneclass, align_soft;
+    float noneclass;
+};
+// loss and dL/dlogit of ONE point from its logit: the output pass (wide_out_kernel) and the pass that rebuilds dL/dlogits from the
+// logits for dL/dcoords (pcn_wide_dy_kernel) evaluate the same expressions.  JOINT = false: SE / BCE against target[p] with the
+// class coefficient, or target[p] as dL/dlogit itself (INR_LOSS_EXTERNAL).
+template <bool JOINT>
+__device__ __forceinline__ void wide_data_term(const float* __restrict__ target, const float* __restrict__ coef, int loss_kind,
+                                               const WideJoint& jn, long long p, float y, float& l, float& dy) {
+    const float tg = target[JOINT ? (p < jn.data_count ? p : jn.data_count - 1) : p];   // (joint: never past the targets)
+    if (!JOINT && loss_kind == INR_LOSS_EXTERNAL) {
+        dy = tg;
+        return;
+    }
+    const float pr = 1.f / (1.f + expf(-y));
+    const float cw = tg < 0.5f ? coef[0] : coef[1];
+    if (loss_kind == INR_LOSS_SE) {
+        const float d = tg - pr;
+        l = d * d * cw;
+        dy = 2.f * (pr - tg) * pr * (1.f - pr) * cw;
+    } else {
+        const float lp = bce_log(pr), lq = bce_log(1.f - pr);   // clamped at -100, NaN kept (torch.nn.BCELoss)
+        l = -(tg * lp + (1.f - tg) * lq) * cw;
+        const float pq = pr * (1.f - pr);
+        dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
+    }
+    if (JOINT) {
+        if (p >= jn.data_count || (jn.use_noneclass && tg == jn.noneclass)) {   // a select: a NaN prior there stays out of the sum
+            l = 0.f;
+            dy = 0.f;
+        }
+        if (jn.seg != nullptr && p >= jn.align_begin) align_term(jn.seg + p, jn.c_align, jn.align_soft, pr, l, dy);
+    }
+}
+
 struct WideOutArgs {
     const float* zl;        // [N][hs]
     const float* wo;        // [h]
@@ -176,15 +219,34 @@ struct WideOutArgs {
     float* part_ext;        // [blocks][h][1 + C] partials of (db | dS) of the last hidden layer = dZ_L^T (1, X) (train, EXT instantiations)
     long long N;
     int h, C, hs, hp, hsv, loss_kind, train;
+    WideJoint jn;           // JOINT instantiations only
 };
 constexpr int WIDE_OUT_MAXQ = (WIDE_MAX_HIDDEN_PAD + 63) / 64;   // f32x4 per lane and row
-template <int WIDE_OUT_NQ, bool EXT>   // 64-column slices a row may have (register budget of the instantiation); EXT: also dZ_L^T (1, X)
+// 64-column slices a row may have (register budget of the instantiation); EXT: also dZ_L^T (1, X); JOINT: the data term of a joint step
+template <int WIDE_OUT_NQ, bool EXT, bool JOINT = false>
 __global__ __launch_bounds__(256) void wide_out_kernel(const WideOutArgs a) {
     __shared__ float sm[4];
     __shared__ float colw[4][5][64];        // per wave: the column sums of one 64-column slice (output layer; (1, x) sums)
+    // JOINT: what only the data term and the logits' store read - the joint constants, the target / coefficient / logits pointers, the
+    // loss kind - is read from LDS there: seventeen scalar registers less held across the point loop
+    __shared__ WideJoint sjn;
+    __shared__ const float* s_target;
+    __shared__ const float* s_coef;
+    __shared__ float* s_logits;
+    __shared__ int s_kind;
     const int tid = threadIdx.x, l15 = tid & 15, rg = tid >> 4;      // 16 lanes per point, 16 row groups
     const long long p0 = (long long)blockIdx.x * WIDE_OUT_CHUNK;
     const int nq = (a.hs + 63) / 64;        // 64-column slices of a row (16 lanes x 4 floats)
+    if (JOINT) {
+        if (tid == 0) {
+            sjn = a.jn;
+            s_target = a.target;
+            s_coef = a.coef;
+            s_logits = a.logits;
+            s_kind = a.loss_kind;
+        }
+        __syncthreads();
+    }
     f32x4 gacc[WIDE_OUT_NQ];
     f32x4 eacc[EXT ? WIDE_OUT_NQ : 1][4];   // [slice][column of the lane's four] = sum_p dZ_L[p][j] (1, x_p)
 #pragma unroll
@@ -235,27 +297,14 @@ __global__ __launch_bounds__(256) void wide_out_kernel(const WideOutArgs a) {
             xe[1 + c] = zr[a.h + 1 + c];
             y = fmaf(a.sc[1 + c], xe[1 + c], y);
         }
-        if (a.logits && valid && l15 == 0) a.logits[p] = y;
-        if (!a.train) continue;
+        if (JOINT) {
+            if (valid && l15 == 0) s_logits[p] = y;   // (a joint step always writes its logits)
+        } else if (a.logits && valid && l15 == 0) a.logits[p] = y;
+        if (!JOINT && !a.train) continue;   // (a joint step always trains)
         float l = 0.f, dy = 0.f;
         if (valid) {
-            const float tg = a.target[p];
-            if (a.loss_kind == INR_LOSS_EXTERNAL) {
-                dy = tg;
-            } else {
-                const float pr = 1.f / (1.f + expf(-y));
-                const float cw = tg < 0.5f ? a.coef[0] : a.coef[1];
-                if (a.loss_kind == INR_LOSS_SE) {
-                    const float d = tg - pr;
-                    l = d * d * cw;
-                    dy = 2.f * (pr - tg) * pr * (1.f - pr) * cw;
-                } else {
-                    const float lp = bce_log(pr), lq = bce_log(1.f - pr);   // clamped at -100, NaN kept (torch.nn.BCELoss)
-                    l = -(tg * lp + (1.f - tg) * lq) * cw;
-                    const float pq = pr * (1.f - pr);
-                    dy = (pr - tg) / fmaxf(pq, 1e-12f) * pq * cw;
-                }
-            }
+            if (JOINT) wide_data_term<true>(s_target, s_coef, s_kind, sjn, p, y, l, dy);
+            else wide_data_term<false>(a.target, a.coef, a.loss_kind, a.jn, p, y, l, dy);
         }
         if (l15 == 0) lsum += l;
         float* dr = a.dz + (size_t)(valid ? p : 0) * a.hp;
@@ -278,7 +327,7 @@ __global__ __launch_bounds__(256) void wide_out_kernel(const WideOutArgs a) {
             }
         }
     }
-    if (!a.train) return;
+    if (!JOINT && !a.train) return;
     {   // loss partial of the block: the 16 row groups in order
         const float v = sum_over_groups(sum_over_points(lsum));
         if ((tid & 63) == 0) sm[tid >> 6] = v;
@@ -693,7 +742,7 @@ inline int wide_head(const WideMap& m, const WideWs& w, const InrModelDesc* md, 
 
 // forward of ONE image; with `train`: also dZ_L (w.dza), the output layer's gradients and the loss (w.grads)
 inline int wide_forward(const WideMap& m, const WideWs& w, const InrModelDesc* md, const float* params, const InrGridDesc* grid, int img,
-                        const float* target, int loss_kind, bool train, float* logits, hipStream_t s) {
+                        const float* target, int loss_kind, bool train, float* logits, hipStream_t s, const WideJoint* jn = nullptr) {
     const long long N = grid->n_points;
     const int h = m.h, C = m.C, hs = w.hs;
     // layer 0 at width F (+ in the launch's last blocks: the padded copy of the hidden layers' weights)
@@ -721,11 +770,18 @@ inline int wide_forward(const WideMap& m, const WideWs& w, const InrModelDesc* m
     a.dz = w.dza; a.part = w.part;
     a.N = N; a.h = h; a.C = C; a.hs = hs; a.hp = w.hp; a.hsv = w.hsv; a.loss_kind = loss_kind; a.train = train ? 1 : 0;
     a.part_ext = w.part2;
-    if (hs <= 5 * 64) hipLaunchKernelGGL((wide_out_kernel<5, true>), dim3(w.blocks), dim3(256), 0, s, a);
-    else if (hs <= 6 * 64) hipLaunchKernelGGL((wide_out_kernel<6, true>), dim3(w.blocks), dim3(256), 0, s, a);   // (h = 350: no AGPR spills)
-    else if (hs <= 7 * 64) hipLaunchKernelGGL((wide_out_kernel<7, true>), dim3(w.blocks), dim3(256), 0, s, a);
-    else if (hs <= 9 * 64) hipLaunchKernelGGL((wide_out_kernel<9, true>), dim3(w.blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wide_out_kernel<WIDE_OUT_MAXQ, false>), dim3(w.blocks), dim3(256), 0, s, a);
+#define WIDE_OUT_GO(NQ_, EXT_)                                                                                              \
+    do {                                                                                                                    \
+        if (jn) hipLaunchKernelGGL((wide_out_kernel<NQ_, EXT_, true>), dim3(w.blocks), dim3(256), 0, s, a);                 \
+        else hipLaunchKernelGGL((wide_out_kernel<NQ_, EXT_>), dim3(w.blocks), dim3(256), 0, s, a);                          \
+    } while (0)
+    if (jn) a.jn = *jn;   // (a joint step's data term: an ICNN-form shape in training)
+    if (hs <= 5 * 64) WIDE_OUT_GO(5, true);
+    else if (hs <= 6 * 64) WIDE_OUT_GO(6, true);   // (h = 350: no AGPR spills)
+    else if (hs <= 7 * 64) WIDE_OUT_GO(7, true);
+    else if (hs <= 9 * 64) WIDE_OUT_GO(9, true);
+    else WIDE_OUT_GO(WIDE_OUT_MAXQ, false);
+#undef WIDE_OUT_GO
     if (train) {
         // (dw_o | db_o | ds_o | loss), and (db | dS) of the last hidden layer = dZ_L^T (1, X) where the same pass summed it
         const WideRedJob jo = wide_red_job(w.part, w.blocks, 1, w.hsv + 1, 2, 0);

@@ -11,7 +11,11 @@ noneclass); `loss[2]` is then the mean align term before beta and `loss[3]` = 1,
 
 `joint_prior_step` (inrfit_joint_prior_step) is the prior's share alone, for the convexity benchmark's losses: the caller evaluates
 the segmentation share in torch (any criterion, second-order autograd included) and hands its device scalar over; the call adds
-the prior's masked data term and the hard / soft align term, steps the row and returns d(prior's share) / d seg."""
+the prior's masked data term and the hard / soft align term, steps the row and returns d(prior's share) / d seg.
+
+`wide_joint_step`, `pcn_wide_joint_step` and `wide_joint_prior_step` are the same three steps for ICNN shapes of the layer-by-layer
+path (n_hidden > 130 or more than two hidden layers: inrfit_wide_joint_step / _pcn_wide_joint_step / _wide_joint_prior_step); the
+entry points above refuse those shapes, these refuse the shapes with a fused kernel."""
 from __future__ import annotations
 
 import ctypes as C
@@ -73,15 +77,17 @@ def _workspace(key, nbytes_fn, dev) -> Tensor:
 
 
 def _icnn_joint(entry: str, spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
-                n_target: int, desc, extra: tuple, od: L.InrOptDesc, step: int) -> JointStepResult:
-    """inrfit_joint_step / inrfit_joint_prior_step: `extra` is what the entry point takes between its loss desc and its opt desc."""
+                n_target: int, desc, extra: tuple, od: L.InrOptDesc, step: int, wide: bool = False) -> JointStepResult:
+    """inrfit_joint_step / inrfit_joint_prior_step: `extra` is what the entry point takes between its loss desc and its opt desc.
+    `wide`: the layer-by-layer entry points and their workspace."""
     params, seg, target = K._check_dev(params, "params"), K._check_dev(seg, "seg"), K._check_dev(target, "target")
     dev, n = params.device, grid.n_points
     assert params.numel() == spec.n_params and seg.numel() == n and target.numel() == n_target
     assert opt_state.numel() == 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS and opt_state.is_contiguous()
     md, gd = spec.desc(), grid.desc()
     lib = L.load()
-    ws = _workspace(("icnn", spec, n), lambda: lib.inrfit_joint_step_workspace_bytes(C.byref(md), C.byref(gd)), dev)
+    ws_bytes = lib.inrfit_wide_joint_step_workspace_bytes if wide else lib.inrfit_joint_step_workspace_bytes
+    ws = _workspace(("icnn-wide" if wide else "icnn", spec, n), lambda: ws_bytes(C.byref(md), C.byref(gd)), dev)
     loss, dseg, logits, status = _outputs(n, dev)
     rc = getattr(lib, entry)(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(),
                              C.byref(desc), *extra, C.byref(od), int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(),
@@ -93,14 +99,19 @@ def _icnn_joint(entry: str, spec: K.IcnnSpec, params: Tensor, opt_state: Tensor,
 def _flow_joint(family: str, ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
                 flow_opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, od: L.InrOptDesc,
                 flow_weight_decay: float, step: int) -> JointStepResult:
-    """inrfit_pcn_joint_step / inrfit_cdn_joint_step: `fspec` is the family's flow (RnvpSpec / FlowSpec)."""
+    """inrfit_pcn_joint_step / inrfit_cdn_joint_step: `fspec` is the family's flow (RnvpSpec / FlowSpec); family 'pcn_wide':
+    inrfit_pcn_wide_joint_step with its own workspace call."""
     dev, n = icnn_params.device, grid.n_points
     md, fd, gd = ispec.desc(), fspec.desc(), grid.desc()
     lib = L.load()
-    ws_bytes = getattr(lib, f"inrfit_{family}_workspace_bytes")
-    ws = _workspace((family, ispec, fspec, n),
-                    lambda: ws_bytes(C.byref(md), C.byref(fd), C.byref(gd), 1) + lib.inrfit_joint_loss_workspace_bytes(n) + 4 * n + 1024,
-                    dev)
+    if family == "pcn_wide":
+        ws = _workspace((family, ispec, fspec, n),
+                        lambda: lib.inrfit_pcn_wide_joint_step_workspace_bytes(C.byref(md), C.byref(fd), C.byref(gd)), dev)
+    else:
+        ws_bytes = getattr(lib, f"inrfit_{family}_workspace_bytes")
+        ws = _workspace((family, ispec, fspec, n),
+                        lambda: ws_bytes(C.byref(md), C.byref(fd), C.byref(gd), 1) + lib.inrfit_joint_loss_workspace_bytes(n) + 4 * n + 1024,
+                        dev)
     loss, dseg, logits, status = _outputs(n, dev)
     entry = f"inrfit_{family}_joint_step"
     rc = getattr(lib, entry)(C.byref(md), C.byref(fd), icnn_params.data_ptr(), flow_params.data_ptr(), icnn_opt_state.data_ptr(),
@@ -155,3 +166,33 @@ def joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: 
                        desc.data_count if desc.data_count > 0 else grid.n_points, desc,
                        (None if seg_term is None else seg_term.data_ptr(),),
                        _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
+
+
+def wide_joint_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
+                    desc: L.InrJointLossDesc, step: int, lr: float, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8,
+                    weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
+    """`joint_step` for an ICNN of the layer-by-layer path (inrfit_wide_joint_step)."""
+    return _icnn_joint("inrfit_wide_joint_step", spec, params, opt_state, grid, seg, target, grid.n_points, desc, (),
+                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step, wide=True)
+
+
+def pcn_wide_joint_step(ispec: K.IcnnSpec, rspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
+                        flow_opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, step: int,
+                        lr: float, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8,
+                        flow_weight_decay: float = 0.0) -> JointStepResult:
+    """`pcn_joint_step` over an ICNN of the layer-by-layer path (inrfit_pcn_wide_joint_step)."""
+    return _flow_joint("pcn_wide", ispec, rspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
+                       _opt_desc(optimizer, lr, betas, eps, 0.0, True), flow_weight_decay, step)
+
+
+def wide_joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
+                          desc: L.InrJointPriorDesc, step: int, lr: float, seg_term: Optional[Tensor] = None, optimizer: str = "adam",
+                          betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
+    """`joint_prior_step` for an ICNN of the layer-by-layer path (inrfit_wide_joint_prior_step)."""
+    if seg_term is not None:
+        seg_term = K._check_dev(seg_term, "seg_term")
+        assert seg_term.numel() == 1
+    return _icnn_joint("inrfit_wide_joint_prior_step", spec, params, opt_state, grid, seg, target,
+                       desc.data_count if desc.data_count > 0 else grid.n_points, desc,
+                       (None if seg_term is None else seg_term.data_ptr(),),
+                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step, wide=True)

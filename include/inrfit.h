@@ -316,7 +316,7 @@ int inrfit_rnvp_fit_identity(const InrRnvpDesc* rnvp, float* flow_params, float*
  * there one optimizer step is the RealNVP forward, the layer-by-layer forward / backward on the deformed coordinates (which also
  * returns dL/dcoords), the ICNN update, the RealNVP backward seeded from dL/dcoords and the RealNVP update - all on the stream, same
  * semantics (one learning rate from the ICNN header, a non-finite loss freezes both halves of the image).  The encode shapes and
- * n_hidden > 1024 stay INR_EUNSUPPORTED; inrfit_pcn_joint_step takes the fused shapes only. */
+ * n_hidden > 1024 stay INR_EUNSUPPORTED; inrfit_pcn_joint_step takes the fused shapes only (the others: inrfit_pcn_wide_joint_step). */
 int inrfit_pcn_forward(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params, const float* flow_params,
                        const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
                        void* stream);
@@ -432,7 +432,7 @@ int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, fl
  * and this call evaluates the last two in the step kernel: prior forward, loss, backward, Adam / Adamax + enforce_convexity on the
  * row in place, as inrfit_joint_step.  `target` holds data_count values: target[p] is the target of point p.  Points whose target
  * equals `noneclass` (use_noneclass) contribute nothing and are not counted; the class weight (weight_mode) is taken over the rest.
- * ICNN priors with a fused kernel only (a layer-by-layer shape: INR_EUNSUPPORTED). */
+ * ICNN priors with a fused kernel only (a layer-by-layer shape: INR_EUNSUPPORTED; inrfit_wide_joint_prior_step takes those). */
 enum { INR_ALIGN_NONE = 0, INR_ALIGN_HARD = 1, INR_ALIGN_SOFT = 2 };
 typedef struct InrJointPriorDesc {
     int32_t kind;             /* the prior's data term: INR_LOSS_SE or INR_LOSS_BCE */
@@ -456,6 +456,36 @@ int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt
                             const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
                             int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                             int64_t workspace_bytes, void* stream);
+
+/* ---- the fused joint step for ICNN shapes of the layer-by-layer path (n_hidden > 130 or more than two hidden layers).
+ * inrfit_joint_step, inrfit_pcn_joint_step and inrfit_joint_prior_step keep returning INR_EUNSUPPORTED for these shapes; the three
+ * calls below take the same argument lists with the same semantics (one image per call, the row updated in place, `step` = torch's
+ * state['step'] after the step, opt->plateau ignored, loss_out [4], dseg, optional prior_logits; a non-finite composite loss leaves
+ * the row - for the path-connected prior also the flow parameters - and every moment untouched and sets *status; nothing is read
+ * on the host) for exactly the ICNN-form shapes without a fused kernel: relu layer 0, one output, n_features = n_hidden,
+ * in_features 2 or 3, n_hidden <= 1024, n_layers <= 8.  A shape WITH a fused kernel and the encode shapes: INR_EUNSUPPORTED.
+ * One step = the layer-by-layer forward, whose output pass evaluates the joint step's data term (soft targets, the masked data
+ * term, the hard / soft align term) into the loss column of its gradient vector, the layer-by-layer backward, the finish kernel
+ * (clip factor / gradient scale), the optimizer step on the gradient vector times that scale, d loss / d seg - and for the
+ * path-connected prior the RealNVP's forward in front and its backward and update (same scale, learning rate and frozen flag from
+ * the ICNN's header) behind.  Forms of inrfit_wide_joint_step / inrfit_pcn_wide_joint_step: as inrfit_joint_step.
+ * One addition to the fused calls' semantics: when the composite loss is not finite (*status = 1), dseg is all zeros - a frozen step
+ * hands the backbone no gradient.
+ * Workspace: the two calls below (inrfit_wide_joint_prior_step: inrfit_wide_joint_step_workspace_bytes). */
+int64_t inrfit_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrGridDesc* grid);
+int64_t inrfit_pcn_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrRnvpDesc* rnvp, const InrGridDesc* grid);
+int inrfit_wide_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                           const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
+                           float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+int inrfit_pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
+                               float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* seg,
+                               const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, float flow_weight_decay,
+                               int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+int inrfit_wide_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                                 const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
+                                 int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
 
 /* Measurement hook (bench.py, rocprof): launch ONLY the fused forward+loss+backward step kernel `iters` times
  * back-to-back on `stream` (no optimizer step), so its average duration can be bracketed with events. */

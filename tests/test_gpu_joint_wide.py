@@ -1,0 +1,651 @@
+"""The fused joint step for priors on the layer-by-layer path (n_hidden > 130 or more than two hidden layers): inrfit_wide_joint_step,
+inrfit_wide_joint_prior_step, inrfit_pcn_wide_joint_step and JointTrainer(fused_layer_by_layer=True).
+
+Shapes: a 20 x 23 grid (460 points: a multiple of neither 16 nor the output pass's chunk of 128, four blocks); ICNN 136 x 1 (the first
+width past the fused kernels, rows padded to 140), 144 x 3 (depth), 200 x 1 (a partly filled fourth 64-column slice of the output
+pass); the path-connected cases at C = 2 and C = 3 with 4 flows x 16.
+
+Bars: the ICNN steps against the oracle (forward, the loss under torch autograd, O.adam_step / O.adamax_step,
+O.icnn_enforce_convexity) with the bars of tests/test_gpu_joint_penalty.py::test_icnn_joint_step_with_extra_penalty_matches_oracle;
+the path-connected step and the trainer against the autograd step of the same modules with that file's _assert_same."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import inr_oracle as O  # noqa: E402  (checker only)
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+H, W, LR = 20, 23, 1e-3
+N = H * W
+SHAPES = {"136x1": (136, 1), "144x3": (144, 3), "200x1": (200, 1)}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def _state(spec, seed):
+    g = torch.Generator().manual_seed(seed)
+    p0 = {k: (torch.rand(shp, generator=g) - 0.45) * 0.3 for k, shp in spec.keys_shapes()}
+    return p0, g
+
+
+def _seg_target(g, n=N):
+    seg = torch.rand(n, generator=g) * 0.9 + 0.05
+    half = torch.tensor(0.5)
+    seg[3], seg[4], seg[5] = half, torch.nextafter(half, torch.tensor(0.0)), torch.nextafter(half, torch.tensor(1.0))
+    return seg, (torch.rand(n, generator=g) > 0.7).float()
+
+
+def _oracle_step(p0, grads, opt_kind):
+    p1 = {k: v.detach().clone() for k, v in p0.items()}
+    st = O.AdamState(p1)
+    (O.adam_step if opt_kind == "adam" else O.adamax_step)(p1, grads, st, LR)
+    O.icnn_enforce_convexity(p1)
+    return p1, st
+
+
+def _check_row(spec, row, opt, p1, st):
+    import awesome_amd as A
+    P = spec.n_params
+    np.testing.assert_allclose(row.cpu().numpy(), A.pack_state_dict(spec, p1).numpy(), rtol=1e-3, atol=2e-5)
+    for got, ref in ((opt[:P], st.m), (opt[P:2 * P], st.v)):
+        ref = A.pack_state_dict(spec, ref).numpy()
+        np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=1e-3, atol=2e-5 * float(np.abs(ref).max()))
+
+
+def _device_joint_loss(seg, prior, target, desc, dev):
+    """inrfit_joint_loss on [seg, prior] (1, 2, n): loss_out [4]."""
+    from awesome_amd import _lib as L
+    from awesome_amd import icnn as K
+    out = torch.stack([seg, prior]).reshape(1, 2, -1).contiguous()
+    lib = L.load()
+    ws = torch.empty(int(lib.inrfit_joint_loss_workspace_bytes(seg.numel())) // 4 + 1, device=dev)
+    res = torch.empty(4, device=dev)
+    rc = lib.inrfit_joint_loss(out.data_ptr(), target.contiguous().data_ptr(), 1, seg.numel(), C.byref(desc), res.data_ptr(), None,
+                               ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
+    L.check(rc, "inrfit_joint_loss")
+    return res
+
+
+# ---- 1. inrfit_wide_joint_step against the oracle ------------------------------------------------------------------------------
+# (shape, optimizer, form, seg criterion, prior criterion, gamma, alpha, beta)
+JOINT_CASES = [
+    ("136x1", "adam", "fbms_clip", ("bce", "sssdms"), None, 1.0, 1.0, 40.0),       # the penalty exceeds the segmentation loss: clip < 1
+    ("144x3", "adamax", "fbms_clip", ("se", "none"), None, 1.0, 0.5, 60.0),
+    ("200x1", "adamax", "fbms", ("bce", "sssdms"), None, 1.0, 1.0, 0.05),          # clip inactive
+    ("144x3", "adam", "fbms", ("bce", "none"), None, 1.0, 0.0, 0.05),              # alpha = 0: segmentation loss 0, so the clip is 0
+    ("136x1", "adamax", "image", ("bce", "none"), ("bce", "equal"), 1.0, 0.7, 0.0),
+    ("200x1", "adam", "image", ("se", "sssdms"), ("se", "sssdms"), 1.0, 0.0, 0.0),  # alpha = 0
+    ("136x1", "adam", "penalty", ("bce", "none"), ("bce", "none"), 0.1, 0.7, 100.0),
+    ("144x3", "adamax", "penalty", ("se", "sssdms"), ("bce", "equal"), 0.3, 0.0, 100.0),
+    ("200x1", "adam", "penalty", ("bce", "none"), ("se", "sssdms"), 2.0, 1.3, 100.0),
+]
+
+
+@pytest.mark.parametrize("case", range(len(JOINT_CASES)), ids=["-".join(map(str, c[:3])) for c in JOINT_CASES])
+def test_wide_joint_step_matches_oracle(dev, case):
+    """One inrfit_wide_joint_step: loss_out, d loss / d seg, the prior's logits, the updated row and both moments against the oracle;
+    loss_out also against inrfit_joint_loss on [seg, sigmoid(prior_logits)].  seg holds 0.5 and one ulp on either side."""
+    import awesome_amd as A
+    from awesome_amd import _lib as L
+    from awesome_amd import joint as J
+    shape, opt_kind, form, (kind, mode), pc, gamma, alpha, beta = JOINT_CASES[case]
+    h, nl = SHAPES[shape]
+    spec = A.IcnnSpec(n_hidden=h, in_features=2, n_layers=nl)
+    p0, g = _state(spec, 300 + case)
+    seg, tgt = _seg_target(g)
+    grid = O.positional_grid(W, H)[None]
+    pt = {k: v.clone().requires_grad_(True) for k, v in p0.items()}
+    seg_t = seg.clone().requires_grad_(True)
+    logits_ref = O.icnn_forward_image(pt, grid).reshape(-1)
+    prior = torch.sigmoid(logits_ref)
+    crit = O.weighted_loss(seg_t, tgt, kind=kind, mode=mode)
+    if form.startswith("fbms"):
+        out = torch.stack([seg_t, prior]).reshape(1, 2, H, W)
+        loss_ref = O.fbms_joint_loss(out, tgt.reshape(1, 1, H, W), alpha=alpha, beta=beta, clip_penalty=True, kind=kind, mode=mode)
+        pen = torch.mean((seg_t - prior) ** 2)
+        clip_active = bool(beta * pen > alpha * crit)
+        assert clip_active == (form == "fbms_clip" or alpha == 0.0)
+        desc = J.joint_desc(kind=kind, weight_mode=mode, alpha=alpha, beta=beta, clip_penalty=True)
+        want = [loss_ref.item(), crit.item(), pen.item()]
+    else:
+        pcrit = O.weighted_loss(prior, tgt, kind=pc[0], mode=pc[1])
+        align = torch.mean((prior - (seg_t > 0.5).float()) ** 2)
+        penalty = form == "penalty"
+        loss_ref = gamma * (crit + alpha * pcrit) + beta * align if penalty else crit + alpha * pcrit
+        desc = J.joint_desc(kind=kind, weight_mode=mode, alpha=alpha, beta=beta, form=L.JOINT_AWESOME_IMAGE, prior_kind=pc[0],
+                            prior_weight_mode=pc[1], gamma=gamma, extra_penalty=penalty)
+        want = [loss_ref.item(), crit.item(), align.item() if penalty else 0.0]
+    loss_ref.backward()
+    p1, st = _oracle_step(p0, {k: pt[k].grad if pt[k].grad is not None else torch.zeros_like(pt[k]) for k in p0}, opt_kind)
+
+    row = A.pack_state_dict(spec, p0, dev).clone()
+    opt = torch.zeros(2 * spec.n_params + 8, device=dev)
+    res = J.wide_joint_step(spec, row, opt, A.Grid.from_image_grid(grid.to(dev)), seg.to(dev), tgt.to(dev), desc, step=1, lr=LR,
+                            optimizer=opt_kind)
+    lo = res.loss.cpu()
+    print(f"[loss_out] {lo.tolist()} want {want}")
+    assert int(res.status[0]) == 0
+    np.testing.assert_allclose(lo[:3].numpy(), np.array(want, dtype=np.float32), rtol=2e-5, atol=1e-12)   # (atol: the terms that are exactly 0)
+    if form == "fbms":
+        assert lo[3].item() == 1.0 or alpha == 0.0
+    elif form == "fbms_clip":
+        assert 0.0 < lo[3].item() < 1.0
+    else:
+        assert lo[3].item() == 1.0
+    lo_dev = _device_joint_loss(seg.to(dev), torch.sigmoid(res.prior_logits), tgt.to(dev), desc, dev).cpu()
+    np.testing.assert_allclose(lo.numpy(), lo_dev.numpy(), rtol=2e-5, atol=1e-12)
+    ds_ref = seg_t.grad.numpy()
+    np.testing.assert_allclose(res.dseg.cpu().numpy(), ds_ref, rtol=5e-5, atol=1e-7 * float(np.abs(ds_ref).max()))
+    np.testing.assert_allclose(res.prior_logits.cpu().numpy(), logits_ref.detach().numpy(), rtol=0, atol=5e-6)
+    _check_row(spec, row, opt, p1, st)
+
+
+# ---- 2. inrfit_wide_joint_prior_step against the oracle --------------------------------------------------------------------------
+# (shape, optimizer, prior criterion, data_count, noneclass, align rule, align_begin, beta, c_data, seg_term, explicit grid)
+PRIOR_CASES = [
+    ("136x1", "adam", ("bce", "none"), 0, None, "none", 0, 0.0, 0.07, None, False),
+    ("144x3", "adamax", ("bce", "equal"), 301, None, "hard", 301, 100.0, 0.07, 0.4, False),     # data_count < N, hard align behind it
+    ("200x1", "adam", ("se", "sssdms"), 0, 2.0, "soft", 17, 3.0, 0.14, 0.25, False),             # noneclass, soft align, align_begin > 0
+    ("136x1", "adamax", ("bce", "none"), 333, 2.0, "soft", 129, 3.0, 0.12, None, True),          # the pixel form: explicit coordinates
+    ("200x1", "adam", ("bce", "none"), 0, None, "hard", 5, 100.0, 0.07, 0.4, True),
+]
+
+
+@pytest.mark.parametrize("case", range(len(PRIOR_CASES)), ids=["-".join(map(str, (c[0], c[1], c[5], c[3]))) for c in PRIOR_CASES])
+def test_wide_joint_prior_step_matches_oracle(dev, case):
+    """The prior's share: c_data pcrit_masked(prior[:data_count], t) + beta mean_{p >= align_begin}((prior - A(seg))^2), against the
+    oracle.  With a noneclass, loss_out[1] is also compared with the oracle's data term over the kept points alone: the dropped
+    points do not count."""
+    import awesome_amd as A
+    from awesome_amd import _lib as L
+    from awesome_amd import joint as J
+    shape, opt_kind, (kind, mode), dc, nonec, rule, ab, beta, c_data, seg_term, explicit = PRIOR_CASES[case]
+    h, nl = SHAPES[shape]
+    spec = A.IcnnSpec(n_hidden=h, in_features=2, n_layers=nl)
+    p0, g = _state(spec, 500 + case)
+    seg, _ = _seg_target(g)
+    n_data = dc or N
+    tgt = (torch.rand(n_data, generator=g) > 0.6).float()
+    if nonec is not None:
+        tgt[torch.rand(n_data, generator=g) > 0.7] = nonec
+    if explicit:
+        rows = torch.rand(N, 2, generator=g)
+        grid_dev = A.Grid.explicit(rows.t().contiguous().to(dev))
+    else:
+        rows = O.positional_grid(W, H).reshape(2, -1).t().contiguous()
+        grid_dev = A.Grid.from_image_grid(O.positional_grid(W, H)[None].to(dev))
+    pt = {k: v.clone().requires_grad_(True) for k, v in p0.items()}
+    seg_t = seg.clone().requires_grad_(True)
+    logits_ref = O.icnn_forward(pt, rows).reshape(-1)
+    prior = torch.sigmoid(logits_ref)
+    data = c_data * O.weighted_loss(prior[:n_data], tgt, kind=kind, mode=mode, noneclass=nonec)
+    if rule == "none":
+        align = torch.zeros(())
+    else:
+        a_of_seg = seg_t[ab:] if rule == "soft" else (seg_t[ab:] > 0.5).float()
+        align = torch.mean((prior[ab:] - a_of_seg) ** 2)
+    share = data + beta * align
+    share.backward()
+    p1, st = _oracle_step(p0, {k: pt[k].grad for k in p0}, opt_kind)
+    ds_ref = seg_t.grad.numpy() if seg_t.grad is not None else np.zeros(N, dtype=np.float32)
+
+    desc = J.joint_prior_desc(kind=kind, weight_mode=mode, noneclass=nonec, data_count=dc, c_data=c_data,
+                              align_rule={"none": L.ALIGN_NONE, "hard": L.ALIGN_HARD, "soft": L.ALIGN_SOFT}[rule], beta=beta,
+                              align_begin=ab)
+    row = A.pack_state_dict(spec, p0, dev).clone()
+    opt = torch.zeros(2 * spec.n_params + 8, device=dev)
+    st_dev = None if seg_term is None else torch.tensor([seg_term], device=dev)
+    res = J.wide_joint_prior_step(spec, row, opt, grid_dev, seg.to(dev), tgt.to(dev), desc, step=1, lr=LR, seg_term=st_dev,
+                                  optimizer=opt_kind)
+    lo = res.loss.cpu()
+    want = [share.item() + (seg_term or 0.0), data.item(), align.item()]
+    print(f"[loss_out] {lo.tolist()} want {want}")
+    assert int(res.status[0]) == 0 and lo[3].item() == 1.0
+    np.testing.assert_allclose(lo[:3].numpy(), np.array(want, dtype=np.float32), rtol=2e-5, atol=1e-12)   # (atol: no align term -> exactly 0)
+    np.testing.assert_allclose(res.dseg.cpu().numpy(), ds_ref, rtol=5e-5, atol=1e-7 * float(np.abs(ds_ref).max()))
+    np.testing.assert_allclose(res.prior_logits.cpu().numpy(), logits_ref.detach().numpy(), rtol=0, atol=5e-6)
+    _check_row(spec, row, opt, p1, st)
+    if nonec is not None:   # the dropped points do not count: the data term is the mean over the kept ones alone
+        keep = tgt != nonec
+        assert 0 < int(keep.sum()) < n_data
+        alone = c_data * O.weighted_loss(prior[:n_data][keep].detach(), tgt[keep], kind=kind, mode=mode)
+        np.testing.assert_allclose(lo[1].item(), alone.item(), rtol=2e-5)
+
+
+# ---- 3. inrfit_pcn_wide_joint_step and JointTrainer(fused_layer_by_layer=True) against the autograd step ----------------------------
+
+
+class _SegStandIn(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.conv = torch.nn.Conv2d(1, 1, 3, padding=1)
+
+    def forward(self, image, *args, **kwargs):
+        return self.conv(image)
+
+
+def _pcn_factory(h, layers, channels=2):
+    from awesome_amd.model import real_nvp_path_connected_net
+    return lambda: real_nvp_path_connected_net(channels=channels, hidden_units=16, flow_n_flows=4, flow_output_fn="tanh",
+                                               convex_net_hidden_units=h, convex_net_hidden_layers=layers)
+
+
+def _icnn_factory(h, layers):
+    from awesome_amd.model import ConvexNextNet
+    return lambda: ConvexNextNet(n_hidden=h, in_features=2, n_hidden_layers=layers)
+
+
+def _init_flow_parts(model, bank):
+    """Non-zero last layers (zero-initialised flows are the identity) and ActNorm marked initialised, on every row."""
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(3)
+        for i in range(len(bank)):
+            with bank.manager(model, i):
+                for name, p in model.named_parameters():
+                    if ".net.2." in name or "out_linear" in name or "linear2" in name:
+                        p.add_((0.05 * torch.randn(p.shape, generator=g)).to(p.device))
+        for b_name, b in model.named_buffers():
+            if b_name.endswith("data_dep_init_done"):
+                b.fill_(1.0)
+
+
+def _fbms(beta):
+    from awesome_amd.measures import FBMSJointLoss
+    return FBMSJointLoss(alpha=1.0, beta=beta, clip_penalty=True)
+
+
+def _image_loss(**kw):
+    from awesome_amd.measures import AwesomeImageLoss
+    return AwesomeImageLoss(**kw)
+
+
+def _moments(tr, opt, prior):
+    from awesome_amd.prior_bank import _ordered_parameters
+    if tr._fused_plan is not None and tr._path == "fused":
+        return torch.cat([torch.cat([m.reshape(-1), v.reshape(-1)]) for _, m, v in tr._flat_moment_views(tr._fused_plan)]).cpu()
+    k1, k2 = ("exp_avg", "exp_inf") if isinstance(opt, torch.optim.Adamax) else ("exp_avg", "exp_avg_sq")
+    return torch.cat([torch.cat([opt.state[p][k1].reshape(-1), opt.state[p][k2].reshape(-1)]) for p in _ordered_parameters(prior)]).cpu()
+
+
+def _run(dev, factory, crit, wide, schedule, fused=None, opt_type=torch.optim.Adam, lr=2e-3, flow=False, S=24, extra_penalty=False):
+    """Joint steps on two images from identical starting points; schedule [(steps, extra_penalty)].  wide: fused_layer_by_layer.
+    -> (losses, backbone weight, rows, paths, moments, trainer)"""
+    from awesome_amd.agent import JointTrainer
+    from awesome_amd.dataset import SyntheticPriorDataset
+    from awesome_amd.model import WrapperModule
+    from awesome_amd.prior_bank import PriorBank, _ordered_parameters
+    torch.manual_seed(5)
+    ds = SyntheticPriorDataset(n_images=2, size=S, kind="noisy_blob")
+    items = [ds[i] for i in range(2)]
+    seg = _SegStandIn()
+    wrapper = WrapperModule(seg, factory(), use_segmentation_output_inversion=True).to(dev)
+    bank = PriorBank(lambda: factory().to(dev), n_images=2, device=dev)
+    for k in range(2):
+        bank.row(k)
+    if flow:
+        _init_flow_parts(wrapper.prior_module, bank)
+    opt = opt_type(list(seg.parameters()) + list(_ordered_parameters(wrapper.prior_module)), lr=lr)
+    tr = JointTrainer(wrapper, bank, crit, opt, fused=fused, fused_layer_by_layer=wide, fused_extra_penalty=extra_penalty)
+    feat = torch.zeros(1, 1, 1, 1, device=dev)
+    losses, paths, s = [], [], 0
+    for steps, penalty in schedule:
+        if hasattr(crit, "extra_penalty"):
+            crit.extra_penalty = penalty
+        for _ in range(steps):
+            i = s % 2
+            (image, _, xy), target = items[i]
+            loss, _ = tr.perform_step(i, (image[None].to(dev), feat, xy[None].to(dev)), target[None].to(dev))
+            losses.append(float(loss))
+            paths.append(tr._path)
+            s += 1
+    return (losses, seg.conv.weight.detach().cpu().clone(), bank.params.detach().cpu().clone(), paths,
+            _moments(tr, opt, wrapper.prior_module), tr)
+
+
+def _assert_same(a, b):
+    """tests/test_gpu_joint_penalty.py::_assert_same, and the moments with the bar of the oracle parity above."""
+    np.testing.assert_allclose(a[0], b[0], rtol=2e-5)
+    np.testing.assert_allclose(a[1].numpy(), b[1].numpy(), rtol=2e-4, atol=2e-6)
+    np.testing.assert_allclose(a[2].numpy(), b[2].numpy(), rtol=1e-3, atol=2e-5)
+    np.testing.assert_allclose(a[4].numpy(), b[4].numpy(), rtol=1e-3, atol=2e-5 * float(b[4].abs().max()))
+
+
+@pytest.mark.parametrize("shape,crit", [("136x2", "fbms_clip"), ("144x3", "fbms"), ("136x2", "penalty")])
+def test_pcn_wide_joint_step_matches_the_autograd_step(dev, shape, crit):
+    """inrfit_pcn_wide_joint_step through the trainer (C = 2), 4 steps on two rows, against get_deformation(differentiable=True) +
+    ConvexNextNet under torch's optimizer: losses, backbone, both halves' parameters and moments; with and without the clip."""
+    h, layers = map(int, shape.split("x"))
+    make = {"fbms_clip": lambda: _fbms(40.0), "fbms": lambda: _fbms(0.05),
+            "penalty": lambda: _image_loss(alpha=0.7, gamma=0.1, beta=100.0)}[crit]
+    kw = dict(opt_type=torch.optim.Adamax if crit == "fbms" else torch.optim.Adam, flow=True, extra_penalty=True)
+    sched = [(4, crit == "penalty")]
+    f = _run(dev, _pcn_factory(h, layers), make(), True, sched, fused=True, **kw)
+    a = _run(dev, _pcn_factory(h, layers), make(), False, sched, fused=False, **kw)
+    assert f[3] == ["fused"] * 4 and a[3] == ["autograd"] * 4 and f[5]._fused_plan["wide"]
+    assert int(f[5].last_status[0]) == 0
+    _assert_same(f, a)
+
+
+def _pcn_rows(dev, C_in, h, layers, seed):
+    """One PathConnectedNet row split into its halves, ActNorm initialised, flows away from the identity; the module itself."""
+    from awesome_amd.prior_bank import _ordered_parameters
+    torch.manual_seed(seed)
+    m = _pcn_factory(h, layers, channels=C_in)().to(dev)
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(seed)
+        for name, p in m.named_parameters():
+            if ".net.2." in name:
+                p.add_((0.05 * torch.randn(p.shape, generator=g)).to(dev))
+        for b_name, b in m.named_buffers():
+            if b_name.endswith("data_dep_init_done"):
+                b.fill_(1.0)
+    ispec, rspec = m._specs()
+    flat = torch.cat([p.detach().reshape(-1) for p in _ordered_parameters(m)]).clone()
+    return m, ispec, rspec, flat
+
+
+@pytest.mark.parametrize("C_in,clip", [(3, True), (3, False), (2, True)])
+def test_pcn_wide_joint_step_call(dev, C_in, clip):
+    """The entry point itself at C = 3 (and C = 2): one FBMS step against the module's own autograd step (differentiable deformation
+    + the ICNN, torch.optim.Adam, enforce_convexity) - loss, d loss / d seg, both halves' parameters and moments."""
+    import awesome_amd as A
+    from awesome_amd import joint as J
+    from awesome_amd.prior_bank import _ordered_parameters
+    m, ispec, rspec, flat = _pcn_rows(dev, C_in, 136, 1, 11 + C_in)
+    P = ispec.n_params
+    g = torch.Generator().manual_seed(21)
+    seg, tgt = _seg_target(g)
+    coords = (O.positional_grid(W, H) if C_in == 2 else O.positional_grid(W, H, 0.37, 1.0)).to(dev)
+    beta = 40.0 if clip else 0.05
+    crit = _fbms(beta)
+    # the module's autograd step
+    params = list(_ordered_parameters(m))
+    opt_t = torch.optim.Adam(params, lr=LR)
+    seg_t = seg.to(dev).requires_grad_(True)
+    prior = torch.sigmoid(m(coords[None]).reshape(-1))
+    loss = crit(torch.stack([seg_t, prior]).reshape(1, 2, H, W), tgt.to(dev).reshape(1, 1, H, W))
+    loss.backward()
+    opt_t.step()
+    m.enforce_convexity()
+    ref_row = torch.cat([p.detach().reshape(-1) for p in params]).cpu()
+    ref_m = torch.cat([opt_t.state[p]["exp_avg"].reshape(-1) for p in params]).cpu()
+    ref_v = torch.cat([opt_t.state[p]["exp_avg_sq"].reshape(-1) for p in params]).cpu()
+    # the fused step
+    row = flat.clone()
+    iopt = torch.zeros(2 * P + 8, device=dev)
+    fopt = torch.zeros(2 * rspec.n_params, device=dev)
+    res = J.pcn_wide_joint_step(ispec, rspec, row[:P], row[P:], iopt, fopt, A.Grid.explicit(coords.reshape(C_in, -1).contiguous()),
+                                seg.to(dev), tgt.to(dev), crit.joint_desc(), step=1, lr=LR)
+    assert int(res.status[0]) == 0
+    assert (0.0 < float(res.loss[3]) < 1.0) == clip
+    np.testing.assert_allclose(float(res.loss[0]), float(loss), rtol=2e-5)
+    ds_ref = seg_t.grad.cpu().numpy()
+    np.testing.assert_allclose(res.dseg.cpu().numpy(), ds_ref, rtol=5e-5, atol=1e-7 * float(np.abs(ds_ref).max()))
+    np.testing.assert_allclose(row.cpu().numpy(), ref_row.numpy(), rtol=1e-3, atol=2e-5)
+    Pf = rspec.n_params
+    got_m = torch.cat([iopt[:P], fopt[:Pf]]).cpu().numpy()
+    got_v = torch.cat([iopt[P:2 * P], fopt[Pf:2 * Pf]]).cpu().numpy()
+    np.testing.assert_allclose(got_m, ref_m.numpy(), rtol=1e-3, atol=2e-5 * float(ref_m.abs().max()))
+    np.testing.assert_allclose(got_v, ref_v.numpy(), rtol=1e-3, atol=2e-5 * float(ref_v.abs().max()))
+    assert not torch.equal(row[P:], flat[P:])          # the flow half stepped
+
+
+@pytest.mark.parametrize("prior,crit", [("icnn_136x1", "fbms"), ("icnn_144x3", "image"), ("pcn_136x1", "fbms")])
+def test_joint_trainer_fused_layer_by_layer_matches_the_default_trainer(dev, prior, crit):
+    """Six steps on two images: JointTrainer(fused_layer_by_layer=True) takes the fused path, the default trainer the autograd step;
+    losses, backbone weights, every bank row and the moments agree."""
+    kind, shape = prior.split("_")
+    h, layers = map(int, shape.split("x"))
+    factory = _pcn_factory(h, layers) if kind == "pcn" else _icnn_factory(h, layers)
+    make = (lambda: _fbms(2.0)) if crit == "fbms" else (lambda: _image_loss(alpha=0.7))
+    f = _run(dev, factory, make(), True, [(6, False)], flow=kind == "pcn")
+    a = _run(dev, factory, make(), False, [(6, False)], flow=kind == "pcn")
+    assert f[3] == ["fused"] * 6 and f[5]._path == "fused" and f[5].fused is True
+    assert a[3] == ["autograd"] * 6 and a[5].fused is False
+    _assert_same(f, a)
+
+
+def test_route_switch_in_mid_run_carries_the_moments(dev):
+    """AwesomeImageLoss, the penalty hook firing after three steps WITHOUT fused_extra_penalty: three fused layer-by-layer steps, then
+    three autograd steps, then (penalty off again) two fused ones - the pure autograd run's trajectory (moment hand-over both ways)."""
+    sched = [(3, False), (3, True), (2, False)]
+    f = _run(dev, _icnn_factory(136, 1), _image_loss(alpha=0.7), True, sched)
+    a = _run(dev, _icnn_factory(136, 1), _image_loss(alpha=0.7), False, sched)
+    assert f[3] == ["fused"] * 3 + ["autograd"] * 3 + ["fused"] * 2 and a[3] == ["autograd"] * 8
+    _assert_same(f, a)
+
+
+def test_fused_true_with_the_switch_no_longer_raises(dev):
+    from awesome_amd.agent import JointTrainer
+    from awesome_amd.model import ConvexDiffeomorphismNet, ConvexNextNet, WrapperModule
+    from awesome_amd.prior_bank import PriorBank, _ordered_parameters
+
+    def trainer(factory, **kw):
+        wrapper = WrapperModule(_SegStandIn(), factory()).to(dev)
+        bank = PriorBank(lambda: factory().to(dev), n_images=1, device=dev)
+        opt = torch.optim.Adam(list(wrapper.segmentation_module.parameters()) + list(_ordered_parameters(wrapper.prior_module)), lr=1e-3)
+        return JointTrainer(wrapper, bank, _fbms(1.0), opt, **kw)
+
+    wide = lambda: ConvexNextNet(n_hidden=256, in_features=2, n_hidden_layers=1)   # noqa: E731
+    assert trainer(wide, fused=True, fused_layer_by_layer=True).fused is True
+    with pytest.raises(ValueError, match="no fused joint step"):
+        trainer(wide, fused=True)
+    cdn = lambda: ConvexDiffeomorphismNet(n_hidden=144, n_hidden_layers=1, nf_layers=4, nf_hidden=24,   # noqa: E731
+                                          diffeo_args=dict(backbone="normal_block"))
+    assert trainer(cdn, fused_layer_by_layer=True).fused is False       # out of scope: stays on autograd
+
+
+# ---- 4. a non-finite loss, determinism, the config --------------------------------------------------------------------------------
+def test_nan_in_seg_freezes_the_row(dev):
+    """status 1, parameters and moments bit-equal to before - ICNN row, and both halves of the path-connected row."""
+    import awesome_amd as A
+    from awesome_amd import joint as J
+    spec = A.IcnnSpec(n_hidden=136, in_features=2, n_layers=1)
+    p0, g = _state(spec, 7)
+    seg, tgt = _seg_target(g)
+    seg, tgt = seg.to(dev), tgt.to(dev)
+    grid = A.Grid.from_image_grid(O.positional_grid(W, H)[None].to(dev))
+    row0 = A.pack_state_dict(spec, p0, dev).clone()
+    opt0 = torch.zeros(2 * spec.n_params + 8, device=dev)
+    desc = J.joint_desc(alpha=1.0, beta=2.0)
+    J.wide_joint_step(spec, row0, opt0, grid, seg, tgt, desc, step=1, lr=LR)      # one good step: non-zero moments
+    bad = seg.clone()
+    bad[11] = float("nan")
+    row, opt = row0.clone(), opt0.clone()
+    res = J.wide_joint_step(spec, row, opt, grid, bad, tgt, desc, step=2, lr=LR)
+    P = spec.n_params
+    assert int(res.status[0]) == 1 and torch.equal(row, row0) and torch.equal(opt[:2 * P], opt0[:2 * P])
+    assert float(res.dseg.abs().sum()) == 0.0 and not bool(torch.isfinite(res.loss[0]))       # a frozen step: no gradient for the backbone
+    good = J.wide_joint_step(spec, row.clone(), opt.clone(), grid, seg, tgt, desc, step=2, lr=LR)
+    assert int(good.status[0]) == 0 and float(good.dseg.abs().sum()) > 0.0
+    pd = J.joint_prior_desc(align_rule=2, beta=3.0)
+    row, opt = row0.clone(), opt0.clone()
+    res = J.wide_joint_prior_step(spec, row, opt, grid, bad, tgt, pd, step=2, lr=LR)   # soft align: the NaN reaches the share
+    assert int(res.status[0]) == 1 and torch.equal(row, row0) and torch.equal(opt[:2 * P], opt0[:2 * P])
+    assert float(res.dseg.abs().sum()) == 0.0
+    row, opt = row0.clone(), opt0.clone()                                               # a NaN segmentation share freezes it as well
+    res = J.wide_joint_prior_step(spec, row, opt, grid, seg, tgt, pd, step=2, lr=LR, seg_term=torch.tensor([float("nan")], device=dev))
+    assert int(res.status[0]) == 1 and torch.equal(row, row0) and torch.equal(opt[:2 * P], opt0[:2 * P])
+    assert float(res.dseg.abs().sum()) == 0.0
+
+    m, ispec, rspec, flat = _pcn_rows(dev, 2, 136, 1, 13)
+    P = ispec.n_params
+    coords = A.Grid.explicit(O.positional_grid(W, H).reshape(2, -1).contiguous().to(dev))
+    iopt0, fopt0 = torch.zeros(2 * P + 8, device=dev), torch.zeros(2 * rspec.n_params, device=dev)
+    r0 = flat.clone()
+    J.pcn_wide_joint_step(ispec, rspec, r0[:P], r0[P:], iopt0, fopt0, coords, seg, tgt, desc, step=1, lr=LR)
+    r, iopt, fopt = r0.clone(), iopt0.clone(), fopt0.clone()
+    res = J.pcn_wide_joint_step(ispec, rspec, r[:P], r[P:], iopt, fopt, coords, bad, tgt, desc, step=2, lr=LR)
+    assert int(res.status[0]) == 1 and torch.equal(r, r0) and torch.equal(iopt[:2 * P], iopt0[:2 * P]) and torch.equal(fopt, fopt0)
+    assert float(res.dseg.abs().sum()) == 0.0
+    assert not torch.equal(r0, flat) and float(fopt0.abs().sum()) > 0
+
+
+def test_nan_in_seg_through_the_trainer_latches_the_failure(dev):
+    """Through the trainer with a torch backbone that produces the NaN itself: the row is frozen, the failure latched,
+    raise_if_failed raises.  (The backbone's zero gradient: test_nan_with_the_hip_segmentation_share_zeroes_the_backbone_gradient.)"""
+    from awesome_amd.agent import JointTrainer
+    from awesome_amd.dataset import SyntheticPriorDataset
+    from awesome_amd.model import WrapperModule
+    from awesome_amd.prior_bank import PriorBank, _ordered_parameters
+
+    class NanSeg(_SegStandIn):
+        def forward(self, image, *a, **k):
+            out = self.conv(image)
+            return out + torch.where(torch.arange(out.numel(), device=out.device).view_as(out) == 5, float("nan"), 0.0)
+
+    torch.manual_seed(5)
+    ds = SyntheticPriorDataset(n_images=1, size=24, kind="noisy_blob")
+    (image, _, xy), target = ds[0]
+    factory = _icnn_factory(136, 1)
+    wrapper = WrapperModule(NanSeg(), factory(), use_segmentation_output_inversion=True).to(dev)
+    bank = PriorBank(lambda: factory().to(dev), n_images=1, device=dev)
+    bank.row(0)
+    opt = torch.optim.Adam(list(wrapper.segmentation_module.parameters()) + list(_ordered_parameters(wrapper.prior_module)), lr=1e-2)
+    tr = JointTrainer(wrapper, bank, _fbms(2.0), opt, fused=True, fused_layer_by_layer=True)
+    before = bank.params.detach().clone()
+    tr.perform_step(0, (image[None].to(dev), torch.zeros(1, 1, 1, 1, device=dev), xy[None].to(dev)), target[None].to(dev))
+    assert tr._path == "fused" and int(tr.last_status[0]) == 1 and torch.equal(bank.params, before)
+    with pytest.raises(ValueError, match="Loss is nan or inf!"):
+        tr.raise_if_failed()
+
+
+def _run_convexity(dev, fused, steps, hook, hip_share=False, nan=False, Hc=40, Wc=44):
+    """The trainer's `convexity` route over ConvexNextNet 136 x 1: AwesomeImageLossJoint (soft align: d(prior's share) / d seg goes back
+    to the backbone) on a CNNNet backbone, the extra-penalty hook firing at step `hook`.  fused: fused_convexity_losses +
+    fused_layer_by_layer (+ fused_segmentation with hip_share); else the autograd step.  Problem and criterion: tests/test_gpu_cnnseg.py's."""
+    from awesome_amd.agent import JointTrainer
+    from awesome_amd.model import WrapperModule
+    from awesome_amd.prior_bank import PriorBank, _ordered_parameters
+    from tests import test_gpu_cnnseg as TC
+    net = TC._net(2, seed=7)
+    torch.manual_seed(11)
+    factory = _icnn_factory(136, 1)
+    wrapper = WrapperModule(net, factory(), use_segmentation_output_inversion=True).to(dev)
+    bank = PriorBank(lambda: factory().to(dev), n_images=2, device=dev)
+    for k in range(2):
+        bank.row(k)
+    items = []
+    for k in range(2):
+        image, feat, t, _ = TC._problem(Hc, Wc, 2, 2.0, seed=20 + k)
+        if nan and k == 0:
+            image[0, 0, 3, 4] = float("nan")
+        xy = O.positional_grid(Wc, Hc)[None]
+        items.append(((image.to(dev).requires_grad_(True), feat.to(dev).requires_grad_(True), xy.to(dev)), t.to(dev)))
+    rows0 = bank.params.detach().cpu().clone()
+    opt = torch.optim.Adam(list(net.parameters()) + list(_ordered_parameters(wrapper.prior_module)), lr=1e-3)
+    crit = TC._loss("joint", "xy")
+    tr = JointTrainer(wrapper, bank, crit, opt, fused=fused, fused_convexity_losses=True, fused_layer_by_layer=fused,
+                      fused_segmentation=fused and hip_share)
+    losses, paths = [], []
+    for s in range(steps):
+        crit.extra_penalty = s >= hook
+        inputs, target = items[s % 2]
+        loss, _ = tr.perform_step(s % 2, inputs, target)
+        losses.append(float(loss))
+        paths.append(tr._path)
+    return dict(losses=losses, paths=paths, rows=bank.params.detach().cpu().clone(), rows0=rows0, tr=tr, net=net,
+                seg_w=torch.cat([p.detach().reshape(-1) for p in net.parameters()]).cpu(), mom=_moments(tr, opt, wrapper.prior_module))
+
+
+@pytest.mark.parametrize("hip_share", [False, True], ids=["torch_share", "hip_share"])
+def test_joint_trainer_convexity_route_with_the_switch_matches_autograd(dev, hip_share):
+    """Six steps on two images, the hook firing at step 3: _perform_step_prior_share dispatches to inrfit_wide_joint_prior_step (with
+    the torch and with the HIP segmentation share), every step fused; losses, backbone weights (they see the soft align's dseg), rows
+    and moments match the autograd run.  Bars: this route's own, tests/test_gpu_joint_convexity.py::_assert_same."""
+    f = _run_convexity(dev, True, 6, 3, hip_share=hip_share)
+    a = _run_convexity(dev, False, 6, 3)
+    assert f["paths"] == ["fused"] * 6 and a["paths"] == ["autograd"] * 6 and f["tr"]._fused_plan["wide"]
+    assert (f["tr"].cnnseg_status is not None) == hip_share
+    np.testing.assert_allclose(f["losses"], a["losses"], rtol=2e-5, atol=1e-7)
+    np.testing.assert_allclose(f["seg_w"].numpy(), a["seg_w"].numpy(), rtol=2e-4, atol=2e-6)
+    np.testing.assert_allclose(f["rows"].numpy(), a["rows"].numpy(), rtol=1e-3, atol=2e-5)
+    np.testing.assert_allclose(f["mom"].numpy(), a["mom"].numpy(), rtol=1e-3, atol=2e-4 * float(a["mom"].abs().max()))
+    assert not torch.equal(f["rows"], f["rows0"])
+
+
+def test_nan_with_the_hip_segmentation_share_zeroes_the_backbone_gradient(dev):
+    """A NaN in image 0, fused_segmentation + fused_convexity_losses + fused_layer_by_layer: status 1, the row and its moments
+    untouched, and the backbone gets a zero gradient - every .grad is exactly zero and every weight stays finite."""
+    r = _run_convexity(dev, True, 1, 5, hip_share=True, nan=True)
+    tr = r["tr"]
+    assert r["paths"] == ["fused"] and int(tr.last_status[0]) == 1 and int(tr.cnnseg_status[0]) == 1 and bool(tr.failed)
+    assert torch.equal(r["rows"], r["rows0"]) and float(r["mom"].abs().sum()) == 0.0
+    for p in r["net"].parameters():
+        assert p.grad is not None and float(p.grad.abs().sum()) == 0.0 and bool(torch.isfinite(p).all())
+    with pytest.raises(ValueError, match="Loss is nan or inf!"):
+        tr.raise_if_failed()
+
+
+@pytest.mark.parametrize("which", ["icnn", "prior", "pcn"])
+def test_two_identical_calls_give_identical_bits(dev, which):
+    import awesome_amd as A
+    from awesome_amd import joint as J
+    g = torch.Generator().manual_seed(9)
+    seg, tgt = _seg_target(g)
+    seg, tgt = seg.to(dev), tgt.to(dev)
+    spec = A.IcnnSpec(n_hidden=200, in_features=2, n_layers=1)
+    p0, _ = _state(spec, 9)
+    grid = A.Grid.from_image_grid(O.positional_grid(W, H)[None].to(dev))
+    m, ispec, rspec, flat = _pcn_rows(dev, 2, 144, 3, 17)
+
+    def run():
+        outs = []
+        if which == "pcn":
+            P = ispec.n_params
+            row, iopt, fopt = flat.clone(), torch.zeros(2 * P + 8, device=dev), torch.zeros(2 * rspec.n_params, device=dev)
+            coords = A.Grid.explicit(O.positional_grid(W, H).reshape(2, -1).contiguous().to(dev))
+            for t in (1, 2, 3):
+                r = J.pcn_wide_joint_step(ispec, rspec, row[:P], row[P:], iopt, fopt, coords, seg, tgt, J.joint_desc(beta=40.0), step=t, lr=LR)
+                outs += [r.loss.clone(), r.dseg.clone(), r.prior_logits.clone()]
+            return outs + [row, iopt, fopt]
+        row, opt = A.pack_state_dict(spec, p0, dev).clone(), torch.zeros(2 * spec.n_params + 8, device=dev)
+        for t in (1, 2, 3):
+            if which == "icnn":
+                r = J.wide_joint_step(spec, row, opt, grid, seg, tgt, J.joint_desc(beta=40.0), step=t, lr=LR)
+            else:
+                r = J.wide_joint_prior_step(spec, row, opt, grid, seg, tgt, J.joint_prior_desc(align_rule=2, beta=3.0, align_begin=7),
+                                            step=t, lr=LR)
+            outs += [r.loss.clone(), r.dseg.clone(), r.prior_logits.clone()]
+        return outs + [row, opt]
+
+    for x, y in zip(run(), run()):
+        assert torch.equal(x, y)
+
+
+def test_fused_shapes_and_encode_shapes_are_refused(dev):
+    import awesome_amd as A
+    from awesome_amd import _lib as L
+    from awesome_amd import joint as J
+    g = torch.Generator().manual_seed(1)
+    seg, tgt = _seg_target(g)
+    grid = A.Grid.from_image_grid(O.positional_grid(W, H)[None].to(dev))
+    for spec in (A.IcnnSpec(n_hidden=130, in_features=2, n_layers=1), A.IcnnSpec(n_hidden=64, in_features=2, n_layers=1, act0="cos", n_out=2)):
+        row, opt = torch.zeros(spec.n_params, device=dev), torch.zeros(2 * spec.n_params + 8, device=dev)
+        with pytest.raises(L.InrfitError):
+            J.wide_joint_step(spec, row, opt, grid, seg.to(dev), tgt.to(dev), J.joint_desc(), step=1, lr=LR)
+
+
+def test_run_py_refine_noisy256_wide256(tmp_path):
+    """config/c5_refine_noisy256_wide256.yaml through scripts/run.py at size 32 with a handful of epochs: every joint step fused."""
+    override = {"dataset_args": {"n_images": 2, "size": 32},
+                "agent_args": {"joint_epochs": 3, "pretrain_args": {"num_epochs": 40, "prefit_flow_net_identity_num_epochs": 10,
+                                                                    "prefit_convex_net_num_epochs": 10, "proper_prior_fit_retrys": 0}}}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "run.py"), "--config-path",
+                          os.path.join(ROOT, "config", "c5_refine_noisy256_wide256.yaml"), "--output-folder", str(tmp_path),
+                          "--override", json.dumps(override)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    summary = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert summary["images"] == 2 and summary["joint_steps_fused"] == 2 * 3, summary
+    assert all(np.isfinite(summary["joint_loss_first_last"])), summary
