@@ -660,10 +660,10 @@ struct FlowUpdArgs {
     int mode;             // 0 = Adam step + effective weights, 1 = gradients only, 2 = effective weights only (prep)
     const int32_t* status;   // per image (mode 0): frozen by a non-finite loss -> no step, like the ICNN and RealNVP updates
     const float* gscale;     // [n_images] factor on every reduced gradient (the joint step's detached clip factor), or null
-    // set when the ICNN update of the same optimizer step runs in the SAME launch (cdn_update_kernel): the loss column of its slabs
-    const float* loss_slabs;   // slab entry "loss" of image 0, workgroup 0 (stride loss_PS per workgroup, loss_wgs * loss_PS per image)
+    // set when the ICNN update of the same optimizer step runs in the SAME launch (cdn_update_kernel): its step kernel's loss partials
+    const float* loss_part;    // loss partial of image 0, workgroup 0 (stride loss_stride per workgroup, loss_wgs * loss_stride per image)
     int loss_wgs;
-    long long loss_PS;
+    long long loss_stride;
 };
 
 // fixed-order sum over the first 256 threads of a block (tid = linear thread index; those 256 threads are waves 0-3)
@@ -676,30 +676,32 @@ __device__ __forceinline__ float block_sum256(float v, float* sm, const int tid)
 }
 __device__ __forceinline__ float block_sum256(float v, float* sm) { return block_sum256(v, sm, threadIdx.x); }
 
-// The loss of one image = the sum of the loss column over its slabs, in the order icnn_update_kernel uses: 16 groups (group g takes the
+// The loss of one image = the sum of its workgroups' loss partials, in the order icnn_update_kernel uses: 16 groups (group g takes the
 // workgroups g, g + 16, ...), then the groups in order.  One definition for every kernel that needs the "non-finite loss" decision.
+// `sl` = the partial of workgroup 0, `stride` = floats from one workgroup's partial to the next: 1 for the step kernels' dense copy
+// (StepArgs::loss_part: 256 partials are 8 lines), the slab stride for a loss column read in place (the one-slab views of wide.h).
 constexpr int LOSS_GROUPS = 16;
-__device__ __forceinline__ float loss_column_group_sum(const float* __restrict__ sl, const int wgs, const size_t PS, const int grp) {
+__device__ __forceinline__ float loss_column_group_sum(const float* __restrict__ sl, const int wgs, const size_t stride, const int grp) {
     float lp = 0.f;
     int w = grp;
     for (; w + 15 * LOSS_GROUPS < wgs; w += 16 * LOSS_GROUPS) {   // 256 slabs: one trip, 16 loads in flight
         float q[16];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) q[k] = sl[(size_t)(w + k * LOSS_GROUPS) * PS];
+        for (int k = 0; k < 16; ++k) q[k] = sl[(size_t)(w + k * LOSS_GROUPS) * stride];
 #pragma unroll
         for (int k = 0; k < 16; ++k) lp += q[k];
     }
-    for (; w < wgs; w += LOSS_GROUPS) lp += sl[(size_t)w * PS];
+    for (; w < wgs; w += LOSS_GROUPS) lp += sl[(size_t)w * stride];
     return lp;
 }
 
 // "this image takes no optimizer step" exactly as the ICNN update of the same launch decides it: frozen by an earlier step (the flag
 // the PREVIOUS launch wrote, hdr[6 + (t & 1)]) or a non-finite loss now.  Called by the first 256 threads of a block.
-__device__ __forceinline__ bool frozen_in_launch(const float* __restrict__ loss_slabs, const int wgs, const long long PS,
+__device__ __forceinline__ bool frozen_in_launch(const float* __restrict__ loss_part, const int wgs, const long long stride,
                                                  const float* __restrict__ hdr0, const long long hdr_stride, const int t, const int img,
                                                  const int tid) {
     __shared__ float redl[LOSS_GROUPS];
-    if (tid < LOSS_GROUPS) redl[tid] = loss_column_group_sum(loss_slabs + (size_t)img * wgs * PS, wgs, (size_t)PS, tid);
+    if (tid < LOSS_GROUPS) redl[tid] = loss_column_group_sum(loss_part + (size_t)img * wgs * stride, wgs, (size_t)stride, tid);
     __syncthreads();
     float loss_now = 0.f;
 #pragma unroll
@@ -733,8 +735,8 @@ __device__ __forceinline__ void flow_update_body(const FlowUpdArgs& u, const int
     // into the header's double buffer (hdr[6 + ((t + 1) & 1)], one launch earlier on this stream; `status` may be NULL) - or, when
     // that update runs in THIS launch (cdn_update_kernel), the same decision from the same numbers (frozen_in_launch).
     const bool frozen = !isfinite(gmul) ||    // the joint step's composite loss was not finite (joint_step_finish_kernel)
-                        ((u.mode == 0 && u.loss_slabs != nullptr)
-                             ? frozen_in_launch(u.loss_slabs, u.loss_wgs, u.loss_PS, u.lr_hdr, u.hdr_stride, u.t, img, tid)
+                        ((u.mode == 0 && u.loss_part != nullptr)
+                             ? frozen_in_launch(u.loss_part, u.loss_wgs, u.loss_stride, u.lr_hdr, u.hdr_stride, u.t, img, tid)
                              : ((u.lr_hdr != nullptr && u.lr_hdr[(size_t)img * u.hdr_stride + 6 + ((u.t + 1) & 1)] != 0.f) ||
                                 (u.status != nullptr && u.status[img] != INR_STATUS_OK)));
     const int mode = (u.mode == 0 && frozen) ? 2 : u.mode;

@@ -246,6 +246,7 @@ struct StepArgs {
     const float* targets;  // [n_images][N]            (TRAIN)
     const float* coef;     // [n_images][2] c_fg, c_bg (TRAIN)
     float* slabs;          // [n_images][wgs][PS]      (TRAIN)
+    float* loss_part;      // [n_images][wgs] the workgroups' loss partials once more, dense (TRAIN): what the update kernels' "frozen" decision reads
     float* logits;         // [n_images][N] or null
     float* dcoords;        // [n_images][C][N] dL/dcoords (DX kernels only)
     InrGridDesc grid;
@@ -1057,8 +1058,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         }
         if (tid < 2 + C) {
             const float v = wsum(SC_SC + tid);
-            if (tid == 0) slab[G::SL_LOSS] = v;  // loss partial
-            else if (tid == 1) slab[G::slab_col(G::P_BO)] = v;
+            if (tid == 0) {
+                slab[G::SL_LOSS] = v;  // loss partial
+                a.loss_part[(size_t)img * a.wgs + wg] = v;
+            } else if (tid == 1) slab[G::slab_col(G::P_BO)] = v;
             else slab[G::slab_col(G::P_SO) + tid - 2] = v;
         }
     }

@@ -780,8 +780,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn2_step_kernel(const StepArg
         }
         if (tid < 2 + C) {
             const float v = wsum(SC_SC + tid);
-            if (tid == 0) slab[G::SL_LOSS] = v;
-            else if (tid == 1) slab[G::SL_WO + (G::P_BO - G::P_WO)] = v;
+            if (tid == 0) {
+                slab[G::SL_LOSS] = v;
+                a.loss_part[(size_t)img * a.wgs + wg] = v;
+            } else if (tid == 1) slab[G::SL_WO + (G::P_BO - G::P_WO)] = v;
             else slab[G::SL_WO + (G::P_SO - G::P_WO) + tid - 2] = v;
         }
     }

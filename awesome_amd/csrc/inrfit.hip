@@ -47,6 +47,8 @@ struct UpdArgs {
     float* params;        // [n_images][P]
     float* opt_state;     // [n_images][2P + HDR]
     const float* slabs;   // [n_images][wgs][PS]
+    const float* loss_part;    // the workgroups' loss partials, [n_images][wgs] at stride loss_stride: the step kernels' dense copy
+    long long loss_stride;     // (stride 1, Workspace::loss_part), or the loss column of a one-slab view in place (stride PS)
     float* loss_hist;     // [n_images][steps] or null
     float* grads_out;     // mode 1: [n_images][P]
     float* loss_out;      // mode 1: [n_images]
@@ -111,22 +113,39 @@ __host__ __device__ __forceinline__ int user_param_index(const ImgMap& m, int h,
 constexpr int UPD_MAX_PARAMS = 256;  // most parameters per block
 constexpr int UPD_GROUPS = 16;       // slab groups summed in parallel, then combined in fixed order
 
-// Parameters per block: a CU pulls ~10 B/clock from memory whatever runs on it, so the reduction is as fast as its busiest
-// CU: one block per CU, all equally long (17 814 parameters -> 248 blocks of 72), instead of 279 blocks of 64 with 23 CUs
-// doing double duty.  Multiple of 4 (float4 loads), x n_images blocks when there are many images.
+constexpr int UPD_LINE = 32;         // slab columns per 128-byte line (slab rows start on lines: carve)
+
+// Which slab columns a block owns.  A CU pulls ~10 B/clock from memory whatever runs on it, so the reduction is as fast as its busiest
+// CU, and what a CU pulls is whole lines: every block owns whole lines (its first column is a multiple of 32), so no line is taken in
+// by two blocks - neighbours sit on different XCDs, which fetched a shared line twice - and a block takes in what it sums and nothing
+// else.  One block per CU: the first n_wide blocks own ppb columns, the others one line less (the headline's 19 222 columns = 601
+// lines -> 89 blocks of 96 + 167 of 64; DESIGN.md 4.3 lists the uniform splits, which INRFIT_UPD_LINES runs).  More than 8 lines per CU, or
+// fewer lines than CUs: equal blocks of 8 lines / of one line.  x n_images blocks when there are many images.
 // `reserve` = CUs left to other blocks of the same launch (the deformation's update in cdn_/pcn_update_kernel).
-inline int upd_params_per_block(int cols, int reserve = 0) {   // cols = slab columns in use (P + 1 in the parameter-ordered layout)
-    const int cus = 256 - reserve;
-    int ppb = ((cols + cus - 1) / cus + 3) / 4 * 4;
-    if (ppb < 16) ppb = 16;
-    if (ppb > UPD_MAX_PARAMS) ppb = UPD_MAX_PARAMS;
-    return ppb;
+struct UpdSplit {
+    int ppb;       // columns of a wide block (multiple of 32, <= UPD_MAX_PARAMS); blockDim.x = ppb / 4
+    int n_wide;    // blocks [0, n_wide) own ppb columns, blocks [n_wide, blocks) ppb - 32
+    int blocks;
+};
+inline UpdSplit upd_split(int cols, int reserve = 0) {   // cols = slab columns in use (P + 1 in the parameter-ordered layout)
+    static const int forced = getenv("INRFIT_UPD_LINES") ? atoi(getenv("INRFIT_UPD_LINES")) : 0;   // measurement switch: equal blocks of n lines
+    const int cus = 256 - reserve, lines = (cols + UPD_LINE - 1) / UPD_LINE, max_lpb = UPD_MAX_PARAMS / UPD_LINE;
+    int lpb = forced > 0 ? forced : (lines + cus - 1) / cus;
+    if (lpb < 1) lpb = 1;
+    if (lpb > max_lpb) lpb = max_lpb;
+    UpdSplit sp;
+    sp.ppb = lpb * UPD_LINE;
+    if (forced > 0 || lpb == 1 || lines >= lpb * cus) {
+        sp.blocks = (lines + lpb - 1) / lpb;
+        sp.n_wide = sp.blocks;
+    } else {
+        sp.blocks = cus;
+        sp.n_wide = lines - (lpb - 1) * cus;
+    }
+    return sp;
 }
-inline dim3 upd_grid(int cols, int n_images, int reserve = 0) {
-    const int ppb = upd_params_per_block(cols, reserve);
-    return dim3((cols + ppb - 1) / ppb, n_images);
-}
-inline dim3 upd_block(int cols, int reserve = 0) { return dim3(upd_params_per_block(cols, reserve) / 4, UPD_GROUPS); }
+inline dim3 upd_grid(int cols, int n_images, int reserve = 0) { return dim3(upd_split(cols, reserve).blocks, n_images); }
+inline dim3 upd_block(int cols, int reserve = 0) { return dim3(upd_split(cols, reserve).ppb / 4, UPD_GROUPS); }
 
 #if INR_STAMPS
 __device__ unsigned long long g_updtimes[512][4];   // per block of the LAST update launch, s_memrealtime (100 MHz): entry, slab loads back, reduced, stores done
@@ -138,16 +157,19 @@ __device__ unsigned long long g_updtimes[512][4];   // per block of the LAST upd
 #else
 #define UPD_STAMP(k)
 #endif
-// block = (blockDim.x lanes x float4 = ppb parameters) x 16 slab groups; bx = the block's index along the slab columns
+// block = (blockDim.x lanes x float4 = the columns of a wide block) x 16 slab groups; bx = the block's index along the slab columns,
+// n_wide = UpdSplit::n_wide (in a narrow block the last 8 lanes of every group have nothing to load)
 static_assert(UPD_GROUPS == LOSS_GROUPS, "the loss column is summed in the update's group order");
-__device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx, const int img) {
+__device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx, const int img, const int n_wide) {
     const int tx = threadIdx.x, grp = threadIdx.y;
-    const int ppb = 4 * blockDim.x;
+    const int ppbw = 4 * blockDim.x;
+    const int ppb = bx < n_wide ? ppbw : ppbw - UPD_LINE;                               // this block's columns ...
+    const int col0 = bx < n_wide ? bx * ppbw : bx * (ppbw - UPD_LINE) + n_wide * UPD_LINE;   // ... and the first of them
     __shared__ float red[UPD_GROUPS][UPD_MAX_PARAMS];
-    __shared__ float redl[UPD_GROUPS];     // this step's loss partials (every block sums them: see `frozen` below)
+    __shared__ float redl[UPD_GROUPS];     // this step's loss partials (every block sums them, from u.loss_part: see `frozen` below)
     UPD_STAMP(0);
     const int jl = grp * blockDim.x + tx;  // the first ppb threads finish one slab column = one parameter each
-    const int j = jl < ppb ? slab_param_of_col(u.img, bx * ppb + jl) : -1;   // flat parameter index (kernel shape), P = loss, -1 = none
+    const int j = jl < ppb ? slab_param_of_col(u.img, col0 + jl) : -1;   // flat parameter index (kernel shape), P = loss, -1 = none
     const int ju = (j >= 0 && j < u.P) ? user_param_index(u.img, u.hu, j) : -1;       // ... in the caller's layout; -1: padding (gradient exactly 0)
     // The kernel is one dependent chain (slabs -> LDS -> optimizer -> stores) and at one image it is latency, not bandwidth,
     // that it pays for: everything the tail needs is requested up front, and all slab rows of a thread are in flight at once.
@@ -165,9 +187,9 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
         }
     }
     {
-        const int j4 = bx * ppb + 4 * tx;
+        const int j4 = col0 + 4 * tx;
         f32x4 part = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (j4 < u.PS && slab_param_of_col(u.img, j4) >= 0) {   // (a lane's 4 tile registers are parameters or padding together)
+        if (4 * tx < ppb && j4 < u.PS && slab_param_of_col(u.img, j4) >= 0) {   // (a lane's 4 tile registers are parameters or padding together)
             const float* __restrict__ sl = u.slabs + (size_t)img * u.wgs * u.PS + j4;
             int w = grp;
             for (; w + 15 * UPD_GROUPS < u.wgs; w += 16 * UPD_GROUPS) {   // 256 slabs: one trip, 16 loads in flight
@@ -180,8 +202,8 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
             for (; w < u.wgs; w += UPD_GROUPS) part += *(const f32x4*)(sl + (size_t)w * u.PS);
         }
         *(f32x4*)&red[grp][4 * tx] = part;
-        if (u.mode == 0 && tx == 0) {   // the loss column (slab entry P), summed in the same order as any parameter column
-            redl[grp] = loss_column_group_sum(u.slabs + (size_t)img * u.wgs * u.PS + (u.img.sl_cols - 1), u.wgs, (size_t)u.PS, grp);
+        if (u.mode == 0 && tx == 0) {   // the loss partials, summed in the same order as any parameter column
+            redl[grp] = loss_column_group_sum(u.loss_part + (size_t)img * u.wgs * u.loss_stride, u.wgs, (size_t)u.loss_stride, grp);
         }
     }
     UPD_STAMP(1);
@@ -284,19 +306,19 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
     UPD_STAMP(3);
 }
 
-__global__ __launch_bounds__(UPD_MAX_PARAMS / 4 * UPD_GROUPS) void icnn_update_kernel(const UpdArgs u) { icnn_update_body(u, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(UPD_MAX_PARAMS / 4 * UPD_GROUPS) void icnn_update_kernel(const UpdArgs u, const int n_wide) { icnn_update_body(u, blockIdx.x, blockIdx.y, n_wide); }
 
 // Both optimizer updates of a composite step (ICNN + its deformation) in ONE launch.  They are independent - the ICNN update reads the
 // step kernel's slabs, the deformation's update the unit / point slabs of its backward kernels - and each alone is a latency chain that
 // leaves most of the chip idle (the flow / RealNVP update has 2K + 1 / F + 1 blocks): blocks [0, nbi) of a grid row are the ICNN
 // update's, the rest the deformation's (its 256 threads = the first four waves of the block; the other waves leave at once, which
 // s_barrier allows).  A CU holds one of these blocks (12 waves at up to 168 registers), so the ICNN update leaves the deformation's
-// blocks their own CUs (`reserve` of upd_params_per_block): measured with 248 + 13 blocks the two parts ran one after the other.  Same arithmetic in the same order as the two separate kernels; the deformation's blocks take the "frozen by a
+// blocks their own CUs (`reserve` of upd_split): measured with 248 + 13 blocks the two parts ran one after the other.  Same arithmetic in the same order as the two separate kernels; the deformation's blocks take the "frozen by a
 // non-finite loss" decision from the slabs themselves (frozen_in_launch) instead of the flag the ICNN update writes.
 constexpr int UPD_UNION_MAX_THREADS = 768;   // 12 waves: three per SIMD, 168 registers each
-__global__ __launch_bounds__(UPD_UNION_MAX_THREADS) void cdn_update_kernel(const UpdArgs ui, const FlowUpdArgs uf, const int nbi) {
+__global__ __launch_bounds__(UPD_UNION_MAX_THREADS) void cdn_update_kernel(const UpdArgs ui, const FlowUpdArgs uf, const int nbi, const int n_wide) {
     if ((int)blockIdx.x < nbi) {
-        icnn_update_body(ui, blockIdx.x, blockIdx.y);
+        icnn_update_body(ui, blockIdx.x, blockIdx.y, n_wide);
         return;
     }
     const int tid = threadIdx.y * blockDim.x + threadIdx.x;
@@ -304,9 +326,9 @@ __global__ __launch_bounds__(UPD_UNION_MAX_THREADS) void cdn_update_kernel(const
     flow_update_body<32>(uf, (int)blockIdx.x - nbi, blockIdx.y, tid);
 }
 template <int C>
-__global__ __launch_bounds__(UPD_UNION_MAX_THREADS) void pcn_update_kernel(const UpdArgs ui, const RnvpUpdArgs ur, const int nbi) {
+__global__ __launch_bounds__(UPD_UNION_MAX_THREADS) void pcn_update_kernel(const UpdArgs ui, const RnvpUpdArgs ur, const int nbi, const int n_wide) {
     if ((int)blockIdx.x < nbi) {
-        icnn_update_body(ui, blockIdx.x, blockIdx.y);
+        icnn_update_body(ui, blockIdx.x, blockIdx.y, n_wide);
         return;
     }
     const int tid = threadIdx.y * blockDim.x + threadIdx.x;
@@ -595,11 +617,16 @@ struct Workspace {
     float* coef;
     float* wimg;
     float* slabs;            // the buffer of the current step (set_step rotates it)
+    float* loss_part;        // ... and its tail: the workgroups' loss partials once more, dense [n_images][wgs]
     float* slabs0;           // buffer 0
-    long long slab_floats;   // floats per buffer
+    long long slab_floats;   // floats per buffer (slabs + loss partials)
+    long long loss_off;      // floats from a buffer's start to its loss partials
     int wgs, PS;
     long long bytes;
-    void set_step(int it) { slabs = slabs0 + (size_t)(it % INR_SLAB_BUFFERS) * slab_floats; }
+    void set_step(int it) {
+        slabs = slabs0 + (size_t)(it % INR_SLAB_BUFFERS) * slab_floats;
+        loss_part = slabs + loss_off;
+    }
     int act0 = INR_ACT_RELU;     // layer-0 activation of the model this workspace was prepared for
     float act_omega = 0.f;
     int hu = 0, Pu = 0;          // the caller's n_hidden and parameter count (set_user; hu < e->h: zero-padded on the kernel's width)
@@ -616,11 +643,13 @@ Workspace carve(const KernelEntry* e, long long n_points, int n_images, void* ba
     w.PS = (e->img.sl_cols + 31) / 32 * 32;   // slab rows start on 128-byte lines (the tile stores are whole lines then: -0.3 us)
     const long long coef_bytes = ((long long)n_images * 2 * 4 + 255) / 256 * 256;
     const long long img_bytes = ((long long)n_images * e->img.floats * 4 + 255) / 256 * 256;
-    w.slab_floats = ((long long)n_images * w.wgs * w.PS + 63) / 64 * 64;
+    w.loss_off = ((long long)n_images * w.wgs * w.PS + 63) / 64 * 64;
+    w.slab_floats = w.loss_off + ((long long)n_images * w.wgs + 63) / 64 * 64;
     const long long slab_bytes = w.slab_floats * 4 * INR_SLAB_BUFFERS;
     w.coef = (float*)base;
     w.wimg = (float*)((char*)base + coef_bytes);
     w.slabs0 = w.slabs = (float*)((char*)base + coef_bytes + img_bytes);
+    w.loss_part = w.slabs + w.loss_off;
     w.bytes = coef_bytes + img_bytes + slab_bytes;
     return w;
 }
@@ -985,6 +1014,7 @@ static int launch_step(const KernelEntry* e, const Workspace& w, bool train, con
     a.targets = targets;
     a.coef = w.coef;
     a.slabs = w.slabs;
+    a.loss_part = w.loss_part;
     a.logits = logits;
     a.grid = *grid;
     a.N = grid->n_points;
@@ -1038,6 +1068,8 @@ static UpdArgs make_upd_args(const KernelEntry* e, const Workspace& w, float* pa
     u.params = params;
     u.opt_state = opt_state;
     u.slabs = w.slabs;
+    u.loss_part = w.loss_part;
+    u.loss_stride = 1;
     u.loss_hist = loss_hist;
     u.status = status;
     u.opt = *opt;
@@ -1083,7 +1115,7 @@ static void set_step_consts(UpdArgs& u, const InrOptDesc* opt, int t, int hist_i
 }
 
 static void launch_icnn_update(const KernelEntry* e, const UpdArgs& u, hipStream_t s) {
-    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, u.n_images), upd_block(e->img.sl_cols), 0, s, u);
+    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, u.n_images), upd_block(e->img.sl_cols), 0, s, u, upd_split(e->img.sl_cols).n_wide);
 }
 
 // the update-kernel half of bench.py's timing hook (launch_step_timed is the step kernel's)
@@ -1134,7 +1166,7 @@ static void launch_reduce(const KernelEntry* e, const Workspace& w, int n_images
     u.wgs = w.wgs;
     u.n_images = n_images;
     u.mode = 1;
-    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, n_images), upd_block(e->img.sl_cols), 0, s, u);
+    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(e->img.sl_cols, n_images), upd_block(e->img.sl_cols), 0, s, u, upd_split(e->img.sl_cols).n_wide);
 }
 
 
@@ -1211,6 +1243,8 @@ static UpdArgs wide_upd_args(const WideMap& m, const float* grads, const InrOptD
     u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
     u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
     u.slabs = grads;
+    u.loss_part = grads + m.P;   // the one-slab view's loss column, in place
+    u.loss_stride = u.PS;
     for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = u.freeze_lo[k] = u.freeze_hi[k] = 0;
     for (int k = 0; k < m.L; ++k) {
         u.clamp_lo[k] = m.p_w(k); u.clamp_hi[k] = m.p_w(k) + m.h * m.kin(k);
@@ -1222,7 +1256,7 @@ static UpdArgs wide_upd_args(const WideMap& m, const float* grads, const InrOptD
     return u;
 }
 static void launch_wide_update(const WideMap& m, const UpdArgs& u, hipStream_t s) {
-    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(m.P + 1, 1), upd_block(m.P + 1), 0, s, u);
+    hipLaunchKernelGGL(icnn_update_kernel, upd_grid(m.P + 1, 1), upd_block(m.P + 1), 0, s, u, upd_split(m.P + 1).n_wide);
 }
 
 static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
@@ -1444,10 +1478,11 @@ static void launch_cdn_update(const KernelEntry* e, const UpdArgs& ui, FlowUpdAr
     const int nbf = 2 * f->num_coupling + 1;
     const dim3 gi = upd_grid(e->img.sl_cols, n_images, nbf);
     uf.status = nullptr;
-    uf.loss_slabs = ui.slabs + (e->img.sl_cols - 1);
+    uf.loss_part = ui.loss_part;
     uf.loss_wgs = ui.wgs;
-    uf.loss_PS = ui.PS;
-    hipLaunchKernelGGL(cdn_update_kernel, dim3(gi.x + nbf, n_images), upd_block(e->img.sl_cols, nbf), 0, s, ui, uf, (int)gi.x);
+    uf.loss_stride = ui.loss_stride;
+    hipLaunchKernelGGL(cdn_update_kernel, dim3(gi.x + nbf, n_images), upd_block(e->img.sl_cols, nbf), 0, s, ui, uf, (int)gi.x,
+                       upd_split(e->img.sl_cols, nbf).n_wide);
 }
 
 static void launch_flow_fwd(const CdnWs& w, const InrGridDesc* grid, int n_images, float* out, hipStream_t s) {
@@ -1890,11 +1925,12 @@ static void launch_pcn_update(const KernelEntry* e, const PcnWs& w, const UpdArg
     const int nbf = w.rm.F + 1;
     const dim3 gi = upd_grid(e->img.sl_cols, n_images, nbf), g(gi.x + nbf, n_images), b = upd_block(e->img.sl_cols, nbf);
     ur.status = nullptr;
-    ur.loss_slabs = ui.slabs + (e->img.sl_cols - 1);
+    ur.loss_part = ui.loss_part;
     ur.loss_wgs = ui.wgs;
-    ur.loss_PS = ui.PS;
-    if (w.rm.C == 2) hipLaunchKernelGGL(pcn_update_kernel<2>, g, b, 0, s, ui, ur, (int)gi.x);
-    else hipLaunchKernelGGL(pcn_update_kernel<3>, g, b, 0, s, ui, ur, (int)gi.x);
+    ur.loss_stride = ui.loss_stride;
+    const int n_wide = upd_split(e->img.sl_cols, nbf).n_wide;
+    if (w.rm.C == 2) hipLaunchKernelGGL(pcn_update_kernel<2>, g, b, 0, s, ui, ur, (int)gi.x, n_wide);
+    else hipLaunchKernelGGL(pcn_update_kernel<3>, g, b, 0, s, ui, ur, (int)gi.x, n_wide);
 }
 
 static void launch_rnvp_update_args(const PcnWs& w, int n_images, const RnvpUpdArgs& u, hipStream_t s) {
@@ -2516,6 +2552,7 @@ int fit_run(D d, const InrModelDesc* model, float* params, float* opt_state, con
     for (int it = 0; it < steps; ++it) {
         d.icnn.set_step(step0 + it);
         u.slabs = d.icnn.slabs;
+        u.loss_part = d.icnn.loss_part;
         set_step_consts(u, opt, step0 + it + 1, it);
         float* logits = gate_logits && it == steps - 1 ? final_logits : nullptr;
         d.forward(true, it > 0, s);

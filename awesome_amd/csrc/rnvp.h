@@ -971,10 +971,10 @@ struct RnvpUpdArgs {
     float* RE;            // [n_images][LDSF] packed image to refresh after the step (mode 0), or null
     int unit_linear;      // header of RE with a = 1, b = 0 (learn_flow_identity)
     const float* gscale;  // [n_images] factor on every reduced gradient (the joint step's detached clip factor), or null
-    // set when the ICNN update of the same optimizer step runs in the SAME launch (pcn_update_kernel): the loss column of its slabs
-    const float* loss_slabs;   // slab entry "loss" of image 0, workgroup 0 (stride loss_PS per workgroup, loss_wgs * loss_PS per image)
+    // set when the ICNN update of the same optimizer step runs in the SAME launch (pcn_update_kernel): its step kernel's loss partials
+    const float* loss_part;    // loss partial of image 0, workgroup 0 (stride loss_stride per workgroup, loss_wgs * loss_stride per image)
     int loss_wgs;
-    long long loss_PS;
+    long long loss_stride;
 };
 
 __device__ __forceinline__ float opt_apply(const RnvpUpdArgs& u, float gmul, float p, float g, float lr, float wd, float* m_, float* v_) {
@@ -1007,8 +1007,8 @@ __device__ __forceinline__ void rnvp_update_body(const RnvpUpdArgs& u, const int
     // one source of truth with the ICNN update: the flag it has written for step t (hdr[6 + ((t + 1) & 1)]; `status` may be NULL) -
     // or, when that update runs in THIS launch (pcn_update_kernel), the same decision from the same numbers (frozen_in_launch)
     const bool frozen = !isfinite(gmul) ||    // the joint step's composite loss was not finite (joint_step_finish_kernel)
-                        (u.loss_slabs != nullptr
-                             ? frozen_in_launch(u.loss_slabs, u.loss_wgs, u.loss_PS, u.lr_hdr, u.hdr_stride, u.t, img, tid)
+                        (u.loss_part != nullptr
+                             ? frozen_in_launch(u.loss_part, u.loss_wgs, u.loss_stride, u.lr_hdr, u.hdr_stride, u.t, img, tid)
                              : ((u.lr_hdr != nullptr && u.lr_hdr[(size_t)img * u.hdr_stride + 6 + ((u.t + 1) & 1)] != 0.f) ||
                                 (u.status != nullptr && u.status[img] != INR_STATUS_OK)));
     float* __restrict__ rp = u.RP + (size_t)img * m.RP;

@@ -165,7 +165,8 @@ int inrfit_debug_set_slab_base(int slab_base);
 int inrfit_supported(const InrModelDesc* model);
 int64_t inrfit_param_count(const InrModelDesc* model);
 int64_t inrfit_opt_state_floats(const InrModelDesc* model);
-/* Scratch every compute call needs (parameter images in LDS layout, per-workgroup gradient slabs, loss coefficients). */
+/* Scratch every compute call needs (parameter images in LDS layout, per-workgroup gradient slabs each followed by the workgroups'
+ * loss partials as a dense array, loss coefficients). */
 int64_t inrfit_workspace_bytes(const InrModelDesc* model, const InrGridDesc* grid, int n_images);
 
 /* logits[n_images][n_points] = f_theta(grid).  Replaces ConvexNet/ConvexNextNet.forward
