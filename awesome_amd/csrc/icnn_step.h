@@ -437,7 +437,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 
     // persistent gradient accumulators (TRAIN)
     f32x4 dW[RPW][KG];     // dW1ext tiles: rows 16*(wave*RPW+j).., columns 16*b..             (MFMA)
-    f32x4 dL0[TM];         // layer-0 gradient of this wave's own points: rows 16t.., columns = slots of k-group TM (MFMA)
+    // layer-0 gradient (VALU): lane group g owns the hidden units of the tiles 4q + g - unit bcol(4q + g, l15) - and sums over ALL 16
+    // points of the wave in the order the matrix pipe would (k-step r, then lane group k: point 4k + r), one FMA chain per parameter
+    constexpr int NQ = (TM + 3) / 4;
+    float dL0[NQ][NEXT];
     f32x4 dwo[TM];         // dw_o partial sums over this lane's points                          (VALU)
     float dwol[HRA];       // ... leftover units (lane group 0 only)
     float dWl[HRA][KG];    // leftover rows of dW1ext: column 16b + l15, partial over this lane group's points
@@ -449,10 +452,11 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 #pragma unroll
             for (int b = 0; b < KG; ++b) dW[j][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int t = 0; t < TM; ++t) {
-            dwo[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dL0[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        for (int t = 0; t < TM; ++t) dwo[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int e = 0; e < NEXT; ++e) dL0[q][e] = 0.f;
 #pragma unroll
         for (int u = 0; u < HRA; ++u) {
             dwol[u] = 0.f;
@@ -736,22 +740,27 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             STAMP(3);
             // ---- backward through layer 1 (MFMA, pipelined): dZ0 = dZ1 . W1 ----------------------------------------
             // Operands swapped w.r.t. the forward product (same registers): the D tile comes out transposed - rows =
-            // this wave's points 4g+r, columns = hidden unit 16t + l15 - which is the A operand of the layer-0
-            // gradient product dW_in = dZ0^T . (1, x), so that product needs no staging and no barrier.
+            // this wave's points 4g+r, columns = hidden unit 16t + l15 - so every lane holds dz0 of ONE hidden unit per tile for
+            // four of the wave's own points: the layer-0 gradient dW_in = dZ0^T . (1, x) is per-lane FMAs, no staging, no barrier.
             f32x4 dz0[TM];
             f32x4 dzx = f32x4{0.f, 0.f, 0.f, 0.f};  // DX: same product for the columns of k-group TM (skip-path inputs)
             float bqx[2] = {0.f, 0.f};
             float dz0l[HRA];
 #pragma unroll
             for (int u = 0; u < HRA; ++u) dz0l[u] = 0.f;
-            constexpr int KS = 4 * TM + HR;  // k-steps over the hidden outputs
+            // k-steps over the hidden outputs.  The HR <= 4 leftover outputs share ONE k-step: dzl[] is the same in all four lane
+            // groups, so lane group u < HR carries leftover unit u (operand dzl[u], weight row HM + u), the others feed zeros.
+            constexpr int KS = 4 * TM + (HR > 0 ? 1 : 0);
+            float dzlg = 0.f;   // this lane group's leftover dz1
+#pragma unroll
+            for (int u = 0; u < HR; ++u) dzlg = g == u ? dzl[u] : dzlg;
             float bq[2][B128 ? 1 : TM];          // B operands (weights): row o of this k-step, columns 16t + l15
             f32x4 bq4[2][B128 ? TM / 4 : 1];     // B128: the same row as 16-byte reads, columns 64 u + 4 l15 .. + 3
             f32x4 wcq[2][HRA];    // leftover input columns W1[o][HM+u] at this lane's positions of a tile
             auto b_row = [&](int ks) -> const float* {  // LDS row of the weight operand for k-step ks
                 const int tk = ks >> 2, r = ks & 3;
                 if (tk < TM) return wb + (16 * tk + 4 * g + r) * S;
-                return wb + (g == 0 ? (HM + r) * S : 0);  // leftover outputs live in lane group 0 (others: A = 0)
+                return wb + (g < HR ? (HM + g) * S : 0);  // leftover output u lives in lane group u (others: A = 0)
             };
             auto b_vec = [&](int ks, int u) { return *(const f32x4*)(b_row(ks) + 3 * l15 + 64 * u); };   // (wb = Wimg + l15)
             dz1_tile(0);
@@ -780,7 +789,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                     for (int u = 0; u < HR; ++u) wcq[(tk + 1) & 1][u] = *(const f32x4*)(WcT + u * PT + 16 * (tk + 1) + 4 * g);
                 }
                 OPERAND_FENCE();
-                const float bop = tk < TM ? acc[tk < TM ? tk : 0][r] : (g == 0 ? dzl[r < HRA ? r : 0] : 0.f);
+                const float bop = tk < TM ? acc[tk < TM ? tk : 0][r] : dzlg;
 #pragma unroll
                 for (int t = 0; t < TM; ++t) {  // D = dZ0 with POINTS on the rows; next k-step's operand reads one per product
                     if constexpr (B128) {
@@ -800,17 +809,20 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 #pragma unroll
                 for (int u = 0; u < HR; ++u) {
                     if (tk < TM) dz0l[u] = fmaf(wcq[tk & 1][u][r], acc[tk < TM ? tk : 0][r], dz0l[u]);
-                    else if (g == 0) dz0l[u] = fmaf(wcq[tk & 1][u][r], dzl[r < HRA ? r : 0], dz0l[u]);
+                    else if (g == 0) {   // the leftover outputs' share stays ONE chain in lane group 0 (output HM + 0, then HM + 1, ..)
+#pragma unroll
+                        for (int v = 0; v < HR; ++v) dz0l[u] = fmaf(wcq[tk & 1][u][v], dzl[v], dz0l[u]);
+                    }
                 }
                 MFMA_STEP_FENCE();
             }
             STAMP(4);
-            // relu mask of layer 0 (z0p, computed before the output layer); then dL0[t] += dZ0[:, tile t]^T . ext columns of
-            // this wave's own stage-B rows.
+            // relu mask of layer 0 (z0p, computed before the output layer); then the layer-0 gradient dW_in += dZ0^T . (1, x) over this
+            // wave's 16 points.  On the VALU: the product has NEXT useful columns, a matrix-pipe tile pads them to 16 (4 TM MFMAs for 6
+            // MFMAs' worth of arithmetic).  dz0[t][r] holds point 4g + r of unit (t, l15); a 4 x 4 transpose between lane
+            // groups and tiles (four permlane swaps per four registers) hands lane group g the tiles 4q + g for the points of ALL lane
+            // groups, and every parameter is then one FMA chain in the matrix pipe's own order: the same bits as the MFMA form.
             {
-                float bfe[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) bfe[r] = stB[(wave * 16 + 4 * g + r) * G::SB + HM + l15];
 #pragma unroll
                 for (int t = 0; t < TM; ++t)
 #pragma unroll
@@ -822,11 +834,41 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                         else dz0[t][r] *= dact0_f<ACT0>(z0p[t][r], a.act_omega);
 #endif
                     }
+                auto swap32 = [](float& u, float& v) {   // lane groups 2, 3 of u <-> lane groups 0, 1 of v
+                    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(v), false, false);
+                    u = __uint_as_float(s[0]);
+                    v = __uint_as_float(s[1]);
+                };
+                auto swap16 = [](float& u, float& v) {   // lane groups 1, 3 of u <-> lane groups 0, 2 of v
+                    const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(v), false, false);
+                    u = __uint_as_float(s[0]);
+                    v = __uint_as_float(s[1]);
+                };
+                const float* const xrow = stB + wave * 16 * G::SB;   // this wave's stage-B rows: one address per wave, LDS broadcasts
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
+                    float D[NQ][4];   // D[q][k]: dz0 of unit (4q + g, l15) at point 4k + r
 #pragma unroll
-                    for (int t = 0; t < TM; ++t) dL0[t] = MFMA16(dz0[t][r], bfe[r], dL0[t]);
-                    MFMA_STEP_FENCE();
+                    for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) D[q][j] = 4 * q + j < TM ? dz0[4 * q + j < TM ? 4 * q + j : 0][r] : 0.f;
+                        swap32(D[q][0], D[q][2]);
+                        swap32(D[q][1], D[q][3]);
+                        swap16(D[q][0], D[q][1]);
+                        swap16(D[q][2], D[q][3]);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float xp[C];
+#pragma unroll
+                        for (int c = 0; c < C; ++c) xp[c] = xrow[(4 * k + r) * G::SB + G::ext_pos(1 + c)];
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q) {
+                            dL0[q][0] += D[q][k];
+#pragma unroll
+                            for (int c = 0; c < C; ++c) dL0[q][1 + c] = fmaf(D[q][k], xp[c], dL0[q][1 + c]);
+                        }
+                    }
                 }
             }
             // leftover rows of the layer-0 gradient (lane group 0, VALU)
@@ -1006,18 +1048,13 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 if (lane == 0) scr[SC_L0L + u * 4 + e] = w;
             }
         }
-        {   // dL0 tiles: row 4g + r of tile t = hidden unit bcol(t, 4g + r), column l15 = slot of k-group TM; keep the ext-input columns
-            int e = -1;
+        // layer-0 gradient of the main units: lane (g, l15) holds this wave's sums of hidden unit bcol(4q + g, l15)
 #pragma unroll
-            for (int k = 0; k < NEXT; ++k)
-                if (HM + l15 == G::ext_pos(k)) e = k;
-            if (e >= 0) {
+        for (int q = 0; q < NQ; ++q)
+            if (4 * q + g < TM) {
 #pragma unroll
-                for (int t = 0; t < TM; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) scr[SC_L0 + bcol(t, 4 * g + r) * 4 + e] = dL0[t][r];
+                for (int e = 0; e < NEXT; ++e) scr[SC_L0 + bcol(4 * q + g, l15) * 4 + e] = dL0[q][e];
             }
-        }
         {
             float sc[2 + C];
             sc[0] = loss_acc;

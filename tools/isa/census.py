@@ -25,7 +25,11 @@ mf=[i for i in range(lo,hi) if ops[i].startswith('v_mfma')]
 print("body",lo,hi,hi-lo,"mfma",len(mf))
 tot=collections.Counter(cls(o,l) for o,l in zip(ops[lo:hi],lines[lo:hi]))
 for k,v in tot.most_common(): print(f"  {k:24s} {v}")
-names=[('top+fwd',0,272),('bwd',272,544),('mask+dL0',544,584),('dW',584,len(mf))]
+# headline shape (h = 130): layer 0 + forward + mask = 288 MFMAs, dW = 288, whatever lies between is the backward product (and, in
+# builds that still run it on the matrix pipe, the layer-0 gradient's tiles)
+n=len(mf)
+if n not in (840,880): print('NOTE: the phase rows below assume the h = 130 headline kernel (840 / 880 MFMAs per chunk); this loop has',n,'- read the totals only')
+names=[('top+fwd+mask',0,288),('bwd (.. layer-0 gradient)',288,n-288),('dW',n-288,n)]
 prev=lo
 for nm,a,b in names:
     h=mf[b-1]+1
