@@ -324,6 +324,9 @@ __device__ __forceinline__ float sum_over_groups(float v) {  // the 4 lanes shar
 #ifndef INR_STAGE_Z0_EARLY
 #define INR_STAGE_Z0_EARLY 1
 #endif
+#ifndef INR_PROLOGUE_EARLY
+#define INR_PROLOGUE_EARLY 1   // 1: the parameter image goes to LDS by LDS-DMA, and everything that does not read it (kernel arguments, the first chunk's point, the accumulator zeroing) sits between the copy's issue and its wait; 0: register-staged copy, wait, barrier, then the rest (A/B in DESIGN.md 6)
+#endif
 #ifndef INR_SLAB_NT
 #define INR_SLAB_NT 1   // the slab tiles are written once and read once by another kernel: non-temporal stores (A/B in DESIGN.md 6)
 #endif
@@ -348,6 +351,7 @@ __device__ __forceinline__ float sum_over_groups(float v) {  // the 4 lanes shar
 #if INR_STAMPS
 __device__ unsigned long long g_stamps[16];
 __device__ unsigned long long g_wgtimes[1024][4];   // per workgroup, s_memrealtime (100 MHz): entry, loop start, loop end, stores done
+__device__ unsigned long long g_wgfirst[1024];      // per workgroup: entry -> the first chunk's inputs are there (its first MFMA can issue)
 #define STAMP(k)                                                                                   \
     do {                                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -360,6 +364,31 @@ __device__ unsigned long long g_wgtimes[1024][4];   // per workgroup, s_memrealt
 #else
 #define STAMP(k)
 #endif
+
+// The parameter image -> LDS by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave and instruction, no registers, every piece in flight at
+// once; 256 threads).  No compiled image is a whole number of KB: the floats behind the last whole KB go through one register per
+// thread, requested FIRST (the wait in front of its LDS write then covers nothing issued later) and returned to the caller, who hands
+// it to image_tail_to_lds in front of the barrier that awaits the copy (the barrier's fence waits for vmcnt(0): the pieces have landed).
+template <int FLOATS>
+__device__ __forceinline__ f32x4 image_to_lds_issue(const float* __restrict__ gimg, float* smem, const int tid, const int lane, const int wave) {
+    constexpr int PIECES = FLOATS / 256, TAIL4 = (FLOATS - 256 * PIECES) / 4;
+    static_assert(FLOATS % 4 == 0 && TAIL4 <= 256, "the tail is one float4 per thread at most");
+    f32x4 tail = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (tid < TAIL4) tail = ((const f32x4*)gimg)[64 * PIECES + tid];
+#pragma unroll
+    for (int k = 0; k < (PIECES + 3) / 4; ++k) {
+        const int pc = wave + 4 * k;
+        if (pc < PIECES)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gimg + pc * 256 + lane * 4),
+                                             (__attribute__((address_space(3))) void*)(smem + pc * 256), 16, 0, 0);
+    }
+    return tail;
+}
+template <int FLOATS>
+__device__ __forceinline__ void image_tail_to_lds(float* smem, const int tid, const f32x4 tail) {
+    constexpr int PIECES = FLOATS / 256, TAIL4 = (FLOATS - 256 * PIECES) / 4;
+    if (tid < TAIL4) ((f32x4*)smem)[64 * PIECES + tid] = tail;
+}
 
 // DX: additionally write dL/d(coordinates) (needed when the ICNN sits behind a learned deformation of the grid).
 template <int H, int C, bool TRAIN, bool DX = false, int ACT0 = INR_ACT_RELU>
@@ -398,9 +427,16 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     const int wg = blockIdx.x - img * a.wgs;
     const long long N = a.N;
 
-    // ---- copy the parameter image into LDS (all loads in flight at once) ------------------------------------------
-    {
-        const f32x4* __restrict__ src = (const f32x4*)(a.wimg + (size_t)img * G::IMG_FLOATS);
+    // ---- copy the parameter image into LDS ------------------------------------------------------------------------
+    const float* __restrict__ gimg = a.wimg + (size_t)img * G::IMG_FLOATS;
+#if INR_PROLOGUE_EARLY
+    // LDS-DMA; awaited by the barrier in image_arrived() below, behind everything in this prologue that does not read the image
+    static_assert(WG_THREADS == 256, "image_to_lds_issue");
+    const f32x4 img_tail = image_to_lds_issue<G::IMG_FLOATS>(gimg, smem, tid, lane, wave);
+    __builtin_amdgcn_sched_barrier(0);
+#else
+    {   // register-staged (all loads in flight at once)
+        const f32x4* __restrict__ src = (const f32x4*)gimg;
         constexpr int NV4 = G::IMG_FLOATS / 4;
         constexpr int NIT = (NV4 + WG_THREADS - 1) / WG_THREADS;
         f32x4 tmp[NIT];
@@ -415,19 +451,26 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             if (i < NV4) ((f32x4*)smem)[i] = tmp[k];
         }
     }
+#endif
     float cfg_ = 0.f, cbg_ = 0.f;
     if (TRAIN) {
         cfg_ = a.coef[2 * img];
         cbg_ = a.coef[2 * img + 1];
     }
-    __syncthreads();
-    const float b_o = smem[G::OFF_SC];
-    float s_o[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) s_o[c] = smem[G::OFF_SC + 1 + c];
+    // the only values of the prologue that come out of the image
+    float b_o, s_o[C];
     float wol[HRA];  // w_o of the leftover units
+    auto image_arrived = [&]() {
+        __syncthreads();   // (its fence waits for vmcnt(0): every wave's DMA pieces have landed)
+        b_o = smem[G::OFF_SC];
 #pragma unroll
-    for (int u = 0; u < HRA; ++u) wol[u] = HR > 0 ? woT[HM + u] : 0.f;
+        for (int c = 0; c < C; ++c) s_o[c] = smem[G::OFF_SC + 1 + c];
+#pragma unroll
+        for (int u = 0; u < HRA; ++u) wol[u] = HR > 0 ? woT[HM + u] : 0.f;
+    };
+#if !INR_PROLOGUE_EARLY
+    image_arrived();
+#endif
 
     // per-lane LDS addresses
     const float* const wf = Wimg + l15 * S + 4 * g;  // forward A operand: row 16t + l15, columns 16tk + 4g ..+3
@@ -445,6 +488,9 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     float dwol[HRA];       // ... leftover units (lane group 0 only)
     float dWl[HRA][KG];    // leftover rows of dW1ext: column 16b + l15, partial over this lane group's points
     float dL0l[HRA][NEXT]; // leftover rows of the layer-0 gradient (lane group 0 only)
+    // (With INR_PROLOGUE_EARLY these zeros still land behind the image's barrier: hipcc materialises them at the end of the block in
+    // front of the loop wherever the source writes them.  Pinning them in front of the wait takes one asm statement per register, and
+    // that moved the chunk loop's allocation: +85 v_accvgpr moves per chunk.)
     float loss_acc = 0.f, dbo = 0.f, dso[C];
     if (TRAIN) {
 #pragma unroll
@@ -508,7 +554,13 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         q.tg = TRAIN ? a.targets[(size_t)img * a.data_count + min(pc, a.data_count - 1)] : 0.f;   // never past the targets
         return q;
     };
-    PointIn nxt = load_point(wg);
+    PointIn nxt = load_point(wg);   // (a workgroup without a chunk loads the clamped, valid address and never uses it)
+#if INR_PROLOGUE_EARLY
+    __builtin_amdgcn_sched_barrier(0);
+    image_tail_to_lds<G::IMG_FLOATS>(smem, tid, img_tail);
+    image_arrived();
+    __builtin_amdgcn_sched_barrier(0);
+#endif
 #if INR_STAMPS
     unsigned long long st_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
@@ -517,6 +569,14 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     const unsigned long long rt_loop = __builtin_amdgcn_s_memrealtime();
 #endif
     for (int chunk = wg; chunk < n_chunks; chunk += a.wgs) {
+#if INR_STAMPS
+        if (chunk == wg) {   // everything in front of the first MFMA has been issued; wait for the point, then stamp
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0);
+            if (tid == 0 && blockIdx.x < 1024) g_wgfirst[blockIdx.x] = __builtin_amdgcn_s_memrealtime() - rt_entry;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
         STAMP(0);
         const int p = chunk * SP + wave * 16 + l15;
         const bool valid = p < (int)N;

@@ -110,6 +110,9 @@ __host__ __device__ __forceinline__ int user_param_index(const ImgMap& m, int h,
     return base_u + h + (j - m.p_bo);        // out.ln.bias, out.skp.weight [C]
 }
 
+#ifndef INR_UPD_SLABS_FIRST
+#define INR_UPD_SLABS_FIRST 1   // 1: the update's slab loads are a block's first memory instructions; 0: behind the index arithmetic and the p / m / v requests
+#endif
 constexpr int UPD_MAX_PARAMS = 256;  // most parameters per block
 constexpr int UPD_GROUPS = 16;       // slab groups summed in parallel, then combined in fixed order
 
@@ -149,6 +152,9 @@ inline dim3 upd_block(int cols, int reserve = 0) { return dim3(upd_split(cols, r
 
 #if INR_STAMPS
 __device__ unsigned long long g_updtimes[512][4];   // per block of the LAST update launch, s_memrealtime (100 MHz): entry, slab loads back, reduced, stores done
+__device__ unsigned long long g_updissue[512];       // per block: entry -> the first slab load is about to issue (no wait in front)
+#define UPD_STAMP_ISSUE()                                                                                     \
+    if (threadIdx.x == 0 && threadIdx.y == 0 && img == 0 && bx < 512) g_updissue[bx] = __builtin_amdgcn_s_memrealtime()
 #define UPD_STAMP(k)                                                                                          \
     if (threadIdx.x == 0 && threadIdx.y == 0 && img == 0 && bx < 512) {                                       \
         __builtin_amdgcn_s_waitcnt(0);                                                                        \
@@ -156,6 +162,7 @@ __device__ unsigned long long g_updtimes[512][4];   // per block of the LAST upd
     }
 #else
 #define UPD_STAMP(k)
+#define UPD_STAMP_ISSUE()
 #endif
 // block = (blockDim.x lanes x float4 = the columns of a wide block) x 16 slab groups; bx = the block's index along the slab columns,
 // n_wide = UpdSplit::n_wide (in a narrow block the last 8 lanes of every group have nothing to load)
@@ -169,35 +176,79 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
     __shared__ float redl[UPD_GROUPS];     // this step's loss partials (every block sums them, from u.loss_part: see `frozen` below)
     UPD_STAMP(0);
     const int jl = grp * blockDim.x + tx;  // the first ppb threads finish one slab column = one parameter each
-    const int j = jl < ppb ? slab_param_of_col(u.img, col0 + jl) : -1;   // flat parameter index (kernel shape), P = loss, -1 = none
-    const int ju = (j >= 0 && j < u.P) ? user_param_index(u.img, u.hu, j) : -1;       // ... in the caller's layout; -1: padding (gradient exactly 0)
-    // The kernel is one dependent chain (slabs -> LDS -> optimizer -> stores) and at one image it is latency, not bandwidth,
-    // that it pays for: everything the tail needs is requested up front, and all slab rows of a thread are in flight at once.
+    // The kernel is one dependent chain (slabs -> LDS -> optimizer -> stores) and at one image it is latency, not bandwidth, that it
+    // pays for.  The slab loads are therefore the block's FIRST memory instructions: their addresses are col0 + 4 tx plus row strides,
+    // nothing else.  A quad of padding columns is read like any other (slab rows are padded to whole lines: in bounds) and never
+    // consumed: only the threads with j >= 0 read their column of red[][] below.  Everything else the tail needs is requested behind
+    // them, and whatever depends only on values known at entry is computed while they are in flight.
+    const int j4 = col0 + 4 * tx;
+    const bool takes = 4 * tx < ppb && j4 < u.PS;
+    const float* __restrict__ sl = u.slabs + (size_t)img * u.wgs * u.PS + j4;
+    const bool trip = takes && grp + 15 * UPD_GROUPS < u.wgs;   // 256 slabs: one trip, 16 loads in flight
+    f32x4 q[16];
+    auto request_slabs = [&]() {
+        UPD_STAMP_ISSUE();
+        if (trip) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) q[k] = *(const f32x4*)(sl + (size_t)(grp + k * UPD_GROUPS) * u.PS);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+#if INR_UPD_SLABS_FIRST
+    request_slabs();
+#endif
+    // then the header
     float* __restrict__ st = u.opt_state + (size_t)img * (2 * (size_t)u.Pu + INR_OPT_HEADER_FLOATS);
     float* __restrict__ hdr = st + 2 * (size_t)u.Pu;
     float p_old = 0.f, m_old = 0.f, v_old = 0.f, lr_now = 0.f;
     bool bad_before = false;
-    if (u.mode == 0 && j >= 0) {
+    if (u.mode == 0 && jl < ppb) {   // (in every thread that may own a parameter: the index is not known yet)
         bad_before = hdr[6 + (u.t & 1)] != 0.f;   // written by the PREVIOUS step's launch (double buffer like the lr: no race)
         lr_now = hdr[u.t & 1];
-        if (ju >= 0) {
-            p_old = u.params[(size_t)img * u.Pu + ju];
-            m_old = st[ju];
-            v_old = st[u.Pu + ju];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const int j = jl < ppb ? slab_param_of_col(u.img, col0 + jl) : -1;   // flat parameter index (kernel shape), P = loss, -1 = none
+    const int ju = (j >= 0 && j < u.P) ? user_param_index(u.img, u.hu, j) : -1;       // ... in the caller's layout; -1: padding (gradient exactly 0)
+    if (u.mode == 0 && ju >= 0) {
+        p_old = u.params[(size_t)img * u.Pu + ju];
+        m_old = st[ju];
+        v_old = st[u.Pu + ju];
+    }
+#if !INR_UPD_SLABS_FIRST
+    __builtin_amdgcn_sched_barrier(0);
+    request_slabs();
+#endif
+    // what the optimizer's tail needs of the index alone: the image slots, the range tests
+    int slot[2] = {0, 0}, n_slots = 0;
+    bool never_updated = false, clamped = false;
+    if (u.mode == 0 && ju >= 0) {
+        if (u.wimg != nullptr) n_slots = image_slots(u.img, j, slot);   // (the layer-by-layer path has no parameter image)
+        if (u.opt.freeze_skips) {
+#pragma unroll
+            for (int k = 0; k < UPD_RANGES; ++k) never_updated = never_updated || (j >= u.freeze_lo[k] && j < u.freeze_hi[k]);
+        }
+        if (u.opt.freeze_input && j < u.input_hi) never_updated = true;
+        if (u.opt.clamp) {
+#pragma unroll
+            for (int k = 0; k < UPD_RANGES; ++k) clamped = clamped || (j >= u.clamp_lo[k] && j < u.clamp_hi[k]);
         }
     }
+    __builtin_amdgcn_sched_barrier(0);
     {
-        const int j4 = col0 + 4 * tx;
         f32x4 part = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (4 * tx < ppb && j4 < u.PS && slab_param_of_col(u.img, j4) >= 0) {   // (a lane's 4 tile registers are parameters or padding together)
-            const float* __restrict__ sl = u.slabs + (size_t)img * u.wgs * u.PS + j4;
+        if (takes) {
             int w = grp;
-            for (; w + 15 * UPD_GROUPS < u.wgs; w += 16 * UPD_GROUPS) {   // 256 slabs: one trip, 16 loads in flight
-                f32x4 q[16];
-#pragma unroll
-                for (int k = 0; k < 16; ++k) q[k] = *(const f32x4*)(sl + (size_t)(w + k * UPD_GROUPS) * u.PS);
+            if (trip) {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) part += q[k];
+                w += 16 * UPD_GROUPS;
+            }
+            for (; w + 15 * UPD_GROUPS < u.wgs; w += 16 * UPD_GROUPS) {
+                f32x4 r[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) r[k] = *(const f32x4*)(sl + (size_t)(w + k * UPD_GROUPS) * u.PS);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) part += r[k];
             }
             for (; w < u.wgs; w += UPD_GROUPS) part += *(const f32x4*)(sl + (size_t)w * u.PS);
         }
@@ -206,6 +257,8 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
             redl[grp] = loss_column_group_sum(u.loss_part + (size_t)img * u.wgs * u.loss_stride, u.wgs, (size_t)u.loss_stride, grp);
         }
     }
+    float step_size = 0.f;
+    if (ju >= 0) step_size = (float)((double)lr_now / u.bc1);   // bc1 = 1 - beta1^t, computed on the host in double like torch does
     UPD_STAMP(1);
     __syncthreads();
     if (j < 0) return;
@@ -258,25 +311,16 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
         hdr[5] = loss;
         return;
     }
-    if (frozen || !isfinite(gsum) || ju < 0) return;
-    if (u.opt.freeze_skips) {
-#pragma unroll
-        for (int k = 0; k < UPD_RANGES; ++k)
-            if (j >= u.freeze_lo[k] && j < u.freeze_hi[k]) return;
-    }
-    if (u.opt.freeze_input && j < u.input_hi) return;
+    if (frozen || !isfinite(gsum) || ju < 0 || never_updated) return;
 
-    const float lr = lr_now;
     float p = p_old, m = m_old, v = v_old;
     float grad = gsum;
     if (u.opt.weight_decay != 0.f) grad = __fadd_rn(grad, __fmul_rn(u.opt.weight_decay, p));
-    const double bc1 = u.bc1;  // 1 - beta1^t, computed on the host in double like torch does
     const float w1 = u.one_minus_b1;
     // exp_avg.lerp_(grad, 1 - beta1)
     m = __fadd_rn(m, __fmul_rn(w1, __fsub_rn(grad, m)));
     if (u.opt.kind == INR_OPT_ADAM) {
         const float bc2_sqrt = u.bc2_sqrt;
-        const float step_size = (float)((double)lr / bc1);
         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
         v = __fadd_rn(__fmul_rn(v, u.opt.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, grad), grad));
         const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), u.opt.eps);
@@ -284,22 +328,14 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
     } else {
         // Adamax: exp_inf = max(beta2*exp_inf, |grad| + eps); p -= lr/bc1 * m / exp_inf
         v = fmaxf(__fmul_rn(v, u.opt.beta2), __fadd_rn(fabsf(grad), u.opt.eps));
-        const float clr = (float)((double)lr / bc1);
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-clr, m), v));
+        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, m), v));
     }
-    if (u.opt.clamp) {
-        bool in = false;
-#pragma unroll
-        for (int k = 0; k < UPD_RANGES; ++k) in = in || (j >= u.clamp_lo[k] && j < u.clamp_hi[k]);
-        if (in) p = fmaxf(p, 0.f);
-    }
+    if (clamped) p = fmaxf(p, 0.f);
     u.params[(size_t)img * u.Pu + ju] = p;
-    if (u.wimg != nullptr) {   // (the layer-by-layer path has no parameter image)
-        int slot[2];
-        const int ns = image_slots(u.img, j, slot);
+    if (n_slots > 0) {
         float* __restrict__ wi = u.wimg + (size_t)img * u.img.floats;
         wi[slot[0]] = p;
-        if (ns > 1) wi[slot[1]] = p;
+        if (n_slots > 1) wi[slot[1]] = p;
     }
     st[ju] = m;
     st[u.Pu + ju] = v;
@@ -3396,6 +3432,12 @@ int inrfit_pack_masks(const float* values, int n_images, int64_t n_points, float
 #if INR_STAMPS
 int inrfit_debug_updtimes(unsigned long long* host_out) {   // [512][4] of the last update launch
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_updtimes), sizeof(unsigned long long) * 2048) == hipSuccess ? 0 : -4;
+}
+int inrfit_debug_updissue(unsigned long long* host_out) {   // [512] of the last update launch (absolute, like updtimes[][0])
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_updissue), sizeof(unsigned long long) * 512) == hipSuccess ? 0 : -4;
+}
+int inrfit_debug_wgfirst(unsigned long long* host_out) {   // [1024] of the last step launch (relative to the workgroup's entry)
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wgfirst), sizeof(unsigned long long) * 1024) == hipSuccess ? 0 : -4;
 }
 int inrfit_debug_stamps2(unsigned long long* host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps2), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -4;

@@ -3,7 +3,8 @@
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["INRFIT_LIB"] = os.path.join(ROOT, "variants", "libinrfit_stamps.so")
+os.environ["INRFIT_LIB"] = os.path.join(ROOT, "variants", f"libinrfit_{os.environ.get('STAMPS_VARIANT', 'stamps')}.so")   # STAMPS_VARIANT: another -DINR_STAMPS=1 build
+os.environ["INRFIT_ABI_ANY"] = "1"
 import torch
 import awesome_amd as A
 from awesome_amd.dataset import convex_blob_unaries
@@ -53,8 +54,12 @@ for rep in range(3):
     print(f"   end skew (last - first workgroup end)       {us(t[:, 3].max() - t[:, 3].min()):6.2f} us")
 
 # ---- the same stamps for the LAST step launch of an optimisation sequence (step, update, step, update, ...) ----
+first = (C.c_ulonglong * 1024)()
+lib.inrfit_debug_wgfirst.argtypes = [C.POINTER(C.c_ulonglong)]
 def report(tag):
-    assert lib.inrfit_debug_wgtimes(wg) == 0
+    assert lib.inrfit_debug_wgtimes(wg) == 0 and lib.inrfit_debug_wgfirst(first) == 0
+    f = np.frombuffer(first, dtype=np.uint64)[:256].astype(np.int64)
+    print(f"{tag}: entry -> first chunk's inputs there (first MFMA) median {np.median(f) / 100.0:5.2f} max {f.max() / 100.0:5.2f} us")
     t = np.frombuffer(wg, dtype=np.uint64).reshape(1024, 4).astype(np.int64)
     t = t[t[:, 0] > 0]
     t0 = t[:, 0].min()

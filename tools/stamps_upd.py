@@ -4,7 +4,8 @@ block of the LAST update launch of an optimisation sequence against the workgrou
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["INRFIT_LIB"] = os.path.join(ROOT, "variants", "libinrfit_stamps.so")
+os.environ["INRFIT_LIB"] = os.path.join(ROOT, "variants", f"libinrfit_{os.environ.get('STAMPS_VARIANT', 'stamps')}.so")   # STAMPS_VARIANT: another -DINR_STAMPS=1 build
+os.environ["INRFIT_ABI_ANY"] = "1"
 import numpy as np
 import torch
 import awesome_amd as A
@@ -22,6 +23,8 @@ wg = (C.c_ulonglong * 4096)()
 up = (C.c_ulonglong * 2048)()
 lib.inrfit_debug_wgtimes.argtypes = [C.POINTER(C.c_ulonglong)]
 lib.inrfit_debug_updtimes.argtypes = [C.POINTER(C.c_ulonglong)]
+iss = (C.c_ulonglong * 512)()
+lib.inrfit_debug_updissue.argtypes = [C.POINTER(C.c_ulonglong)]
 us = lambda x: x / 100.0
 for rep in range(3):
     A.fit(spec, params.clone(), grid, un, 40, record_loss=False, want_logits=False)
@@ -39,6 +42,11 @@ for rep in range(3):
     print(f"rep {rep}: {len(t)} step workgroups, {len(u)} update blocks")
     print(f"   step kernel: workgroups' stores done over {us(step_end - step_first_end):5.2f} us")
     print(f"   update entry after the last step store : first {us(u[:, 0].min() - step_end):5.2f}  median {us(np.median(u[:, 0]) - step_end):5.2f}  last {us(u[:, 0].max() - step_end):5.2f} us")
+    assert lib.inrfit_debug_updissue(iss) == 0
+    d = np.frombuffer(iss, dtype=np.uint64).astype(np.int64)[:len(u)] - u[:, 0]
+    print(f"   entry -> first slab load issued: median {us(np.median(d)):5.2f}  max {us(d.max()):5.2f} us")
+    d = u[:, 3] - u[:, 1]
+    print(f"   slab loads back (barrier) -> stores done: median {us(np.median(d)):5.2f}  max {us(d.max()):5.2f} us")
     for k, name in ((1, "slab loads back   "), (2, "reduced (LDS, sum)"), (3, "stores done       ")):
         d = u[:, k] - u[:, 0]
         d = d[u[:, k] > 0]
