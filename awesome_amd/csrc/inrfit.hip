@@ -1025,9 +1025,13 @@ static int launch_pack(const KernelEntry* e, const Workspace& w, const float* pa
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
-// the data-term mask and align rule of inrfit_joint_prior_step; the default is what every other caller runs (all points, hard align)
-struct StepMask {
-    long long data_count = 0;   // 0 = all points
+// What a joint step adds to the data term of a training pass: the align term against `seg` and the mask of the data term proper.
+// One description for both backbones (the step kernel's StepArgs, wide.h's WideJoint); the default is what every other caller
+// runs: no align term, all points.
+struct DataTerm {
+    const float* align_seg = nullptr;   // [N]: the align term's target, or null
+    float c_align = 0.f;
+    long long data_count = 0;           // 0 = all points
     int use_noneclass = 0;
     float noneclass = 0.f;
     int align_soft = 0;
@@ -1036,11 +1040,11 @@ struct StepMask {
 
 static int launch_step(const KernelEntry* e, const Workspace& w, bool train, const InrGridDesc* grid, const float* targets,
                        int loss_kind, int n_images, float* logits, hipStream_t s, float* dcoords = nullptr,
-                       const float* align_seg = nullptr, float c_align = 0.f, const StepMask& mask = StepMask{}) {
+                       const DataTerm& mask = DataTerm{}) {
     StepArgs a{};
     a.dcoords = dcoords;
-    a.seg = align_seg;
-    a.c_align = c_align;
+    a.seg = mask.align_seg;
+    a.c_align = mask.c_align;
     a.data_count = (int)(mask.data_count > 0 ? mask.data_count : grid->n_points);
     a.use_noneclass = mask.use_noneclass;
     a.noneclass = mask.noneclass;
@@ -1170,9 +1174,9 @@ static int launch_icnn_update_timed(const KernelEntry* e, const UpdArgs& u, hipS
     return INR_OK;
 }
 
-// common argument checks + workspace carve
-static int prepare(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
-                   const KernelEntry** e_out, Workspace* w_out) {
+// common argument checks + workspace carve (every argument first: the device's turn is prepare's set_lds)
+static int prepare_args(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
+                        const KernelEntry** e_out, Workspace* w_out) {
     const KernelEntry* e = find_entry(model);
     if (!e) return INR_EUNSUPPORTED;
     if (!workspace) return INR_EINVAL;
@@ -1184,9 +1188,13 @@ static int prepare(const InrModelDesc* model, const InrGridDesc* grid, int n_ima
     if (model->act0 < INR_ACT_RELU || model->act0 > INR_ACT_SIN) return INR_EINVAL;
     w_out->act0 = model->act0;
     w_out->act_omega = model->act_omega;
-    if ((rc = set_lds(e))) return rc;
     *e_out = e;
     return INR_OK;
+}
+static int prepare(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
+                   const KernelEntry** e_out, Workspace* w_out) {
+    if (const int rc = prepare_args(model, grid, n_images, workspace, workspace_bytes, e_out, w_out)) return rc;
+    return set_lds(*e_out);
 }
 
 static void launch_reduce(const KernelEntry* e, const Workspace& w, int n_images, float* grads, float* loss_out, hipStream_t s) {
@@ -1212,54 +1220,30 @@ static void launch_reduce(const KernelEntry* e, const Workspace& w, int n_images
 // ---------------------------------------------------------------------------------------------------------------------
 static bool use_wide(const InrModelDesc* m) { return find_entry(m) == nullptr && wide_shape_ok(m); }
 
-static int wide_prepare(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
-                        WideMap* m, WideWs* w, float** coef_all, hipStream_t s) {
-    if (!workspace || !grid_ok(grid, n_images, 0x7fffffffLL / WIDE_MAX_HIDDEN * 64)) return INR_EINVAL;
-    if (model->act0 < INR_ACT_RELU || model->act0 > INR_ACT_SIN) return INR_EINVAL;
-    *m = make_wide_map(model);
-    const bool pre0 = model->act0 != INR_ACT_RELU;
-    if (workspace_bytes < wide_total_bytes(*m, grid->n_points, pre0, n_images)) return INR_EWORKSPACE;
-    *w = carve_wide(*m, grid->n_points, pre0, workspace);
-    *coef_all = (float*)((char*)workspace + w->bytes);
-    (void)s;
-    return INR_OK;
-}
+// An ICNN-form shape of the layer-by-layer path: relu layer 0, one output, square layers.  What the RealNVP composite and the joint
+// steps accept (the encode shapes stay refused there).
+static bool pcn_wide_shape(const InrModelDesc* m) { return use_wide(m) && m->act0 == INR_ACT_RELU && !wide_desc_general(m); }
 
-static int wide_forward_all(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
-                            void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    WideMap m;
-    WideWs w;
-    float* coef;
-    int rc = wide_prepare(model, grid, n_images, workspace, workspace_bytes, &m, &w, &coef, s);
-    if (rc) return rc;
-    for (int img = 0; img < n_images; ++img)
-        if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, logits + (size_t)img * m.O * grid->n_points, s)))
-            return rc;
-    return INR_OK;
-}
+long long align256(long long b) { return (b + 255) / 256 * 256; }
 
-// loss + gradients (loss->kind may be INR_LOSS_EXTERNAL: `targets` = dL/dlogits) of every image into grads_out / loss_out
-static int wide_loss_grad_all(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
-                              const InrLossDesc* loss, int n_images, float* loss_out, float* grads_out, void* workspace,
-                              int64_t workspace_bytes, hipStream_t s, float* dcoords = nullptr) {
-    WideMap m;
+// the layer-by-layer workspace behind a deformation's buffers (an ICNN-form shape): logits [N] | dL/dlogits [N] | ONE image's
+// layer-by-layer workspace | the loss coefficients of every image
+struct WideBehind {
+    float *logit, *dy, *coef;
     WideWs w;
-    float* coef;
-    int rc = wide_prepare(model, grid, n_images, workspace, workspace_bytes, &m, &w, &coef, s);
-    if (rc) return rc;
-    const long long N = grid->n_points, ON = (long long)m.O * N;   // targets / dlogits: [n_images][O][N]
-    if (m.O > 1 && loss->weight_mode != INR_WEIGHT_NONE && loss->weight_mode != INR_WEIGHT_EXPLICIT) return INR_EINVAL;
-    if (loss->kind != INR_LOSS_EXTERNAL)   // ('mean' over the O x N elements: torch's MSELoss on (N, O))
-        hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef, 1.f);
-    for (int img = 0; img < n_images; ++img) {
-        w.coef = coef + 2 * img;
-        const float* p = params + (size_t)img * m.P;
-        if ((rc = wide_forward(m, w, model, p, grid, img, targets + (size_t)img * ON, loss->kind, true, nullptr, s))) return rc;
-        if ((rc = wide_backward(m, w, model, p, N, s, targets + (size_t)img * ON, dcoords ? dcoords + (size_t)img * m.C * N : nullptr))) return rc;
-        if (hipMemcpyAsync(grads_out + (size_t)img * m.P, w.grads, sizeof(float) * m.P, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
-        if (loss_out && hipMemcpyAsync(loss_out + img, w.grads + m.P, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
-    }
-    return INR_OK;
+    long long bytes;
+};
+static WideBehind carve_wide_behind(const WideMap& m, long long N, int n_images, void* base) {
+    WideBehind q;
+    char* b = (char*)base;
+    long long off = 0;
+    q.logit = (float*)(b + off); off += align256(N * 4);
+    q.dy = (float*)(b + off); off += align256(N * 4);
+    q.w = carve_wide(m, N, false, b + off);
+    off += q.w.bytes;
+    q.coef = (float*)(b + off); off += wide_align((long long)n_images * 2 * 4);
+    q.bytes = off;
+    return q;
 }
 
 // the optimizer step of the layer-by-layer path = icnn_update_kernel on a one-"slab" view of the gradient vector (column = parameter,
@@ -1293,63 +1277,6 @@ static UpdArgs wide_upd_args(const WideMap& m, const float* grads, const InrOptD
 }
 static void launch_wide_update(const WideMap& m, const UpdArgs& u, hipStream_t s) {
     hipLaunchKernelGGL(icnn_update_kernel, upd_grid(m.P + 1, 1), upd_block(m.P + 1), 0, s, u, upd_split(m.P + 1).n_wide);
-}
-
-static int wide_fit(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
-                    const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist,
-                    float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    WideMap m;
-    WideWs w;
-    float* coef;
-    int rc = wide_prepare(model, grid, n_images, workspace, workspace_bytes, &m, &w, &coef, s);
-    if (rc) return rc;
-    const long long N = grid->n_points, ON = (long long)m.O * N;   // targets / logits: [n_images][O][N]
-    if (m.O > 1 && loss->weight_mode != INR_WEIGHT_NONE && loss->weight_mode != INR_WEIGHT_EXPLICIT) return INR_EINVAL;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, ON, *loss, coef, 1.f);
-    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, m.P, *opt, step0);
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    UpdArgs u = wide_upd_args(m, w.grads, opt, steps);
-    const bool need_dz0 = !(m.general() && opt->freeze_input);   // frozen features: dZ_0 has no use
-    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
-    for (int it = 0; it < steps; ++it) {
-        set_step_consts(u, opt, step0 + it + 1, it);
-        for (int img = 0; img < n_images; ++img) {
-            float* p = params + (size_t)img * m.P;
-            w.coef = coef + 2 * img;
-            if ((rc = wide_forward(m, w, model, p, grid, img, targets + (size_t)img * ON, loss->kind, true,
-                                   gate_logits && it == steps - 1 ? final_logits + (size_t)img * ON : nullptr, s))) return rc;
-            if ((rc = wide_backward(m, w, model, p, N, s, nullptr, nullptr, need_dz0))) return rc;
-            u.params = p;
-            u.opt_state = opt_state + (size_t)img * (2 * (size_t)m.P + INR_OPT_HEADER_FLOATS);
-            u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps : nullptr;
-            u.status = status ? status + img : nullptr;
-            launch_wide_update(m, u, s);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
-    if (final_logits && !gate_logits)
-        for (int img = 0; img < n_images; ++img)
-            if ((rc = wide_forward(m, w, model, params + (size_t)img * m.P, grid, img, nullptr, 0, false, final_logits + (size_t)img * ON, s))) return rc;
-    return INR_OK;
-}
-
-int inrfit_backward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* dlogits,
-                    int n_images, float* grads, float* dcoords, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
-    Workspace w;
-    if (!params || !dlogits || !grads) return INR_EINVAL;
-    if (use_wide(model)) {
-        const InrLossDesc ext{INR_LOSS_EXTERNAL, INR_WEIGHT_NONE, 1.f, 0.f, 0.f};
-        return wide_loss_grad_all(model, params, grid, dlogits, &ext, n_images, nullptr, grads, workspace, workspace_bytes, (hipStream_t)stream,
-                                  dcoords);
-    }
-    int rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
-    if ((rc = launch_step(e, w, true, grid, dlogits, INR_LOSS_EXTERNAL, n_images, nullptr, s, dcoords))) return rc;
-    launch_reduce(e, w, n_images, grads, w.coef /* scratch: the loss slot is unused in this mode */, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
 int inrfit_step_only(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
@@ -1422,7 +1349,6 @@ int inrfit_timing_end(float* avg_step_bracket_us, float* avg_update_bracket_us, 
 namespace {
 
 struct CdnWs {
-    Workspace icnn;       // ICNN workspace (explicit grid = deformed coordinates)
     float *xd, *dxd, *FE, *ps, *slab1, *slab2;
     int blocks1, chunks, Wp, S1;   // blocks1 = blocks of the backward point kernel (rows of slab1)
     FlowShape sf, sb;              // launch shapes of the forward / backward point kernels (flow.h: flow_launch_shape)
@@ -1431,14 +1357,12 @@ struct CdnWs {
     InrGridDesc dgrid;    // the deformed grid handed to the ICNN kernels
 };
 
-long long align256(long long b) { return (b + 255) / 256 * 256; }
-
 static bool flow_ok(const InrFlowDesc* f) {
     return f && f->width >= 1 && f->width <= 256 && (f->backbone == INR_FLOW_NORMAL_BLOCK || f->backbone == INR_FLOW_SIMPLE) &&
            (f->num_coupling == 2 || f->num_coupling == 4 || f->num_coupling == 6 || f->num_coupling == 8);
 }
 
-static CdnWs carve_cdn(const KernelEntry* e, const InrFlowDesc* f, const InrGridDesc* grid, int n_images, void* base) {
+static CdnWs carve_cdn(const InrFlowDesc* f, const InrGridDesc* grid, int n_images, void* base) {
     CdnWs w;
     const long long N = grid->n_points;
     w.fm = make_flow_map(f->width, f->num_coupling, f->backbone == INR_FLOW_SIMPLE ? 0.f : LEAKY_SLOPE);
@@ -1462,10 +1386,6 @@ static CdnWs carve_cdn(const KernelEntry* e, const InrFlowDesc* f, const InrGrid
     w.dgrid.mode = INR_GRID_EXPLICIT;
     w.dgrid.coords = w.xd;
     w.dgrid.coords_image_stride = 2 * N;
-    if (e) {
-        w.icnn = carve(e, N, n_images, b + off);
-        off += align256(w.icnn.bytes);
-    }
     w.bytes = off;
     return w;
 }
@@ -1600,25 +1520,13 @@ static void launch_flow_bwd(const CdnWs& w, const InrFlowDesc* f, const InrGridD
     }
 }
 
-static int check_cdn(const InrModelDesc* model, const InrFlowDesc* flow, const InrGridDesc* grid, int n_images, void* workspace,
-              int64_t workspace_bytes, bool need_icnn, const KernelEntry** e_out, CdnWs* w_out) {
+// the flow on its own (inrfit_flow_forward / _backward); in front of an ICNN: check_deformed
+static int check_cdn(const InrFlowDesc* flow, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes,
+                     CdnWs* w_out) {
     if (!flow_ok(flow)) return INR_EUNSUPPORTED;
-    const KernelEntry* e = nullptr;
-    if (need_icnn) {
-        e = find_entry(model);
-        if (!e) return INR_EUNSUPPORTED;
-        if (e->c != 2) return INR_EUNSUPPORTED;   // the reference flow is 2-D only (diffeomorphism_net.py:288)
-    }
     if (!workspace || !grid_ok(grid, n_images)) return INR_EINVAL;
-    *w_out = carve_cdn(e, flow, grid, n_images, workspace);
-    if (workspace_bytes < w_out->bytes) return INR_EWORKSPACE;
-    if (e) w_out->icnn.set_user(e, model);
-    if (e) {
-        const int rc = set_lds(e);
-        if (rc) return rc;
-    }
-    *e_out = e;
-    return INR_OK;
+    *w_out = carve_cdn(flow, grid, n_images, workspace);
+    return workspace_bytes < w_out->bytes ? INR_EWORKSPACE : INR_OK;
 }
 
 }  // namespace
@@ -1633,15 +1541,14 @@ int64_t inrfit_cdn_workspace_bytes(const InrModelDesc* model, const InrFlowDesc*
     if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
     const KernelEntry* e = model ? find_entry(model) : nullptr;
     if (model && !e) return INR_EUNSUPPORTED;
-    return carve_cdn(e, flow, grid, n_images, nullptr).bytes;
+    return carve_cdn(flow, grid, n_images, nullptr).bytes + (e ? align256(carve(e, grid->n_points, n_images, nullptr).bytes) : 0);
 }
 
 int inrfit_flow_forward(const InrFlowDesc* flow, const float* flow_params, const InrGridDesc* grid, int n_images,
                         float* out_coords, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     CdnWs w;
     if (!flow_params || !out_coords) return INR_EINVAL;
-    int rc = check_cdn(nullptr, flow, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_cdn(flow, grid, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, s);
@@ -1651,10 +1558,9 @@ int inrfit_flow_forward(const InrFlowDesc* flow, const float* flow_params, const
 
 int inrfit_flow_backward(const InrFlowDesc* flow, const float* flow_params, const InrGridDesc* grid, const float* dout_coords,
                          int n_images, float* flow_grads, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     CdnWs w;
     if (!flow_params || !dout_coords || !flow_grads) return INR_EINVAL;
-    int rc = check_cdn(nullptr, flow, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_cdn(flow, grid, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     launch_flow_update(w, flow, n_images, 2, (float*)flow_params, nullptr, s);
@@ -1671,7 +1577,6 @@ int inrfit_flow_backward(const InrFlowDesc* flow, const float* flow_params, cons
 namespace {
 
 struct PcnWs {
-    Workspace icnn;
     float *xd, *dxd, *zs, *ps, *slab1, *slab2, *RE, *lossp;
     int blocksL;
     int blocks1, chunks, S1;      // blocks1 = blocks of the backward point kernel (rows of slab1)
@@ -1718,7 +1623,7 @@ static RnvpMap make_rnvp_map(const InrRnvpDesc* r) {
     return m;
 }
 
-static PcnWs carve_pcn(const KernelEntry* e, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* base) {
+static PcnWs carve_pcn(const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* base) {
     PcnWs w;
     const long long N = grid->n_points;
     w.rm = make_rnvp_map(r);
@@ -1769,10 +1674,6 @@ static PcnWs carve_pcn(const KernelEntry* e, const InrRnvpDesc* r, const InrGrid
     w.dgrid.mode = INR_GRID_EXPLICIT;
     w.dgrid.coords = w.xd;
     w.dgrid.coords_image_stride = (long long)C * N;
-    if (e) {
-        w.icnn = carve(e, N, n_images, b + off);
-        off += align256(w.icnn.bytes);
-    }
     w.bytes = off;
     return w;
 }
@@ -1807,27 +1708,14 @@ static int rnvp_set_lds() {
     return rc;
 }
 
-static int check_pcn(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* workspace,
-              int64_t workspace_bytes, bool need_icnn, const KernelEntry** e_out, PcnWs* w_out) {
+// the RealNVP on its own (inrfit_rnvp_*); in front of an ICNN: check_deformed
+static int check_pcn(const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* workspace, int64_t workspace_bytes, PcnWs* w_out) {
     if (!rnvp_ok(r)) return INR_EUNSUPPORTED;
-    const KernelEntry* e = nullptr;
-    if (need_icnn) {
-        e = find_entry(model);
-        if (!e) return INR_EUNSUPPORTED;
-        if (e->c != r->channels) return INR_EINVAL;
-    }
     if (!workspace || !grid_ok(grid, n_images)) return INR_EINVAL;
     if (grid->mode == INR_GRID_SEPARABLE && r->channels == 3 && !grid->ts) return INR_EINVAL;   // the separable grid's t axis
-    *w_out = carve_pcn(e, r, grid, n_images, workspace);
+    *w_out = carve_pcn(r, grid, n_images, workspace);
     if (workspace_bytes < w_out->bytes) return INR_EWORKSPACE;
-    if (const int rc = rnvp_set_lds()) return rc;   // flow records of wide MLPs exceed the default 64 KB of dynamic LDS
-    if (e) w_out->icnn.set_user(e, model);
-    if (e) {
-        const int rc = set_lds(e);
-        if (rc) return rc;
-    }
-    *e_out = e;
-    return INR_OK;
+    return rnvp_set_lds();   // flow records of wide MLPs exceed the default 64 KB of dynamic LDS
 }
 
 // parameters -> packed image; once per parameter set, in front of the forward
@@ -1980,40 +1868,6 @@ void launch_rnvp_grads(const PcnWs& w, int n_images, float* rp, float* grads_out
     launch_rnvp_update_args(w, n_images, make_rnvp_upd_args(w, n_images, 1, rp, nullptr, grads_out, nullptr, 0.f, 0, nullptr, 0, nullptr), s);
 }
 
-// ---- the RealNVP in front of the layer-by-layer ICNN (wide.h): shapes without a fused kernel ---------------------------------------
-// An ICNN-form shape of the layer-by-layer path: relu layer 0, one output, square layers (the encode shapes stay refused).
-static bool pcn_wide_shape(const InrModelDesc* m) { return use_wide(m) && m->act0 == INR_ACT_RELU && !wide_desc_general(m); }
-
-// workspace: the RealNVP's buffers for all images (carve_pcn without an ICNN) | logits [N] | dL/dlogits [N] | ONE image's
-// layer-by-layer workspace | the loss coefficients of every image
-struct PcnWideWs {
-    PcnWs p;
-    WideMap m;
-    WideWs w;
-    float *logit, *dy, *coef;
-    long long bytes;
-};
-
-static PcnWideWs carve_pcn_wide(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* base) {
-    PcnWideWs q;
-    q.p = carve_pcn(nullptr, r, grid, n_images, base);
-    q.m = make_wide_map(model);
-    const long long N = grid->n_points;
-    char* b = (char*)base;
-    long long off = q.p.bytes;
-    q.logit = (float*)(b + off); off += align256(N * 4);
-    q.dy = (float*)(b + off); off += align256(N * 4);
-    q.w = carve_wide(q.m, N, false, b + off);
-    off += q.w.bytes;
-    q.coef = (float*)(b + off); off += wide_align((long long)n_images * 2 * 4);
-    q.bytes = off;
-    return q;
-}
-
-static int64_t pcn_wide_bytes(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images) {
-    return carve_pcn_wide(model, r, grid, n_images, nullptr).bytes;
-}
-
 }  // namespace
 
 int64_t inrfit_rnvp_param_count(const InrRnvpDesc* rnvp) {
@@ -2025,19 +1879,19 @@ int64_t inrfit_pcn_workspace_bytes(const InrModelDesc* model, const InrRnvpDesc*
     if (!rnvp_ok(rnvp)) return INR_EUNSUPPORTED;
     if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
     const KernelEntry* e = model ? find_entry(model) : nullptr;
-    if (model && !e) {
+    const long long own = carve_pcn(rnvp, grid, n_images, nullptr).bytes;
+    if (model && !e) {   // the layer-by-layer ICNN behind the RealNVP
         if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
-        return pcn_wide_bytes(model, rnvp, grid, n_images);   // the layer-by-layer ICNN behind the RealNVP
+        return own + carve_wide_behind(make_wide_map(model), grid->n_points, n_images, nullptr).bytes;
     }
-    return carve_pcn(e, rnvp, grid, n_images, nullptr).bytes;
+    return own + (e ? align256(carve(e, grid->n_points, n_images, nullptr).bytes) : 0);
 }
 
 int inrfit_rnvp_actnorm_init(const InrRnvpDesc* rnvp, float* flow_params, const InrGridDesc* grid, int n_images, void* workspace,
                              int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     PcnWs w;
     if (!flow_params) return INR_EINVAL;
-    int rc = check_pcn(nullptr, rnvp, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_pcn(rnvp, grid, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     RnvpInitArgs a{};
     a.RP = flow_params;
@@ -2074,10 +1928,9 @@ int inrfit_rnvp_actnorm_init(const InrRnvpDesc* rnvp, float* flow_params, const 
 
 int inrfit_rnvp_forward(const InrRnvpDesc* rnvp, const float* flow_params, const InrGridDesc* grid, int n_images,
                         float* out_coords, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     PcnWs w;
     if (!flow_params || !out_coords) return INR_EINVAL;
-    int rc = check_pcn(nullptr, rnvp, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_pcn(rnvp, grid, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     launch_rnvp_fwd(w, flow_params, grid, n_images, out_coords, false, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
@@ -2085,10 +1938,9 @@ int inrfit_rnvp_forward(const InrRnvpDesc* rnvp, const float* flow_params, const
 
 int inrfit_rnvp_backward(const InrRnvpDesc* rnvp, const float* flow_params, const InrGridDesc* grid, const float* dout_coords,
                          int n_images, float* flow_grads, float* din_coords, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     PcnWs w;
     if (!flow_params || !dout_coords || !flow_grads) return INR_EINVAL;
-    int rc = check_pcn(nullptr, rnvp, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_pcn(rnvp, grid, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     if (w.sb.U != 1) {   // (a forced U-lanes-per-point shape: the seeded walk runs one lane per point; fewer slab rows than carved)
         w.sb = FlowShape{1, 1, 256, (int)((grid->n_points + 255) / 256)};
@@ -2103,7 +1955,6 @@ int inrfit_rnvp_backward(const InrRnvpDesc* rnvp, const float* flow_params, cons
 
 int inrfit_rnvp_inverse(const InrRnvpDesc* rnvp, const float* flow_params, const float* in_coords, int64_t in_image_stride,
                         int64_t n_points, int n_images, float* out_coords, void* workspace, int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     PcnWs w;
     if (!flow_params || !in_coords || !out_coords || n_points <= 0) return INR_EINVAL;
     InrGridDesc g{};
@@ -2111,7 +1962,7 @@ int inrfit_rnvp_inverse(const InrRnvpDesc* rnvp, const float* flow_params, const
     g.n_points = n_points;
     g.coords = in_coords;
     g.coords_image_stride = in_image_stride;
-    int rc = check_pcn(nullptr, rnvp, &g, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_pcn(rnvp, &g, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     launch_rnvp_pack(w, flow_params, n_images, s);
@@ -2132,11 +1983,10 @@ int inrfit_rnvp_inverse(const InrRnvpDesc* rnvp, const float* flow_params, const
 int inrfit_rnvp_fit_identity(const InrRnvpDesc* rnvp, float* flow_params, float* flow_opt_state, const InrGridDesc* grid,
                              const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist, void* workspace,
                              int64_t workspace_bytes, void* stream) {
-    const KernelEntry* e;
     PcnWs w;
     if (!flow_params || !flow_opt_state || !opt || steps < 0 || step0 < 0) return INR_EINVAL;
     if (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) return INR_EINVAL;
-    int rc = check_pcn(nullptr, rnvp, grid, n_images, workspace, workspace_bytes, false, &e, &w);
+    int rc = check_pcn(rnvp, grid, n_images, workspace, workspace_bytes, &w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int C = w.rm.C;
@@ -2339,8 +2189,7 @@ struct JointCtx {
     float* logits;
     InrLossDesc prior_loss;   // the data term the prior's step kernel evaluates
     const float* prior_targets;
-    const float* align_seg;   // AWESOME_IMAGE with the extra penalty: the step kernel's align mode (seg, beta / n), else null
-    float c_align;
+    DataTerm term;            // AWESOME_IMAGE with the extra penalty: the pass's align mode (seg, beta / n, hard, every point), else none
 };
 
 // the loss, optimizer and step arguments of a joint step
@@ -2361,8 +2210,7 @@ int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float
     if ((rc = make_joint_args(seg, target, 1, N, desc, nullptr, jws, &c->jl))) return rc;
     c->gscale = c->jl.res + JL_RES;
     c->logits = prior_logits;
-    c->align_seg = nullptr;
-    c->c_align = 0.f;
+    c->term = DataTerm{};
     hipLaunchKernelGGL(joint_loss_partial_kernel<false>, dim3(c->jl.blocks), dim3(256), 0, s, c->jl);
     const bool fbms = desc->form == INR_JOINT_FBMS;
     hipLaunchKernelGGL(joint_prep_kernel, dim3(1), dim3(64), 0, s, icnn_hdr, opt->lr, step, coef, 1.f / (float)N, fbms ? 1 : 0);
@@ -2375,45 +2223,36 @@ int joint_begin(const InrJointLossDesc* desc, const InrOptDesc* opt, const float
         float scale = 1.f;
         if (c->jl.pen_on) {   // loss = gamma (crit(seg) + alpha pcrit(prior)) + beta align: both prior terms in the step kernel
             scale = desc->gamma * desc->alpha;
-            c->align_seg = seg;
-            c->c_align = desc->beta / (float)N;
+            c->term.align_seg = seg;
+            c->term.c_align = desc->beta / (float)N;
         }
         hipLaunchKernelGGL(loss_coef_kernel, dim3(1), dim3(256), 0, s, target, N, c->prior_loss, coef, scale);
     }
     return INR_OK;
 }
 
-// the prior's loss column: the step kernel's gradient slabs, or the layer-by-layer path's one-slab gradient vector (wgs = 1, loss_col = P)
-static void joint_finish(const JointCtx& c, const float* slabs, int wgs, int PS, int loss_col, float* loss_out, hipStream_t s) {
+// where a training pass left the prior's loss: column `col` of `wgs` rows of PS floats - the step kernel's gradient slabs, or the
+// layer-by-layer path's one-slab gradient vector (wgs = 1, col = P)
+struct LossColumn {
+    const float* slabs;
+    int wgs, PS, col;
+};
+
+static void joint_finish(const JointCtx& c, const LossColumn& lc, float* loss_out, hipStream_t s) {
     JointFinArgs f{};
     f.jl = c.jl;
-    f.slabs = slabs;
-    f.wgs = wgs;
-    f.PS = PS;
-    f.loss_col = loss_col;
+    f.slabs = lc.slabs;
+    f.wgs = lc.wgs;
+    f.PS = lc.PS;
+    f.loss_col = lc.col;
     f.gscale = c.gscale;
     f.loss_out = loss_out;
-    if (c.align_seg) hipLaunchKernelGGL(joint_align_partial_kernel, dim3(c.jl.blocks), dim3(256), 0, s, c.jl, (const float*)c.logits);
+    if (c.term.align_seg) hipLaunchKernelGGL(joint_align_partial_kernel, dim3(c.jl.blocks), dim3(256), 0, s, c.jl, (const float*)c.logits);
     hipLaunchKernelGGL(joint_step_finish_kernel, dim3(1), dim3(256), 0, s, f);
-}
-static void joint_finish(const JointCtx& c, const KernelEntry* e, const Workspace& w, float* loss_out, hipStream_t s) {
-    joint_finish(c, w.slabs, w.wgs, w.PS, e->img.sl_cols - 1, loss_out, s);
 }
 
 static void joint_dseg(const JointCtx& c, float* dseg, hipStream_t s) {
     hipLaunchKernelGGL(joint_loss_grad_kernel<true>, dim3(c.jl.blocks), dim3(256), 0, s, c.jl, (const float*)c.logits, dseg);
-}
-
-// the ICNN update of a joint step: one optimizer step per call, so no plateau scheduler; the reduced gradient is scaled by the finish
-// kernel's `gscale`
-static UpdArgs joint_upd_args(const KernelEntry* e, const Workspace& w, float* params, float* opt_state, int32_t* status,
-                              const InrOptDesc* opt, int step, const float* gscale) {
-    InrOptDesc o = *opt;
-    o.plateau = 0;
-    UpdArgs u = make_upd_args(e, w, params, opt_state, nullptr, status, &o, 1, 1);
-    u.gscale = gscale;
-    set_step_consts(u, &o, step);
-    return u;
 }
 
 long long joint_ws_bytes(long long N) { return align256(inrfit_joint_loss_workspace_bytes(N)) + align256(N * 4); }
@@ -2429,220 +2268,35 @@ int64_t inrfit_joint_step_workspace_bytes(const InrModelDesc* model, const InrGr
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the three prior families on the ICNN step kernel: one driver per operation (forward, loss + gradients, fit, fused joint step)
+// the host driver: one skeleton per operation (forward, loss + gradients, fit, fused joint step, joint prior step) over two policies
 // ---------------------------------------------------------------------------------------------------------------------
-// The families differ only in the deformation in front of the ICNN: a workspace type with
-//   icnn, dgrid, dxd, bytes    the ICNN's Workspace, the grid its step kernel reads, where that kernel writes dL/dcoords (null: it
-//                              writes none), the bytes of the whole workspace
-//   check(...)                 argument checks, workspace carve, set_lds; the ICNN's kernel entry into *e
-//   begin(s)                   once per call, in front of the first forward
-//   forward(train, packed, s)  the coordinates the ICNN sees into dgrid (train: keep what the backward reads)
-//   gradients(s)               loss_grad: the deformation's backward and its gradients (mode 1)
-//   update(e, u, fit, s)       the deformation's backward and both optimizer steps, the ICNN's `u` included: where upd_union_ok
-//                              allows, the backward and then one combined update launch; else icnn_update_kernel, the backward and
-//                              the deformation's own update.  `u` carries status (fit and joint step) and gscale (joint step only).
-namespace {
-
-struct IcnnOnly {   // ConvexNet / ConvexNextNet: the ICNN on the caller's grid
-    Workspace icnn;
-    InrGridDesc dgrid;
-    float* dxd = nullptr;
-    long long bytes = 0;
-    int check(const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* ws, int64_t ws_bytes, const KernelEntry** e) {
-        if (const int rc = prepare(model, grid, n_images, ws, ws_bytes, e, &icnn)) return rc;
-        dgrid = *grid;
-        bytes = icnn.bytes;
-        return INR_OK;
-    }
-    void begin(hipStream_t) {}
-    void forward(bool, bool, hipStream_t) {}
-    void gradients(hipStream_t) {}
-    void update(const KernelEntry* e, const UpdArgs& u, bool, hipStream_t s) { launch_icnn_update(e, u, s); }
-};
-
-struct CdnStep : CdnWs {   // ConvexDiffeomorphismNet: the ICNN behind the weight-normed coupling flow
-    const InrFlowDesc* flow;
-    float *params, *opt_state, *grads;   // the flow's (opt_state: fit and joint step; grads: loss_grad)
-    float wd_g;                          // weight decay on weight_g
-    const InrGridDesc* grid = nullptr;   // the caller's
-    int n_images = 0;
-    CdnStep(const InrFlowDesc* f, const float* p, float* o = nullptr, float* g = nullptr, float wd = 0.f)
-        : flow(f), params(const_cast<float*>(p)), opt_state(o), grads(g), wd_g(wd) {}
-    int check(const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, const KernelEntry** e) {
-        grid = g;
-        n_images = n;
-        return check_cdn(model, flow, g, n, ws, ws_bytes, true, e, this);
-    }
-    // the flow's effective weights (mode 2): once per call; in the fit, the update kernel rebuilds them after every step
-    void begin(hipStream_t s) { launch_flow_update(*this, flow, n_images, 2, params, nullptr, s); }
-    void forward(bool, bool, hipStream_t s) { launch_flow_fwd(*this, grid, n_images, xd, s); }
-    void gradients(hipStream_t s) {
-        launch_flow_bwd(*this, flow, grid, n_images, s);
-        launch_flow_update(*this, flow, n_images, 1, params, grads, s);
-    }
-    void update(const KernelEntry* e, const UpdArgs& u, bool, hipStream_t s) {
-        // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
-        const FlowUpdArgs uf = make_flow_upd_args(*this, 0, params, opt_state, nullptr, &u.opt, wd_g, u.t, u.opt_state + 2 * (size_t)u.Pu,
-                                                  2 * (long long)u.Pu + INR_OPT_HEADER_FLOATS, u.status, u.gscale);
-        if (upd_union_ok(e->img.sl_cols, 2 * flow->num_coupling + 1)) {
-            launch_flow_bwd(*this, flow, grid, n_images, s);
-            launch_cdn_update(e, u, uf, flow, n_images, s);   // (the ICNN half writes `status`: the flow half gets none)
-        } else {
-            launch_icnn_update(e, u, s);
-            launch_flow_bwd(*this, flow, grid, n_images, s);
-            launch_flow_update_args(flow, n_images, uf, s);
-        }
-    }
-};
-
-struct PcnStep : PcnWs {   // PathConnectedNet: the ICNN behind the normflows RealNVP
-    const InrRnvpDesc* rnvp;
-    float *params, *opt_state, *grads;   // the RealNVP's (opt_state: fit and joint step; grads: loss_grad)
-    float wd;                            // its weight decay
-    const InrGridDesc* grid = nullptr;   // the caller's
-    int n_images = 0;
-    PcnStep(const InrRnvpDesc* r, const float* p, float* o = nullptr, float* g = nullptr, float w = 0.f)
-        : rnvp(r), params(const_cast<float*>(p)), opt_state(o), grads(g), wd(w) {}
-    int check(const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, const KernelEntry** e) {
-        grid = g;
-        n_images = n;
-        return check_pcn(model, rnvp, g, n, ws, ws_bytes, true, e, this);
-    }
-    void begin(hipStream_t) {}
-    // the parameters are packed into RE in front of the forward - except in the fit after its first step (`packed`), where the update
-    // kernel has refreshed RE (update with fit = true)
-    void forward(bool train, bool packed, hipStream_t s) { launch_rnvp_fwd(*this, params, grid, n_images, xd, train, s, false, packed); }
-    void gradients(hipStream_t s) {
-        launch_rnvp_bwd(*this, params, grid, n_images, s);
-        launch_rnvp_grads(*this, n_images, params, grads, s);
-    }
-    void update(const KernelEntry* e, const UpdArgs& u, bool fit, hipStream_t s) {
-        // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
-        RnvpUpdArgs ru = make_rnvp_upd_args(*this, n_images, 0, params, opt_state, nullptr, &u.opt, wd, u.t, u.opt_state + 2 * (size_t)u.Pu,
-                                            2 * (long long)u.Pu + INR_OPT_HEADER_FLOATS, u.status);
-        ru.gscale = u.gscale;
-        if (fit) ru.RE = RE;   // the next step's forward reuses it (`packed`)
-        if (upd_union_ok(e->img.sl_cols, rm.F + 1)) {
-            launch_rnvp_bwd(*this, params, grid, n_images, s);
-            launch_pcn_update(e, *this, u, ru, n_images, s);   // (the ICNN half writes `status`: the RealNVP half gets none)
-        } else {
-            launch_icnn_update(e, u, s);
-            launch_rnvp_bwd(*this, params, grid, n_images, s);
-            launch_rnvp_update_args(*this, n_images, ru, s);
-        }
-    }
-};
-
-// the optimizer and loss rules of the fits (a fit evaluates its own loss: no INR_LOSS_EXTERNAL)
-static int check_fit(const InrOptDesc* opt, const InrLossDesc* loss, bool adam_only) {
-    if (opt->kind != INR_OPT_ADAM && (adam_only || opt->kind != INR_OPT_ADAMAX)) return INR_EINVAL;
-    if (const int rc = check_loss(loss)) return rc;
-    return loss->kind == INR_LOSS_EXTERNAL ? INR_EINVAL : INR_OK;
-}
-
-template <class D>
-int forward_run(D d, const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
-                void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    const KernelEntry* e;
-    int rc = d.check(model, grid, n_images, workspace, workspace_bytes, &e);
-    if (rc) return rc;
-    d.begin(s);
-    d.forward(false, false, s);
-    if ((rc = launch_pack(e, d.icnn, params, n_images, s))) return rc;
-    return launch_step(e, d.icnn, false, &d.dgrid, nullptr, 0, n_images, logits, s);
-}
-
-template <class D>
-int loss_grad_run(D d, const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
-                  const InrLossDesc* loss, int n_images, float* loss_out, float* grads, void* workspace, int64_t workspace_bytes,
-                  hipStream_t s) {
-    const KernelEntry* e;
-    int rc = d.check(model, grid, n_images, workspace, workspace_bytes, &e);
-    if (rc) return rc;
-    d.begin(s);
-    d.forward(true, false, s);
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, d.icnn.coef, 1.f);
-    if ((rc = launch_pack(e, d.icnn, params, n_images, s))) return rc;
-    if ((rc = launch_step(e, d.icnn, true, &d.dgrid, targets, loss->kind, n_images, nullptr, s, d.dxd))) return rc;
-    launch_reduce(e, d.icnn, n_images, grads, loss_out, s);
-    d.gradients(s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-template <class D>
-int fit_run(D d, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
-            const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist, float* final_logits,
-            int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    const KernelEntry* e;
-    int rc = d.check(model, grid, n_images, workspace, workspace_bytes, &e);
-    if (rc) return rc;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)grid->n_points, *loss, d.icnn.coef, 1.f);
-    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, d.icnn.Pu, *opt, step0);
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, d.icnn, params, n_images, s))) return rc;
-    d.begin(s);
-    UpdArgs u = make_upd_args(e, d.icnn, params, opt_state, loss_hist, status, opt, n_images, steps);
-    // opt->logits_at_last_forward: final_logits = the output of the LAST training forward (parameters before the last optimizer
-    // step) - what the reference's IoU gate looks at (path_connected_net.py:939-972) - written by that step's launch itself
-    const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
-    for (int it = 0; it < steps; ++it) {
-        d.icnn.set_step(step0 + it);
-        u.slabs = d.icnn.slabs;
-        u.loss_part = d.icnn.loss_part;
-        set_step_consts(u, opt, step0 + it + 1, it);
-        float* logits = gate_logits && it == steps - 1 ? final_logits : nullptr;
-        d.forward(true, it > 0, s);
-        // bench.py's timing hooks (inrfit_timing_*) bracket the plain ICNN fit's launches only: events in the deformed fits would
-        // change what is launched and measured there
-        if constexpr (std::is_same<D, IcnnOnly>::value) {
-            if ((rc = launch_step_timed(e, d.icnn, &d.dgrid, targets, loss->kind, n_images, s, logits))) return rc;
-            if ((rc = launch_icnn_update_timed(e, u, s))) return rc;
-        } else {
-            if ((rc = launch_step(e, d.icnn, true, &d.dgrid, targets, loss->kind, n_images, logits, s, d.dxd))) return rc;
-            d.update(e, u, true, s);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
-    if (final_logits && !gate_logits) {
-        d.forward(false, false, s);
-        return launch_step(e, d.icnn, false, &d.dgrid, nullptr, 0, n_images, final_logits, s);
-    }
-    return INR_OK;
-}
-
-template <class D>
-int joint_step_run(D d, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
-                   const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out, float* dseg,
-                   float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    const KernelEntry* e;
-    int rc = d.check(model, grid, 1, workspace, workspace_bytes, &e);
-    if (rc) return rc;
-    const long long N = grid->n_points;
-    if (workspace_bytes < align256(d.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
-    float* jws = (float*)((char*)workspace + align256(d.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    JointCtx c;
-    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, opt_state + 2 * (size_t)d.icnn.Pu, d.icnn.coef, s, &c))) return rc;
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    if ((rc = launch_pack(e, d.icnn, params, 1, s))) return rc;
-    d.icnn.set_step(step);
-    d.begin(s);
-    d.forward(true, false, s);
-    if ((rc = launch_step(e, d.icnn, true, &d.dgrid, c.prior_targets, c.prior_loss.kind, 1, logits, s, d.dxd, c.align_seg, c.c_align)))
-        return rc;
-    joint_finish(c, e, d.icnn, loss_out, s);
-    d.update(e, joint_upd_args(e, d.icnn, params, opt_state, status, opt, step, c.gscale), false, s);
-    joint_dseg(c, dseg, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------------------------------------------------
-// PathConnectedNet over an ICNN of the layer-by-layer path (n_hidden > 130 or more than two hidden layers): the RealNVP's
-// kernels on all images, then per image wide_forward / wide_backward on the deformed coordinates as an explicit grid with
-// dcoords = dxd, then the RealNVP's backward seeded from dxd.  Everything stays on the stream.
-// ---------------------------------------------------------------------------------------------------------------------
+// A BACKBONE B is the ICNN on a grid.  FusedIcnn runs the hand-written step kernel (KernelEntry + Workspace): one launch covers
+// every image.  WideIcnn runs the layer-by-layer path (WideMap + WideWs): one image at a time through one gradient buffer.  Both give
+//   fused, max_points             whether one launch covers all images; the most points a grid may have
+//   check(...)                    on the caller's grid: shape, arguments and workspace carve (icnn_form: ICNN-form shapes only)
+//   find(model, icnn_form), carve_behind(model, dgrid, n, base)
+//                                 behind a deformation (check_deformed): the shape alone, then the carve at `base` on the deformed grid
+//   loss_ok(loss), device()       the shape's own loss rule; the device's turn (set_lds) once every argument has passed
+//   bytes, P(), coef(), tstride() workspace bytes, parameters per image, loss coefficients, target / logit floats per image
+//   pack(params, s), infer(params, logits, s)
+//                                 parameters into the step kernel's image (nothing layer by layer); the inference pass -> logits
+//   begin_updates(...), set_step(buf, opt, t, hist_idx), u, hdr(), opt_stride(), status()
+//                                 the optimizer step's arguments of this call and of step t; image 0's header, the stride to the next
+//   units()                       gradient buffers walked in turn: 1 (fused), n_images (layer by layer)
+//   train(k, params, pass, s)     the training pass of unit k -> gradients and loss in the unit's buffer (loss_column())
+//   grads_out(k, grads, loss, s)  ... out to the caller
+//   update(k, s)                  ... into the optimizer step.  Layer by layer it sits inside the unit loop: the buffer is one image's.
+// A DEFORMATION F is what runs in front of the backbone: NoDeform, FlowDeform (the coupling flow; fused backbone only) or
+// RnvpDeform.  It gives
+//   none, dxd, bytes              whether it is NoDeform; where the pass writes dL/dcoords (null: none); bytes of the whole workspace
+//   check(b, ...), device()       every argument check and both carves (check_deformed); its set_lds
+//   begin(s)                      once per call, in front of the first forward
+//   forward(train, packed, s)     the coordinates the backbone sees (train: keep what the backward reads)
+//   gradients(s)                  loss_grad: its backward and its gradients (mode 1)
+//   update(b, fit, s)             its backward seeded from dxd and its optimizer step, which reads this step's learning rate and the
+//                                 frozen flag from the ICNN headers and b.u's status and gscale.  Over the fused backbone it owns the
+//                                 ICNN's update too (the skeletons skip b.update): where upd_union_ok allows, the backward and one
+//                                 combined launch, else icnn_update_kernel, the backward, its own update.
 namespace {
 
 // dL/dlogit of the data term from the logits wide_out_kernel wrote (wide_data_term, the expressions of its own dy, which it keeps in
@@ -2658,122 +2312,425 @@ __global__ __launch_bounds__(256) void pcn_wide_dy_kernel(const float* __restric
     dy[p] = d;
 }
 
-static int check_pcn_wide(const InrModelDesc* model, const InrRnvpDesc* r, const InrGridDesc* grid, int n_images, void* workspace,
-                          int64_t workspace_bytes, PcnWideWs* q) {   // arguments only: rnvp_set_lds() is the caller's next step
-    if (!rnvp_ok(r)) return INR_EUNSUPPORTED;
-    if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
-    if (model->in_features != r->channels) return INR_EINVAL;
-    if (!workspace || !grid_ok(grid, n_images, 0x7fffffffLL / WIDE_MAX_HIDDEN * 64)) return INR_EINVAL;
-    if (grid->mode == INR_GRID_SEPARABLE && r->channels == 3 && !grid->ts) return INR_EINVAL;   // the separable grid's t axis
-    *q = carve_pcn_wide(model, r, grid, n_images, workspace);
-    return workspace_bytes < q->bytes ? INR_EWORKSPACE : INR_OK;
-}
+// one training pass, as a skeleton asks a backbone for it
+struct TrainPass {
+    const float* targets;             // [n_images][tstride]; INR_LOSS_EXTERNAL: dL/dlogits
+    int loss_kind;
+    float* logits = nullptr;          // [n_images][tstride]: the pass leaves its logits here as well, or null
+    float* dxd = nullptr;             // [n_images][C][N]: dL/dcoords as well, or null
+    const DataTerm* term = nullptr;   // a joint step's data term, or null
+    int freeze_input = 0;             // the fit's opt->freeze_input: a general shape then skips dZ_0
+};
 
-static int pcn_wide_forward(const InrModelDesc* model, const InrRnvpDesc* r, const float* ip, const float* fp, const InrGridDesc* grid,
-                            int n_images, float* logits, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    PcnWideWs q;
-    int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
-    if (rc || (rc = rnvp_set_lds())) return rc;
-    launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, false, s);
-    for (int img = 0; img < n_images; ++img)
-        if ((rc = wide_forward(q.m, q.w, model, ip + (size_t)img * q.m.P, &q.p.dgrid, img, nullptr, 0, false,
-                               logits + (size_t)img * grid->n_points, s)))
-            return rc;
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
+struct FusedIcnn {
+    static constexpr bool fused = true;
+    static constexpr long long max_points = 0x7fffffffLL;
+    const KernelEntry* e = nullptr;
+    Workspace w;
+    InrGridDesc grid;   // the grid the step kernel reads: the caller's, or the deformation's
+    int n_images = 0;
+    long long bytes = 0;
+    bool timed = false;   // bench.py's timing hooks (inrfit_timing_*) bracket the launches: the plain fit only
+    UpdArgs u;
 
-// forward + backward of image `img` on the deformed grid: gradients and the loss into q.w.grads, dL/dxd into q.p.dxd
-// `logits` [N]: where the output pass leaves them (q.logit, or the caller's); `jn`: the data term of a joint step, or null
-static int pcn_wide_image(PcnWideWs& q, const InrModelDesc* model, const float* p, int img, const float* target, int loss_kind,
-                          float* logits, const WideJoint* jn, hipStream_t s) {
-    const long long N = q.p.dgrid.n_points;
-    const bool ext = loss_kind == INR_LOSS_EXTERNAL;
-    q.w.coef = q.coef + 2 * img;
-    int rc = wide_forward(q.m, q.w, model, p, &q.p.dgrid, img, target, loss_kind, true, ext ? nullptr : logits, s, jn);
-    if (rc) return rc;
-    const dim3 dygrid((unsigned)((N + 255) / 256));
-    if (jn)
-        hipLaunchKernelGGL(pcn_wide_dy_kernel<true>, dygrid, dim3(256), 0, s, (const float*)logits, target, (const float*)q.w.coef, loss_kind, N,
-                           q.dy, *jn);
-    else if (!ext)
-        hipLaunchKernelGGL(pcn_wide_dy_kernel<false>, dygrid, dim3(256), 0, s, (const float*)logits, target, (const float*)q.w.coef, loss_kind,
-                           N, q.dy, WideJoint{});
-    return wide_backward(q.m, q.w, model, p, N, s, ext ? target : q.dy, q.p.dxd + (size_t)img * q.m.C * N);
-}
-
-static int pcn_wide_loss_grad(const InrModelDesc* model, const InrRnvpDesc* r, const float* ip, const float* fp, const InrGridDesc* grid,
-                              const float* targets, const InrLossDesc* loss, int n_images, float* loss_out, float* icnn_grads,
-                              float* flow_grads, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    PcnWideWs q;
-    int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
-    if (rc || (rc = rnvp_set_lds())) return rc;
-    const long long N = grid->n_points;
-    launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, true, s);
-    if (loss->kind != INR_LOSS_EXTERNAL) hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, q.coef, 1.f);
-    for (int img = 0; img < n_images; ++img) {
-        if ((rc = pcn_wide_image(q, model, ip + (size_t)img * q.m.P, img, targets + (size_t)img * N, loss->kind, q.logit, nullptr, s))) return rc;
-        if (hipMemcpyAsync(icnn_grads + (size_t)img * q.m.P, q.w.grads, sizeof(float) * q.m.P, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
-        if (hipMemcpyAsync(loss_out + img, q.w.grads + q.m.P, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
+    int check(const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool) {
+        if (const int rc = prepare_args(model, g, n, ws, ws_bytes, &e, &w)) return rc;
+        grid = *g;
+        n_images = n;
+        bytes = w.bytes;
+        return INR_OK;
     }
-    launch_rnvp_bwd(q.p, fp, grid, n_images, s);
-    launch_rnvp_grads(q.p, n_images, const_cast<float*>(fp), flow_grads, s);
+    bool find(const InrModelDesc* model, bool) { return (e = find_entry(model)) != nullptr; }
+    long long carve_behind(const InrModelDesc* model, const InrGridDesc& dgrid, int n, void* base) {
+        w = carve(e, dgrid.n_points, n, base);
+        w.set_user(e, model);
+        grid = dgrid;
+        n_images = n;
+        return align256(w.bytes);
+    }
+    int loss_ok(const InrLossDesc*) const { return INR_OK; }
+    int device() { return set_lds(e); }
+    int P() const { return w.Pu; }
+    float* coef() const { return w.coef; }
+    long long tstride() const { return grid.n_points; }
+    bool coef_for(int) const { return true; }
+    int units() const { return 1; }
+    int pack(const float* params, hipStream_t s) { return launch_pack(e, w, params, n_images, s); }
+    int infer(const float*, float* logits, hipStream_t s) { return launch_step(e, w, false, &grid, nullptr, 0, n_images, logits, s); }
+    void begin_updates(float* params, float* opt_state, float* loss_hist, int32_t* status, const InrOptDesc* opt, int steps) {
+        u = make_upd_args(e, w, params, opt_state, loss_hist, status, opt, n_images, steps);
+    }
+    void set_step(int buf, const InrOptDesc* opt, int t, int hist_idx) {
+        w.set_step(buf);
+        u.slabs = w.slabs;
+        u.loss_part = w.loss_part;
+        set_step_consts(u, opt, t, hist_idx);
+    }
+    float* hdr() const { return u.opt_state + 2 * (size_t)u.Pu; }
+    long long opt_stride() const { return 2 * (long long)u.Pu + INR_OPT_HEADER_FLOATS; }
+    int32_t* status() const { return u.status; }
+    int train(int, const float*, const TrainPass& a, hipStream_t s) {
+        if (timed) return launch_step_timed(e, w, &grid, a.targets, a.loss_kind, n_images, s, a.logits);
+        return launch_step(e, w, true, &grid, a.targets, a.loss_kind, n_images, a.logits, s, a.dxd, a.term ? *a.term : DataTerm{});
+    }
+    LossColumn loss_column() const { return LossColumn{w.slabs, w.wgs, w.PS, e->img.sl_cols - 1}; }
+    int grads_out(int, float* grads, float* loss_out, hipStream_t s) {
+        launch_reduce(e, w, n_images, grads, loss_out, s);
+        return INR_OK;
+    }
+    int update(int, hipStream_t s) {
+        if (timed) return launch_icnn_update_timed(e, u, s);
+        launch_icnn_update(e, u, s);
+        return INR_OK;
+    }
+};
+
+struct WideIcnn {
+    static constexpr bool fused = false;
+    static constexpr long long max_points = 0x7fffffffLL / WIDE_MAX_HIDDEN * 64;
+    const InrModelDesc* model = nullptr;
+    WideMap m;
+    WideWs w;
+    float *coef_all = nullptr, *logit = nullptr, *dy = nullptr;   // logit, dy [N]: behind a deformation only
+    InrGridDesc grid;
+    int n_images = 0;
+    long long bytes = 0;
+    UpdArgs u;   // the one-slab view of w.grads; its per-image pointers are update's, from:
+    float *params0 = nullptr, *opt0 = nullptr, *hist0 = nullptr;
+    int32_t* status0 = nullptr;
+
+    bool find(const InrModelDesc* md, bool icnn_form) {
+        model = md;
+        return icnn_form ? pcn_wide_shape(md) : use_wide(md);
+    }
+    int check(const InrModelDesc* md, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool icnn_form) {
+        if (!find(md, icnn_form)) return INR_EUNSUPPORTED;
+        if (!ws || !grid_ok(g, n, max_points)) return INR_EINVAL;
+        if (md->act0 < INR_ACT_RELU || md->act0 > INR_ACT_SIN) return INR_EINVAL;
+        m = make_wide_map(md);
+        const bool pre0 = md->act0 != INR_ACT_RELU;
+        bytes = wide_total_bytes(m, g->n_points, pre0, n);
+        if (ws_bytes < bytes) return INR_EWORKSPACE;
+        w = carve_wide(m, g->n_points, pre0, ws);
+        coef_all = (float*)((char*)ws + w.bytes);
+        grid = *g;
+        n_images = n;
+        return INR_OK;
+    }
+    long long carve_behind(const InrModelDesc* md, const InrGridDesc& dgrid, int n, void* base) {
+        m = make_wide_map(md);
+        const WideBehind q = carve_wide_behind(m, dgrid.n_points, n, base);
+        w = q.w;
+        coef_all = q.coef;
+        logit = q.logit;
+        dy = q.dy;
+        grid = dgrid;
+        n_images = n;
+        return q.bytes;
+    }
+    // several outputs: 'mean' over the O x N elements (torch's MSELoss on (N, O)), no class weights from the targets
+    int loss_ok(const InrLossDesc* l) const {
+        return m.O > 1 && l->weight_mode != INR_WEIGHT_NONE && l->weight_mode != INR_WEIGHT_EXPLICIT ? INR_EINVAL : INR_OK;
+    }
+    int device() { return INR_OK; }
+    int P() const { return m.P; }
+    float* coef() const { return coef_all; }
+    long long tstride() const { return (long long)m.O * grid.n_points; }
+    bool coef_for(int loss_kind) const { return loss_kind != INR_LOSS_EXTERNAL; }   // (targets = dL/dlogits: nothing to weigh)
+    int units() const { return n_images; }
+    int pack(const float*, hipStream_t) { return INR_OK; }   // (wide_forward's layer-0 launch packs the weights)
+    int infer(const float* params, float* logits, hipStream_t s) {
+        for (int img = 0; img < n_images; ++img)
+            if (const int rc = wide_forward(m, w, model, params + (size_t)img * m.P, &grid, img, nullptr, 0, false,
+                                            logits + (size_t)img * tstride(), s))
+                return rc;
+        return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    }
+    void begin_updates(float* params, float* opt_state, float* loss_hist, int32_t* status, const InrOptDesc* opt, int steps) {
+        u = wide_upd_args(m, w.grads, opt, steps);
+        params0 = params;
+        opt0 = opt_state;
+        hist0 = loss_hist;
+        status0 = status;
+    }
+    void set_step(int, const InrOptDesc* opt, int t, int hist_idx) { set_step_consts(u, opt, t, hist_idx); }
+    float* hdr() const { return opt0 + 2 * (size_t)m.P; }
+    long long opt_stride() const { return 2 * (long long)m.P + INR_OPT_HEADER_FLOATS; }
+    int32_t* status() const { return status0; }
+    // forward + backward of image k: gradients and the loss into w.grads.  With dxd, dL/dlogits (dy) comes from the logits of the
+    // output pass, which a fit or loss_grad keeps in the scratch row `logit` (and copies out where asked) and a joint step writes to the
+    // caller's row.
+    int train(int k, const float* params, const TrainPass& a, hipStream_t s) {
+        const long long N = grid.n_points, ON = tstride();
+        const bool ext = a.loss_kind == INR_LOSS_EXTERNAL, need_dy = a.dxd && !ext;
+        const float* p = params + (size_t)k * m.P;
+        const float* tg = a.targets + (size_t)k * ON;
+        float* out = a.logits ? a.logits + (size_t)k * ON : nullptr;
+        float* lg = need_dy && !a.term ? logit : out;
+        WideJoint jn{};
+        if (a.term) {
+            jn.seg = a.term->align_seg;
+            jn.c_align = a.term->c_align;
+            jn.data_count = a.term->data_count > 0 ? a.term->data_count : N;
+            jn.align_begin = a.term->align_begin;
+            jn.use_noneclass = a.term->use_noneclass;
+            jn.align_soft = a.term->align_soft;
+            jn.noneclass = a.term->noneclass;
+        }
+        w.coef = coef_all + 2 * k;
+        int rc = wide_forward(m, w, model, p, &grid, k, tg, a.loss_kind, true, ext ? nullptr : lg, s, a.term ? &jn : nullptr);
+        if (rc) return rc;
+        if (need_dy) {
+            const dim3 dygrid((unsigned)((N + 255) / 256));
+            if (a.term)
+                hipLaunchKernelGGL(pcn_wide_dy_kernel<true>, dygrid, dim3(256), 0, s, (const float*)lg, tg, (const float*)w.coef, a.loss_kind, N,
+                                   dy, jn);
+            else
+                hipLaunchKernelGGL(pcn_wide_dy_kernel<false>, dygrid, dim3(256), 0, s, (const float*)lg, tg, (const float*)w.coef, a.loss_kind,
+                                   N, dy, jn);
+        }
+        if ((rc = wide_backward(m, w, model, p, N, s, need_dy ? dy : tg, a.dxd ? a.dxd + (size_t)k * m.C * N : nullptr,
+                                !(m.general() && a.freeze_input))))   // frozen features: dZ_0 has no use
+            return rc;
+        if (lg != out && out && hipMemcpyAsync(out, lg, sizeof(float) * N, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
+        return INR_OK;
+    }
+    LossColumn loss_column() const { return LossColumn{w.grads, 1, u.PS, m.P}; }
+    int grads_out(int k, float* grads, float* loss_out, hipStream_t s) {
+        if (hipMemcpyAsync(grads + (size_t)k * m.P, w.grads, sizeof(float) * m.P, hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
+        if (loss_out && hipMemcpyAsync(loss_out + k, w.grads + m.P, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return INR_ELAUNCH;
+        return INR_OK;
+    }
+    // icnn_update_kernel on the one-slab view (it writes the next learning rate and the "frozen" flag into the image's header)
+    int update(int k, hipStream_t s) {
+        u.params = params0 + (size_t)k * m.P;
+        u.opt_state = opt0 + (size_t)k * opt_stride();
+        u.loss_hist = hist0 ? hist0 + (size_t)k * u.hist_stride : nullptr;
+        u.status = status0 ? status0 + k : nullptr;
+        launch_wide_update(m, u, s);
+        return INR_OK;
+    }
+};
+
+// The checks of a deformed prior, every argument and no device call: the deformation's description and the backbone's shape, the
+// channels, the workspace pointer and the grid, then the carve: the deformation's buffers | the backbone's on the deformed grid.
+template <class F, class B>
+int check_deformed(F& f, B& b, const InrModelDesc* model, const InrGridDesc* grid, int n_images, void* ws, int64_t ws_bytes) {
+    if (!f.desc_ok() || !b.find(model, true)) return INR_EUNSUPPORTED;
+    if (const int rc = f.channels_ok(model->in_features)) return rc;
+    if (!ws || !grid_ok(grid, n_images, B::max_points) || !f.grid_rule(grid)) return INR_EINVAL;
+    f.carve(grid, n_images, ws);
+    f.bytes += b.carve_behind(model, f.dgrid, n_images, (char*)ws + f.bytes);
+    return ws_bytes < f.bytes ? INR_EWORKSPACE : INR_OK;
+}
+
+struct NoDeform {   // ConvexNet / ConvexNextNet: the ICNN on the caller's grid
+    static constexpr bool none = true;
+    float* dxd = nullptr;
+    long long bytes = 0;
+    template <class B>
+    int check(B& b, const InrModelDesc* model, const InrGridDesc* grid, int n, void* ws, int64_t ws_bytes, bool icnn_form) {
+        const int rc = b.check(model, grid, n, ws, ws_bytes, icnn_form);
+        bytes = b.bytes;
+        return rc;
+    }
+    int device() { return INR_OK; }
+    void begin(hipStream_t) {}
+    void forward(bool, bool, hipStream_t) {}
+    void gradients(hipStream_t) {}
+    template <class B>
+    void update(B&, bool, hipStream_t) {}
+};
+
+struct FlowDeform : CdnWs {   // ConvexDiffeomorphismNet: the ICNN behind the weight-normed coupling flow
+    static constexpr bool none = false;
+    const InrFlowDesc* flow;
+    float *params, *opt_state, *grads;   // the flow's (opt_state: fit and joint step; grads: loss_grad)
+    float wd_g;                          // weight decay on weight_g
+    const InrGridDesc* grid = nullptr;   // the caller's
+    int n_images = 0;
+    FlowDeform(const InrFlowDesc* f, const float* p, float* o = nullptr, float* g = nullptr, float wd = 0.f)
+        : flow(f), params(const_cast<float*>(p)), opt_state(o), grads(g), wd_g(wd) {}
+    bool desc_ok() const { return flow_ok(flow); }
+    int channels_ok(int c) const { return c == 2 ? INR_OK : INR_EUNSUPPORTED; }   // the reference flow is 2-D only (diffeomorphism_net.py:288)
+    bool grid_rule(const InrGridDesc*) const { return true; }
+    void carve(const InrGridDesc* g, int n, void* ws) {
+        static_cast<CdnWs&>(*this) = carve_cdn(flow, g, n, ws);
+        grid = g;
+        n_images = n;
+    }
+    template <class B>
+    int check(B& b, const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool) {
+        static_assert(B::fused, "the coupling flow runs over the fused backbone only");
+        return check_deformed(*this, b, model, g, n, ws, ws_bytes);
+    }
+    int device() { return INR_OK; }
+    // the flow's effective weights (mode 2): once per call; in the fit, the update kernel rebuilds them after every step
+    void begin(hipStream_t s) { launch_flow_update(*this, flow, n_images, 2, params, nullptr, s); }
+    void forward(bool, bool, hipStream_t s) { launch_flow_fwd(*this, grid, n_images, xd, s); }
+    void gradients(hipStream_t s) {
+        launch_flow_bwd(*this, flow, grid, n_images, s);
+        launch_flow_update(*this, flow, n_images, 1, params, grads, s);
+    }
+    void update(FusedIcnn& b, bool, hipStream_t s) {
+        // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
+        const UpdArgs& u = b.u;
+        const FlowUpdArgs uf = make_flow_upd_args(*this, 0, params, opt_state, nullptr, &u.opt, wd_g, u.t, b.hdr(), b.opt_stride(),
+                                                  b.status(), u.gscale);
+        if (upd_union_ok(b.e->img.sl_cols, 2 * flow->num_coupling + 1)) {
+            launch_flow_bwd(*this, flow, grid, n_images, s);
+            launch_cdn_update(b.e, u, uf, flow, n_images, s);   // (the ICNN half writes `status`: the flow half gets none)
+        } else {
+            launch_icnn_update(b.e, u, s);
+            launch_flow_bwd(*this, flow, grid, n_images, s);
+            launch_flow_update_args(flow, n_images, uf, s);
+        }
+    }
+};
+
+struct RnvpDeform : PcnWs {   // PathConnectedNet: the ICNN behind the normflows RealNVP
+    static constexpr bool none = false;
+    const InrRnvpDesc* rnvp;
+    float *params, *opt_state, *grads;   // the RealNVP's (opt_state: fit and joint step; grads: loss_grad)
+    float wd;                            // its weight decay
+    const InrGridDesc* grid = nullptr;   // the caller's
+    int n_images = 0;
+    RnvpDeform(const InrRnvpDesc* r, const float* p, float* o = nullptr, float* g = nullptr, float w = 0.f)
+        : rnvp(r), params(const_cast<float*>(p)), opt_state(o), grads(g), wd(w) {}
+    bool desc_ok() const { return rnvp_ok(rnvp); }
+    int channels_ok(int c) const { return c == rnvp->channels ? INR_OK : INR_EINVAL; }
+    bool grid_rule(const InrGridDesc* g) const { return !(g->mode == INR_GRID_SEPARABLE && rnvp->channels == 3 && !g->ts); }   // the t axis
+    void carve(const InrGridDesc* g, int n, void* ws) {
+        static_cast<PcnWs&>(*this) = carve_pcn(rnvp, g, n, ws);
+        grid = g;
+        n_images = n;
+    }
+    template <class B>
+    int check(B& b, const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool) {
+        return check_deformed(*this, b, model, g, n, ws, ws_bytes);
+    }
+    int device() { return rnvp_set_lds(); }   // flow records of wide MLPs exceed the default 64 KB of dynamic LDS
+    void begin(hipStream_t) {}
+    // the parameters are packed into RE in front of the forward - except in the fit after its first step (`packed`), where the update
+    // kernel has refreshed RE (update with fit = true)
+    void forward(bool train, bool packed, hipStream_t s) { launch_rnvp_fwd(*this, params, grid, n_images, xd, train, s, false, packed); }
+    void gradients(hipStream_t s) {
+        launch_rnvp_bwd(*this, params, grid, n_images, s);
+        launch_rnvp_grads(*this, n_images, params, grads, s);
+    }
+    template <class B>
+    void update(B& b, bool fit, hipStream_t s) {
+        // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
+        const UpdArgs& u = b.u;
+        RnvpUpdArgs ru = make_rnvp_upd_args(*this, n_images, 0, params, opt_state, nullptr, &u.opt, wd, u.t, b.hdr(), b.opt_stride(),
+                                            b.status());
+        ru.gscale = u.gscale;
+        if (fit) ru.RE = RE;   // the next step's forward reuses it (`packed`)
+        if constexpr (B::fused) {
+            if (upd_union_ok(b.e->img.sl_cols, rm.F + 1)) {
+                launch_rnvp_bwd(*this, params, grid, n_images, s);
+                launch_pcn_update(b.e, *this, u, ru, n_images, s);   // (the ICNN half writes `status`: the RealNVP half gets none)
+                return;
+            }
+            launch_icnn_update(b.e, u, s);
+        }
+        launch_rnvp_bwd(*this, params, grid, n_images, s);
+        launch_rnvp_update_args(*this, n_images, ru, s);
+    }
+};
+
+// whether F::update runs the backbone's optimizer step too (else the skeletons call b.update in the unit loop)
+template <class B, class F>
+constexpr bool update_merged = B::fused && !F::none;
+
+template <class B, class F>
+int device_ready(B& b, F& f) {
+    const int rc = f.device();
+    return rc ? rc : b.device();
+}
+
+// the optimizer and loss rules of the fits (a fit evaluates its own loss: no INR_LOSS_EXTERNAL)
+static int check_fit(const InrOptDesc* opt, const InrLossDesc* loss, bool adam_only) {
+    if (opt->kind != INR_OPT_ADAM && (adam_only || opt->kind != INR_OPT_ADAMAX)) return INR_EINVAL;
+    if (const int rc = check_loss(loss)) return rc;
+    return loss->kind == INR_LOSS_EXTERNAL ? INR_EINVAL : INR_OK;
+}
+
+template <class B, class F>
+int forward_run(B b, F f, const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
+                void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    int rc = f.check(b, model, grid, n_images, workspace, workspace_bytes, false);
+    if (rc || (rc = device_ready(b, f))) return rc;
+    f.begin(s);
+    f.forward(false, false, s);
+    if ((rc = b.pack(params, s))) return rc;
+    return b.infer(params, logits, s);
+}
+
+// loss + gradients of every image (loss->kind may be INR_LOSS_EXTERNAL: `targets` = dL/dlogits, and on the plain layer-by-layer path
+// loss_out may be null); dcoords: NoDeform only, dL/dcoords as well (inrfit_backward)
+template <class B, class F>
+int loss_grad_run(B b, F f, const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* targets,
+                  const InrLossDesc* loss, int n_images, float* loss_out, float* grads, void* workspace, int64_t workspace_bytes,
+                  hipStream_t s, float* dcoords = nullptr) {
+    int rc = f.check(b, model, grid, n_images, workspace, workspace_bytes, false);
+    if (rc || (rc = b.loss_ok(loss)) || (rc = device_ready(b, f))) return rc;
+    f.begin(s);
+    f.forward(true, false, s);
+    if (b.coef_for(loss->kind)) hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, b.tstride(), *loss, b.coef(), 1.f);
+    if ((rc = b.pack(params, s))) return rc;
+    TrainPass a{targets, loss->kind};
+    a.dxd = F::none ? dcoords : f.dxd;
+    for (int k = 0; k < b.units(); ++k)
+        if ((rc = b.train(k, params, a, s)) || (rc = b.grads_out(k, grads, loss_out, s))) return rc;
+    f.gradients(s);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
-// One optimizer step: RealNVP forward (all images) | per image: wide_forward, dL/dlogits, wide_backward with dcoords = dxd,
-// icnn_update_kernel on the one-slab view (it writes the next learning rate and the "frozen" flag into the image's header) |
-// the RealNVP's backward seeded from dxd | its update, which reads this step's learning rate and the flag from the ICNN headers.
-static int pcn_wide_fit(const InrModelDesc* model, const InrRnvpDesc* r, float* ip, float* fp, float* iopt, float* fopt,
-                        const InrGridDesc* grid, const float* targets, const InrLossDesc* loss, const InrOptDesc* opt, float wd_flow,
-                        int n_images, int steps, int step0, float* loss_hist, float* final_logits, int32_t* status, void* workspace,
-                        int64_t workspace_bytes, hipStream_t s) {
-    PcnWideWs q;
-    int rc = check_pcn_wide(model, r, grid, n_images, workspace, workspace_bytes, &q);
-    if (rc || (rc = rnvp_set_lds())) return rc;
-    const WideMap& m = q.m;
-    const long long N = grid->n_points;
-    const long long ost = 2 * (long long)m.P + INR_OPT_HEADER_FLOATS;
-    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, N, *loss, q.coef, 1.f);
-    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, iopt, m.P, *opt, step0);
+// One optimizer step: the deformation's forward (all images) | per unit: the training pass, then (unless F::update owns it) the ICNN's
+// update | the deformation's backward seeded from dxd and its update.
+template <class B, class F>
+int fit_run(B b, F f, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
+            const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist, float* final_logits,
+            int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    int rc = f.check(b, model, grid, n_images, workspace, workspace_bytes, false);
+    if (rc || (rc = b.loss_ok(loss)) || (rc = device_ready(b, f))) return rc;
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, b.tstride(), *loss, b.coef(), 1.f);
+    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(64), 0, s, opt_state, b.P(), *opt, step0);
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
-    UpdArgs u = wide_upd_args(m, q.w.grads, opt, steps);
+    if ((rc = b.pack(params, s))) return rc;
+    f.begin(s);
+    b.begin_updates(params, opt_state, loss_hist, status, opt, steps);
+    // bench.py's timing hooks bracket the plain fused fit's launches only: events elsewhere would change what is launched and measured
+    if constexpr (B::fused && F::none) b.timed = true;
+    // opt->logits_at_last_forward: final_logits = the output of the LAST training forward (parameters before the last optimizer
+    // step) - what the reference's IoU gate looks at (path_connected_net.py:939-972) - written by that step's pass itself
     const bool gate_logits = final_logits && opt->logits_at_last_forward && steps > 0;
+    TrainPass a{targets, loss->kind};
+    a.dxd = f.dxd;
+    a.freeze_input = opt->freeze_input;
     for (int it = 0; it < steps; ++it) {
-        set_step_consts(u, opt, step0 + it + 1, it);
-        launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, true, s, false, it > 0);   // (it > 0: the update refreshed the packed image)
-        for (int img = 0; img < n_images; ++img) {
-            float* p = ip + (size_t)img * m.P;
-            if ((rc = pcn_wide_image(q, model, p, img, targets + (size_t)img * N, loss->kind, q.logit, nullptr, s))) return rc;
-            if (gate_logits && it == steps - 1 &&
-                hipMemcpyAsync(final_logits + (size_t)img * N, q.logit, sizeof(float) * N, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                return INR_ELAUNCH;
-            u.params = p;
-            u.opt_state = iopt + (size_t)img * ost;
-            u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps : nullptr;
-            u.status = status ? status + img : nullptr;
-            launch_wide_update(m, u, s);
+        b.set_step(step0 + it, opt, step0 + it + 1, it);
+        a.logits = gate_logits && it == steps - 1 ? final_logits : nullptr;
+        f.forward(true, it > 0, s);
+        for (int k = 0; k < b.units(); ++k) {
+            if ((rc = b.train(k, params, a, s))) return rc;
+            if constexpr (!update_merged<B, F>)
+                if ((rc = b.update(k, s))) return rc;
         }
-        launch_rnvp_bwd(q.p, fp, grid, n_images, s);
-        RnvpUpdArgs ru = make_rnvp_upd_args(q.p, n_images, 0, fp, fopt, nullptr, opt, wd_flow, u.t, iopt + 2 * (size_t)m.P, ost, status);
-        ru.RE = q.p.RE;   // the next step's forward reuses it
-        launch_rnvp_update_args(q.p, n_images, ru, s);
+        f.update(b, true, s);
     }
     if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
     if (final_logits && !gate_logits) {
-        launch_rnvp_fwd(q.p, fp, grid, n_images, q.p.xd, false, s);
-        for (int img = 0; img < n_images; ++img)
-            if ((rc = wide_forward(m, q.w, model, ip + (size_t)img * m.P, &q.p.dgrid, img, nullptr, 0, false, final_logits + (size_t)img * N, s)))
-                return rc;
+        f.forward(false, false, s);
+        return b.infer(params, final_logits, s);
     }
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    return INR_OK;
 }
 
-// ---- the fused joint step on the layer-by-layer path: joint_begin | (RealNVP forward) | wide_forward with the joint data term
-// (its loss column = the prior's whole share, with the UNCLIPPED coefficient) | wide_backward (-> dxd) | the finish kernel
-// (gscale) | icnn_update_kernel on the one-slab view x gscale | (RealNVP backward seeded from dxd, its update x gscale: this step's
-// learning rate and the frozen flag from the ICNN header) | d loss / d seg.  Nothing is read on the host.
-// A frozen step hands the backbone a zero gradient: d loss / d seg of a non-finite loss has no meaning, and the kernels that write it
-// (joint_loss_grad_kernel<true>, joint_prior_dseg_kernel) do not look at the status.  gscale is the finish kernel's: NaN = frozen.
+// A frozen step hands a layer-by-layer backbone's caller a zero gradient: d loss / d seg of a non-finite loss has no meaning, and the
+// kernels that write it (joint_loss_grad_kernel<true>, joint_prior_dseg_kernel) do not look at the status.  gscale is the finish
+// kernel's: NaN = frozen.  (The fused joint steps do not launch it.)
 __global__ __launch_bounds__(256) void joint_dseg_gate_kernel(const float* __restrict__ gscale, long long N, float* __restrict__ dseg) {
     if (isfinite(gscale[0])) return;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long long)gridDim.x * 256) dseg[e] = 0.f;
@@ -2782,97 +2739,50 @@ static void joint_dseg_gate(const float* gscale, long long N, float* dseg, int b
     hipLaunchKernelGGL(joint_dseg_gate_kernel, dim3(blocks), dim3(256), 0, s, gscale, N, dseg);
 }
 
-static WideJoint wide_joint_of(const JointCtx& c, long long N) {
-    WideJoint j{};
-    j.seg = c.align_seg;   // AWESOME_IMAGE with the extra penalty: hard align over every point
-    j.c_align = c.c_align;
-    j.data_count = N;
-    return j;
-}
-
-// the ICNN update of a joint step on the one-slab view (joint_upd_args)
-static UpdArgs wide_joint_upd_args(const WideMap& m, const float* grads, float* params, float* opt_state, int32_t* status,
-                                   const InrOptDesc* opt, int step, const float* gscale) {
+// the ICNN update of a joint step: one optimizer step per call, so no plateau scheduler; the reduced gradient is scaled by the finish
+// kernel's `gscale`
+template <class B>
+void joint_begin_update(B& b, float* params, float* opt_state, int32_t* status, const InrOptDesc* opt, int step, const float* gscale) {
     InrOptDesc o = *opt;
     o.plateau = 0;
-    UpdArgs u = wide_upd_args(m, grads, &o, 1);
-    u.params = params;
-    u.opt_state = opt_state;
-    u.status = status;
-    u.gscale = gscale;
-    set_step_consts(u, &o, step);
-    return u;
+    b.begin_updates(params, opt_state, nullptr, status, &o, 1);
+    b.u.gscale = gscale;
+    b.set_step(step, &o, step, 0);
 }
 
-// shape, grid and workspace of inrfit_wide_joint_step / inrfit_wide_joint_prior_step: the layer-by-layer workspace of one image, then
-// the joint step's (joint_ws_bytes) at *jws
-static int wide_joint_prepare(const InrModelDesc* model, const InrGridDesc* grid, void* workspace, int64_t workspace_bytes, WideMap* m,
-                              WideWs* w, float** jws) {
-    if (!pcn_wide_shape(model)) return INR_EUNSUPPORTED;
-    float* coef;
-    if (const int rc = wide_prepare(model, grid, 1, workspace, workspace_bytes, m, w, &coef, nullptr)) return rc;
-    const long long wb = align256(wide_total_bytes(*m, grid->n_points, false, 1));
-    if (workspace_bytes < wb + joint_ws_bytes(grid->n_points)) return INR_EWORKSPACE;
-    w->coef = coef;
-    *jws = (float*)((char*)workspace + wb);
-    return INR_OK;
-}
-
-static int wide_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
-                           const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
-                           float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    WideMap m;
-    WideWs w;
-    float* jws;
-    int rc = wide_joint_prepare(model, grid, workspace, workspace_bytes, &m, &w, &jws);
+// The fused joint step: joint_begin | the deformation's forward | the training pass with the joint data term (its loss column = the
+// prior's whole share, with the UNCLIPPED coefficient; dxd unscaled) | the finish kernel (gscale), in front of both updates: they read
+// it | the ICNN's update x gscale | the deformation's backward seeded from dxd and its update x gscale | d loss / d seg.  Nothing is
+// read on the host.
+template <class B, class F>
+int joint_step_run(B b, F f, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                   const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out, float* dseg,
+                   float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    int rc = f.check(b, model, grid, 1, workspace, workspace_bytes, true);
     if (rc) return rc;
     const long long N = grid->n_points;
+    if (workspace_bytes < align256(f.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
+    if ((rc = check_joint_step(desc, opt, step)) || (rc = device_ready(b, f))) return rc;   // (every argument first, then the device)
+    float* jws = (float*)((char*)workspace + align256(f.bytes));
     float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
     JointCtx c;
-    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, opt_state + 2 * (size_t)m.P, w.coef, s, &c))) return rc;
+    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, opt_state + 2 * (size_t)b.P(), b.coef(), s, &c))) return rc;
     if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    const WideJoint jn = wide_joint_of(c, N);
-    if ((rc = wide_forward(m, w, model, params, grid, 0, c.prior_targets, c.prior_loss.kind, true, logits, s, &jn))) return rc;
-    if ((rc = wide_backward(m, w, model, params, N, s))) return rc;
-    const UpdArgs u = wide_joint_upd_args(m, w.grads, params, opt_state, status, opt, step, c.gscale);
-    joint_finish(c, w.grads, 1, u.PS, m.P, loss_out, s);
-    launch_wide_update(m, u, s);
+    if ((rc = b.pack(params, s))) return rc;
+    joint_begin_update(b, params, opt_state, status, opt, step, c.gscale);
+    f.begin(s);
+    f.forward(true, false, s);
+    TrainPass a{c.prior_targets, c.prior_loss.kind};
+    a.logits = logits;
+    a.dxd = f.dxd;
+    a.term = &c.term;
+    if ((rc = b.train(0, params, a, s))) return rc;
+    joint_finish(c, b.loss_column(), loss_out, s);
+    if constexpr (!update_merged<B, F>)
+        if ((rc = b.update(0, s))) return rc;   // (layer by layer: writes the frozen flag of this step into the header)
+    f.update(b, false, s);
     joint_dseg(c, dseg, s);
-    joint_dseg_gate(c.gscale, N, dseg, c.jl.blocks, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
-}
-
-static int pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* r, float* ip, float* fp, float* iopt, float* fopt,
-                               const InrGridDesc* grid, const float* seg, const float* target, const InrJointLossDesc* desc,
-                               const InrOptDesc* opt, float wd_flow, int step, float* loss_out, float* dseg, float* prior_logits,
-                               int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    PcnWideWs q;
-    int rc = check_pcn_wide(model, r, grid, 1, workspace, workspace_bytes, &q);
-    if (rc) return rc;
-    const WideMap& m = q.m;
-    const long long N = grid->n_points;
-    if (workspace_bytes < align256(q.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
-    if ((rc = check_joint_step(desc, opt, step))) return rc;
-    if ((rc = rnvp_set_lds())) return rc;   // (every argument first, then the device)
-    float* jws = (float*)((char*)workspace + align256(q.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    float* hdr = iopt + 2 * (size_t)m.P;
-    JointCtx c;
-    if ((rc = joint_begin(desc, opt, seg, target, N, step, logits, jws, hdr, q.coef, s, &c))) return rc;
-    if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return INR_ELAUNCH;
-    launch_rnvp_fwd(q.p, fp, grid, 1, q.p.xd, true, s);
-    const WideJoint jn = wide_joint_of(c, N);
-    if ((rc = pcn_wide_image(q, model, ip, 0, c.prior_targets, c.prior_loss.kind, logits, &jn, s))) return rc;   // (dxd: unscaled)
-    const UpdArgs u = wide_joint_upd_args(m, q.w.grads, ip, iopt, status, opt, step, c.gscale);
-    joint_finish(c, q.w.grads, 1, u.PS, m.P, loss_out, s);   // in front of both updates: they read gscale
-    launch_wide_update(m, u, s);                             // (writes the frozen flag of this step into the header)
-    launch_rnvp_bwd(q.p, fp, grid, 1, s);
-    RnvpUpdArgs ru = make_rnvp_upd_args(q.p, 1, 0, fp, fopt, nullptr, &u.opt, wd_flow, step, hdr,
-                                        2 * (long long)m.P + INR_OPT_HEADER_FLOATS, status);
-    ru.gscale = c.gscale;
-    launch_rnvp_update_args(q.p, 1, ru, s);
-    joint_dseg(c, dseg, s);
-    joint_dseg_gate(c.gscale, N, dseg, c.jl.blocks, s);
+    if constexpr (!B::fused) joint_dseg_gate(c.gscale, N, dseg, c.jl.blocks, s);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
@@ -2889,15 +2799,15 @@ int64_t inrfit_wide_joint_step_workspace_bytes(const InrModelDesc* model, const 
 int64_t inrfit_pcn_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrRnvpDesc* rnvp, const InrGridDesc* grid) {
     if (!rnvp_ok(rnvp) || !pcn_wide_shape(model)) return INR_EUNSUPPORTED;
     if (!grid || grid->n_points <= 0) return INR_EINVAL;
-    return align256(pcn_wide_bytes(model, rnvp, grid, 1)) + joint_ws_bytes(grid->n_points);
+    return align256(inrfit_pcn_workspace_bytes(model, rnvp, grid, 1)) + joint_ws_bytes(grid->n_points);
 }
 
 int inrfit_wide_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
                            const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
                            float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!params || !opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    return wide_joint_step(model, params, opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace,
-                           workspace_bytes, (hipStream_t)stream);
+    return joint_step_run(WideIcnn(), NoDeform(), model, params, opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits,
+                          status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
@@ -2906,23 +2816,24 @@ int inrfit_pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnv
                                int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                                int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    return pcn_wide_joint_step(model, rnvp, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc, opt,
-                               flow_weight_decay, step, loss_out, dseg, prior_logits, status, workspace, workspace_bytes,
-                               (hipStream_t)stream);
+    return joint_step_run(WideIcnn(), RnvpDeform(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params,
+                          icnn_opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace,
+                          workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_forward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
                    void* workspace, int64_t workspace_bytes, void* stream) {
     if (!params || !logits) return INR_EINVAL;
-    if (use_wide(model)) return wide_forward_all(model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
-    return forward_run(IcnnOnly(), model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
+    if (use_wide(model))
+        return forward_run(WideIcnn(), NoDeform(), model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
+    return forward_run(FusedIcnn(), NoDeform(), model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_cdn_forward(const InrModelDesc* model, const InrFlowDesc* flow, const float* icnn_params, const float* flow_params,
                        const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
                        void* stream) {
     if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
-    return forward_run(CdnStep(flow, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
+    return forward_run(FusedIcnn(), FlowDeform(flow, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
                        (hipStream_t)stream);
 }
 
@@ -2931,8 +2842,9 @@ int inrfit_pcn_forward(const InrModelDesc* model, const InrRnvpDesc* rnvp, const
                        void* stream) {
     if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
     if (pcn_wide_shape(model))
-        return pcn_wide_forward(model, rnvp, icnn_params, flow_params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
-    return forward_run(PcnStep(rnvp, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
+        return forward_run(WideIcnn(), RnvpDeform(rnvp, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+    return forward_run(FusedIcnn(), RnvpDeform(rnvp, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
                        (hipStream_t)stream);
 }
 
@@ -2942,9 +2854,29 @@ int inrfit_loss_grad(const InrModelDesc* model, const float* params, const InrGr
     if (!params || !targets || !loss_out || !grads) return INR_EINVAL;
     if (const int rc = check_loss(loss)) return rc;
     if (use_wide(model))
-        return wide_loss_grad_all(model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes, (hipStream_t)stream);
-    return loss_grad_run(IcnnOnly(), model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes,
+        return loss_grad_run(WideIcnn(), NoDeform(), model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes,
+                             (hipStream_t)stream);
+    return loss_grad_run(FusedIcnn(), NoDeform(), model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes,
                          (hipStream_t)stream);
+}
+
+int inrfit_backward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, const float* dlogits,
+                    int n_images, float* grads, float* dcoords, void* workspace, int64_t workspace_bytes, void* stream) {
+    const KernelEntry* e;
+    Workspace w;
+    if (!params || !dlogits || !grads) return INR_EINVAL;
+    if (use_wide(model)) {
+        const InrLossDesc ext{INR_LOSS_EXTERNAL, INR_WEIGHT_NONE, 1.f, 0.f, 0.f};
+        return loss_grad_run(WideIcnn(), NoDeform(), model, params, grid, dlogits, &ext, n_images, nullptr, grads, workspace, workspace_bytes,
+                             (hipStream_t)stream, dcoords);
+    }
+    int rc = prepare(model, grid, n_images, workspace, workspace_bytes, &e, &w);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_pack(e, w, params, n_images, s))) return rc;
+    if ((rc = launch_step(e, w, true, grid, dlogits, INR_LOSS_EXTERNAL, n_images, nullptr, s, dcoords))) return rc;
+    launch_reduce(e, w, n_images, grads, w.coef /* scratch: the loss slot is unused in this mode */, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
 int inrfit_cdn_loss_grad(const InrModelDesc* model, const InrFlowDesc* flow, const float* icnn_params,
@@ -2953,8 +2885,8 @@ int inrfit_cdn_loss_grad(const InrModelDesc* model, const InrFlowDesc* flow, con
                          int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
     if (const int rc = check_loss(loss)) return rc;
-    return loss_grad_run(CdnStep(flow, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images, loss_out,
-                         icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
+    return loss_grad_run(FusedIcnn(), FlowDeform(flow, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images,
+                         loss_out, icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params,
@@ -2963,11 +2895,12 @@ int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, con
                          int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
     if (const int rc = check_loss(loss)) return rc;
+    const RnvpDeform f(rnvp, flow_params, nullptr, flow_grads);
     if (pcn_wide_shape(model))
-        return pcn_wide_loss_grad(model, rnvp, icnn_params, flow_params, grid, targets, loss, n_images, loss_out, icnn_grads, flow_grads,
-                                  workspace, workspace_bytes, (hipStream_t)stream);
-    return loss_grad_run(PcnStep(rnvp, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images, loss_out,
-                         icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
+        return loss_grad_run(WideIcnn(), f, model, icnn_params, grid, targets, loss, n_images, loss_out, icnn_grads, workspace,
+                             workspace_bytes, (hipStream_t)stream);
+    return loss_grad_run(FusedIcnn(), f, model, icnn_params, grid, targets, loss, n_images, loss_out, icnn_grads, workspace,
+                         workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_fit(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
@@ -2976,10 +2909,10 @@ int inrfit_fit(const InrModelDesc* model, float* params, float* opt_state, const
     if (!params || !opt_state || !targets || !opt || steps < 0 || step0 < 0) return INR_EINVAL;
     if (const int rc = check_fit(opt, loss, false)) return rc;
     if (use_wide(model))
-        return wide_fit(model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status,
-                        workspace, workspace_bytes, (hipStream_t)stream);
-    return fit_run(IcnnOnly(), model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status,
-                   workspace, workspace_bytes, (hipStream_t)stream);
+        return fit_run(WideIcnn(), NoDeform(), model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist,
+                       final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
+    return fit_run(FusedIcnn(), NoDeform(), model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist,
+                   final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_cdn_fit(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
@@ -2990,8 +2923,9 @@ int inrfit_cdn_fit(const InrModelDesc* model, const InrFlowDesc* flow, float* ic
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
         return INR_EINVAL;
     if (const int rc = check_fit(opt, loss, true)) return rc;   // the flow's optimizer step is Adam's only
-    return fit_run(CdnStep(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params, icnn_opt_state, grid, targets,
-                   loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
+    return fit_run(FusedIcnn(), FlowDeform(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params, icnn_opt_state,
+                   grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
+                   (hipStream_t)stream);
 }
 
 int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
@@ -3002,21 +2936,20 @@ int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* ic
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
         return INR_EINVAL;
     if (const int rc = check_fit(opt, loss, false)) return rc;
+    const RnvpDeform f(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay);
     if (pcn_wide_shape(model))
-        return pcn_wide_fit(model, rnvp, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, targets, loss, opt,
-                            flow_weight_decay, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
-                            (hipStream_t)stream);
-    return fit_run(PcnStep(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params, icnn_opt_state, grid,
-                   targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
-                   (hipStream_t)stream);
+        return fit_run(WideIcnn(), f, model, icnn_params, icnn_opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist,
+                       final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
+    return fit_run(FusedIcnn(), f, model, icnn_params, icnn_opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist,
+                   final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
                       const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
                       float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!params || !opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    return joint_step_run(IcnnOnly(), model, params, opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status,
-                          workspace, workspace_bytes, (hipStream_t)stream);
+    return joint_step_run(FusedIcnn(), NoDeform(), model, params, opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits,
+                          status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_pcn_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
@@ -3025,9 +2958,9 @@ int inrfit_pcn_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnvp, fl
                           int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                           int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
-    return joint_step_run(PcnStep(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params, icnn_opt_state, grid,
-                          seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace, workspace_bytes,
-                          (hipStream_t)stream);
+    return joint_step_run(FusedIcnn(), RnvpDeform(rnvp, flow_params, flow_opt_state, nullptr, flow_weight_decay), model, icnn_params,
+                          icnn_opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace,
+                          workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
@@ -3037,9 +2970,9 @@ int inrfit_cdn_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, fl
                           int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
     if (!opt || opt->kind != INR_OPT_ADAM) return INR_EINVAL;   // the flow's optimizer step is Adam's only (checked before the model)
-    return joint_step_run(CdnStep(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params, icnn_opt_state, grid,
-                          seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace, workspace_bytes,
-                          (hipStream_t)stream);
+    return joint_step_run(FusedIcnn(), FlowDeform(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params,
+                          icnn_opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace,
+                          workspace_bytes, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -3179,8 +3112,8 @@ static int joint_prior_begin(const InrJointPriorDesc* desc, const PriorRanges& r
 // behind the prior's pass: loss_out[1] and [2] on their own, then the finish kernel (gscale) on the pass's loss column; -> the blocks
 // of the point-wise launches
 static int joint_prior_finish(const InrJointPriorDesc* desc, const PriorRanges& r, const float* logits, const float* seg, const float* target,
-                              const float* coef, long long N, float* jws, const float* slabs, int wgs, int PS, int loss_col,
-                              const float* seg_term, float* gscale, float* loss_out, hipStream_t s) {
+                              const float* coef, long long N, float* jws, const LossColumn& lc, const float* seg_term, float* gscale,
+                              float* loss_out, hipStream_t s) {
     PriorShareArgs pa{};
     pa.logits = logits;
     pa.seg = seg;
@@ -3200,10 +3133,10 @@ static int joint_prior_finish(const InrJointPriorDesc* desc, const PriorRanges& 
     PriorFinArgs f{};
     f.part = jws;
     f.blocks = pa.blocks;
-    f.slabs = slabs;
-    f.wgs = wgs;
-    f.PS = PS;
-    f.loss_col = loss_col;
+    f.slabs = lc.slabs;
+    f.wgs = lc.wgs;
+    f.PS = lc.PS;
+    f.loss_col = lc.col;
     f.seg_term = seg_term;
     f.n_align = (float)r.n_align;
     f.gscale = gscale;
@@ -3221,76 +3154,69 @@ static void joint_prior_dseg(const InrJointPriorDesc* desc, const PriorRanges& r
 
 }  // namespace
 
+}  // extern "C"
+
+namespace {
+
+// header, coefficients and status | the training pass with the masked data term and the align term | loss_out and gscale | the ICNN's
+// update x gscale | d loss / d seg (layer by layer: zeroed on a frozen step)
+template <class B>
+int joint_prior_step_run(B b, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
+                         const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt, int step,
+                         float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes,
+                         hipStream_t s) {
+    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
+    int rc = check_joint_prior(desc, opt, step);
+    if (rc) return rc;
+    // (a shape of the other backbone, or an encode shape: INR_EUNSUPPORTED)
+    if ((rc = b.check(model, grid, 1, workspace, workspace_bytes, true))) return rc;
+    const long long N = grid->n_points;
+    if (workspace_bytes < align256(b.bytes) + joint_ws_bytes(N)) return INR_EWORKSPACE;
+    PriorRanges r;
+    if ((rc = prior_ranges(desc, N, &r)) || (rc = b.device())) return rc;
+    float* jws = (float*)((char*)workspace + align256(b.bytes));
+    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
+    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
+    if ((rc = joint_prior_begin(desc, r, opt, step, target, opt_state + 2 * (size_t)b.P(), b.coef(), status, s))) return rc;
+    if ((rc = b.pack(params, s))) return rc;
+    joint_begin_update(b, params, opt_state, status, opt, step, gscale);
+    DataTerm t;
+    t.align_seg = r.align ? seg : nullptr;
+    t.c_align = r.align ? desc->beta / (float)r.n_align : 0.f;
+    t.data_count = r.data_count;
+    t.use_noneclass = desc->use_noneclass ? 1 : 0;
+    t.noneclass = desc->noneclass;
+    t.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
+    t.align_begin = r.align_begin;
+    TrainPass a{target, desc->kind};
+    a.logits = logits;
+    a.term = &t;
+    if ((rc = b.train(0, params, a, s))) return rc;
+    const int blocks = joint_prior_finish(desc, r, logits, seg, target, b.coef(), N, jws, b.loss_column(), seg_term, gscale, loss_out, s);
+    if ((rc = b.update(0, s))) return rc;
+    joint_prior_dseg(desc, r, blocks, logits, seg, N, dseg, s);
+    if constexpr (!B::fused) joint_dseg_gate(gscale, N, dseg, blocks, s);
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+}  // namespace
+
+extern "C" {
+
 int inrfit_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
                             const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
                             int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                             int64_t workspace_bytes, void* stream) {
-    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
-    int rc = check_joint_prior(desc, opt, step);
-    if (rc) return rc;
-    const KernelEntry* e;
-    Workspace w;
-    if ((rc = prepare(model, grid, 1, workspace, workspace_bytes, &e, &w))) return rc;   // no fused kernel for this shape: INR_EUNSUPPORTED
-    const long long N = grid->n_points;
-    PriorRanges r;
-    if ((rc = prior_ranges(desc, N, &r))) return rc;
-    if (workspace_bytes < inrfit_joint_step_workspace_bytes(model, grid)) return INR_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* jws = (float*)((char*)workspace + align256(w.bytes));
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
-    if ((rc = joint_prior_begin(desc, r, opt, step, target, opt_state + 2 * (size_t)w.Pu, w.coef, status, s))) return rc;
-    if ((rc = launch_pack(e, w, params, 1, s))) return rc;
-    w.set_step(step);
-    StepMask m;
-    m.data_count = r.data_count;
-    m.use_noneclass = desc->use_noneclass ? 1 : 0;
-    m.noneclass = desc->noneclass;
-    m.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
-    m.align_begin = r.align_begin;
-    if ((rc = launch_step(e, w, true, grid, target, desc->kind, 1, logits, s, nullptr, r.align ? seg : nullptr,
-                          r.align ? desc->beta / (float)r.n_align : 0.f, m))) return rc;
-    const int blocks = joint_prior_finish(desc, r, logits, seg, target, w.coef, N, jws, w.slabs, w.wgs, w.PS, e->img.sl_cols - 1, seg_term,
-                                          gscale, loss_out, s);
-    launch_icnn_update(e, joint_upd_args(e, w, params, opt_state, status, opt, step, gscale), s);
-    joint_prior_dseg(desc, r, blocks, logits, seg, N, dseg, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    return joint_prior_step_run(FusedIcnn(), model, params, opt_state, grid, seg, target, desc, seg_term, opt, step, loss_out, dseg,
+                                prior_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_wide_joint_prior_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
                                  const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
                                  int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
-    if (!params || !opt_state || !seg || !target || !dseg || !desc || !grid) return INR_EINVAL;
-    int rc = check_joint_prior(desc, opt, step);
-    if (rc) return rc;
-    WideMap m;
-    WideWs w;
-    float* jws;
-    if ((rc = wide_joint_prepare(model, grid, workspace, workspace_bytes, &m, &w, &jws))) return rc;   // a fused or an encode shape: INR_EUNSUPPORTED
-    const long long N = grid->n_points;
-    PriorRanges r;
-    if ((rc = prior_ranges(desc, N, &r))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    float* logits = prior_logits ? prior_logits : (float*)((char*)jws + align256(inrfit_joint_loss_workspace_bytes(N)));
-    float* gscale = jws + JL_MAX_BLOCKS * JL_PART + JL_RES;
-    if ((rc = joint_prior_begin(desc, r, opt, step, target, opt_state + 2 * (size_t)m.P, w.coef, status, s))) return rc;
-    WideJoint jn{};
-    jn.seg = r.align ? seg : nullptr;
-    jn.c_align = r.align ? desc->beta / (float)r.n_align : 0.f;
-    jn.data_count = r.data_count;
-    jn.align_begin = r.align_begin;
-    jn.use_noneclass = desc->use_noneclass ? 1 : 0;
-    jn.align_soft = desc->align_rule == INR_ALIGN_SOFT ? 1 : 0;
-    jn.noneclass = desc->noneclass;
-    if ((rc = wide_forward(m, w, model, params, grid, 0, target, desc->kind, true, logits, s, &jn))) return rc;
-    if ((rc = wide_backward(m, w, model, params, N, s))) return rc;
-    const UpdArgs u = wide_joint_upd_args(m, w.grads, params, opt_state, status, opt, step, gscale);
-    const int blocks = joint_prior_finish(desc, r, logits, seg, target, w.coef, N, jws, w.grads, 1, u.PS, m.P, seg_term, gscale, loss_out, s);
-    launch_wide_update(m, u, s);
-    joint_prior_dseg(desc, r, blocks, logits, seg, N, dseg, s);
-    joint_dseg_gate(gscale, N, dseg, blocks, s);
-    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+    return joint_prior_step_run(WideIcnn(), model, params, opt_state, grid, seg, target, desc, seg_term, opt, step, loss_out, dseg,
+                                prior_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -164,8 +164,8 @@ __global__ __launch_bounds__(256) void wide_layer0_kernel(InrGridDesc gd, int im
 //   dZ_L[p][j] = dy w_o[j] [z_L[p][j] > 0]  (the row is still in the cache);
 //   and the block's share of the output layer's gradients (dw_o | db_o | ds_o)[j] = sum_p dy[p] Z_L,ext[p][j], summed over the block's
 //   points in a fixed order -> part[block][hs_valid] (wide_reduce_kernel adds the blocks in order).
-// The data term of a joint step (the fused step kernels' StepArgs / StepMask, icnn_step.h): the first data_count points carry the
-// criterion against `target` (which holds data_count values; soft targets are FBMS's SE against seg with coefficient 1 / N), a
+// The data term of a joint step (as in the fused step kernels' StepArgs, icnn_step.h; the host fills both from one DataTerm): the
+// first data_count points carry the criterion against `target` (which holds data_count values; soft targets are FBMS's SE against seg with coefficient 1 / N), a
 // target equal to `noneclass` drops the point, and from align_begin on a second term c_align (p - ind)^2 is added with
 // ind = [seg > 0.5] (strict: a NaN in seg counts as 0) or seg itself (align_soft).  seg = null: no align term.
 struct WideJoint {
