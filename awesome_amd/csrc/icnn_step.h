@@ -330,6 +330,9 @@ __device__ __forceinline__ float sum_over_groups(float v) {  // the 4 lanes shar
 #ifndef INR_SLAB_NT
 #define INR_SLAB_NT 1   // the slab tiles are written once and read once by another kernel: non-temporal stores (A/B in DESIGN.md 6)
 #endif
+#ifndef INR_TILES_SPREAD
+#define INR_TILES_SPREAD 1   // 1: the dW tile stores behind the chunk loop go out piece by piece between the cross-lane sums that follow them (a wave issues in order: a burst of 18 KB per wave holds it until the chip has accepted all 17 MB, and the sums wait); 0: all of them in front of the sums (A/B in DESIGN.md 6)
+#endif
 #ifndef INR_MFMA_ORDER
 #define INR_MFMA_ORDER 1
 #endif
@@ -567,6 +570,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     const unsigned long long st_begin = st_prev;
     unsigned long long st_f0 = 0, st_fsum = 0;
     const unsigned long long rt_loop = __builtin_amdgcn_s_memrealtime();
+    unsigned long long st_store = 0;   // the last dW tile store has been issued
 #endif
     for (int chunk = wg; chunk < n_chunks; chunk += a.wgs) {
 #if INR_STAMPS
@@ -1055,28 +1059,18 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     if (TRAIN) {
         float* __restrict__ slab = a.slabs + ((size_t)img * a.wgs + wg) * a.PS;
         // ---- dW1ext tiles of this wave: one 16-byte store per lane and tile, in accumulator order (Cfg: gradient slab) --------
-        if (row_ok) {
-#pragma unroll
-            for (int j = 0; j < RPW; ++j) {
-#pragma unroll
-                for (int b = 0; b < KG; ++b) {
-                    bool used = true;   // the last column tile holds the leftover units and the ext inputs only: skip its padding
-                    if (b == KG - 1) {
-                        used = l15 < HR;
-#pragma unroll
-                        for (int e = 0; e < NEXT; ++e) used = used || (HM + l15 == G::ext_pos(e));
-                    }
-                    if (used) {
-                        f32x4* dst = (f32x4*)(slab + ((((wave * RPW + j) * KG + b) * 64 + lane) << 2));
-#if INR_SLAB_NT
-                        __builtin_nontemporal_store(dW[j][b], dst);
-#else
-                        *dst = dW[j][b];
-#endif
-                    }
-                }
-            }
+        // A wave issues in order, and its RPW KG tile stores (18 KB at h = 130; 17 MB over the chip, all waves at once) are accepted only as
+        // fast as the chip drains them: as one burst they hold the wave for ~4 k cycles while the ~1000 instructions of sums below wait
+        // behind them.  INR_TILES_SPREAD cuts those sums into UW units of work - the reduction of one dw_o tile counts as four columns of
+        // the leftover rows - and lets the tiles that fall to a unit leave behind it: the queue drains while the VALU adds.  (The store
+        // block is a file of its own, included once per place: as a lambda over dW it moves hipcc's allocation of the whole kernel.)
+        constexpr int NTILES = RPW * KG, UW = 4 * TM + HR * KG;
+#if !INR_TILES_SPREAD
+        {
+            constexpr int tile_from = 0, tile_to = NTILES;
+#include "icnn_step_tiles.h"
         }
+#endif
         // ---- everything that was summed per lane: reduce within the wave, then over the waves through LDS -------------
         constexpr int SC_DWO = 0;                    // [PT]            dw_o by position
         constexpr int SC_DWL = SC_DWO + PT;          // [HRA][PT]       leftover rows of dW1ext by column position
@@ -1087,12 +1081,19 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         static_assert(4 * WSTR <= SP * G::SA, "reduction scratch must fit stage A");
         float* const scr = stA + wave * WSTR;
 #pragma unroll
-        for (int t = 0; t < TM; ++t)
+        for (int t = 0; t < TM; ++t) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float v = sum_over_points(dwo[t][r]);
                 if (l15 == 0) scr[SC_DWO + 16 * t + 4 * g + r] = v;
             }
+#if INR_TILES_SPREAD
+            {
+                const int tile_from = 4 * t * NTILES / UW, tile_to = (4 * t + 4) * NTILES / UW;
+#include "icnn_step_tiles.h"
+            }
+#endif
+        }
 #pragma unroll
         for (int u = 0; u < HR; ++u) {
             const float v = sum_over_points(dwol[u]);  // lane group 0 only
@@ -1101,6 +1102,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             for (int b = 0; b < KG; ++b) {
                 const float w = sum_over_groups(dWl[u][b]);
                 if (g == 0) scr[SC_DWL + u * PT + 16 * b + l15] = w;
+#if INR_TILES_SPREAD
+                {
+                    const int tile_from = (4 * TM + u * KG + b) * NTILES / UW, tile_to = (4 * TM + u * KG + b + 1) * NTILES / UW;
+#include "icnn_step_tiles.h"
+                }
+#endif
             }
 #pragma unroll
             for (int e = 0; e < NEXT; ++e) {
@@ -1163,6 +1170,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         }
     }
 #if INR_STAMPS
+    unsigned long long st_wait = 0;   // everything has been issued
+    if (TRAIN) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_wait)::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
     if (TRAIN && (tid & 63) == 0 && blockIdx.x < 1024) {
         __builtin_amdgcn_s_waitcnt(0);   // this wave's slab stores have left
         const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
@@ -1181,6 +1194,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         g_stamps[10] = st_loop_end - st_begin;
         g_stamps[11] = t_end - st_loop_end;   // epilogue
         g_stamps[12] = st_fsum;               // forward k-groups 2..6 (5 x 33 MFMAs per chunk)
+        g_stamps[13] = t_end - st_store;      // last dW tile store issued -> this wave's stores acknowledged (the s_waitcnt(0) above)
+        g_stamps[14] = t_end - st_wait;       // ... of that inside the wait
     }
 #endif
 }
