@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle import inr_oracle as O  # noqa: E402  (checker only)
+from tests import trainer_reference as TR
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -521,58 +522,146 @@ def test_nan_in_seg_through_the_trainer_latches_the_failure(dev):
         tr.raise_if_failed()
 
 
-def _run_convexity(dev, fused, steps, hook, hip_share=False, nan=False, Hc=40, Wc=44):
-    """The trainer's `convexity` route over ConvexNextNet 136 x 1: AwesomeImageLossJoint (soft align: d(prior's share) / d seg goes back
-    to the backbone) on a CNNNet backbone, the extra-penalty hook firing at step `hook`.  fused: fused_convexity_losses +
-    fused_layer_by_layer (+ fused_segmentation with hip_share); else the autograd step.  Problem and criterion: tests/test_gpu_cnnseg.py's."""
-    from awesome_amd.agent import JointTrainer
-    from awesome_amd.model import WrapperModule
-    from awesome_amd.prior_bank import PriorBank, _ordered_parameters
+def _convexity_problem(Hc, Wc, nan=False):
+    """-> (the CNNNet backbone, the prior's factory, the two items), all on the CPU.  Problem: tests/test_gpu_cnnseg.py's."""
     from tests import test_gpu_cnnseg as TC
     net = TC._net(2, seed=7)
-    torch.manual_seed(11)
-    factory = _icnn_factory(136, 1)
-    wrapper = WrapperModule(net, factory(), use_segmentation_output_inversion=True).to(dev)
-    bank = PriorBank(lambda: factory().to(dev), n_images=2, device=dev)
-    for k in range(2):
-        bank.row(k)
     items = []
     for k in range(2):
         image, feat, t, _ = TC._problem(Hc, Wc, 2, 2.0, seed=20 + k)
         if nan and k == 0:
             image[0, 0, 3, 4] = float("nan")
-        xy = O.positional_grid(Wc, Hc)[None]
-        items.append(((image.to(dev).requires_grad_(True), feat.to(dev).requires_grad_(True), xy.to(dev)), t.to(dev)))
+        items.append(((image, feat, O.positional_grid(Wc, Hc)[None]), t))
+    return net, _icnn_factory(136, 1), items
+
+
+def _convexity_ref_args(steps, hook, Hc=40, Wc=44):
+    """_run_convexity's steps as TR.run takes them: the same seeded construction on the CPU - the wrapper's prior, the bank's probe,
+    then the two rows."""
+    from awesome_amd.prior_bank import PriorBank
+    from tests import test_gpu_cnnseg as TC
+    net, factory, items = _convexity_problem(Hc, Wc)
+    torch.manual_seed(11)
+    factory()
+    bank = PriorBank(factory, n_images=2, device="cpu")
+    rows0 = torch.stack([bank.row(k) for k in range(2)]).clone()
+    items = [((im.requires_grad_(True), ft.requires_grad_(True), xy), t) for (im, ft, xy), t in items]
+    return dict(net=net, prior_factory=factory, rows0=rows0, items=items, make_crit=lambda: TC._loss("joint", "xy"), hook=hook,
+                lr=1e-3, steps=steps)
+
+
+def _convexity_ref(steps, hook, Hc=40, Wc=44):
+    """The float64 reference of _run_convexity's steps (tests/trainer_reference.py), computed once per shape."""
+    return TR.reference(("convexity", steps, hook, Hc, Wc), lambda: _convexity_ref_args(steps, hook, Hc, Wc))
+
+
+def _run_convexity(dev, fused, steps, hook, hip_share=False, nan=False, Hc=40, Wc=44, force=None):
+    """The trainer's `convexity` route over ConvexNextNet 136 x 1: AwesomeImageLossJoint (soft align: d(prior's share) / d seg goes back
+    to the backbone) on a CNNNet backbone, the extra-penalty hook firing at step `hook`.  fused: fused_convexity_losses +
+    fused_layer_by_layer (+ fused_segmentation with hip_share); else the autograd step.
+    force: _convexity_ref of the same arguments - after every step the backbone's gradient is kept and its weights and Adam moments
+    are set to the reference's (TR.record_and_force); the prior's rows and moments run free."""
+    from awesome_amd.agent import JointTrainer
+    from awesome_amd.model import WrapperModule
+    from awesome_amd.prior_bank import PriorBank, _ordered_parameters
+    from tests import test_gpu_cnnseg as TC
+    net, factory, cpu_items = _convexity_problem(Hc, Wc, nan)
+    torch.manual_seed(11)
+    wrapper = WrapperModule(net, factory(), use_segmentation_output_inversion=True).to(dev)
+    bank = PriorBank(lambda: factory().to(dev), n_images=2, device=dev)
+    for k in range(2):
+        bank.row(k)
+    items = [((image.to(dev).requires_grad_(True), feat.to(dev).requires_grad_(True), xy.to(dev)), t.to(dev))
+             for (image, feat, xy), t in cpu_items]
     rows0 = bank.params.detach().cpu().clone()
+    assert force is None or torch.equal(rows0, force["rows0"])
     opt = torch.optim.Adam(list(net.parameters()) + list(_ordered_parameters(wrapper.prior_module)), lr=1e-3)
     crit = TC._loss("joint", "xy")
     tr = JointTrainer(wrapper, bank, crit, opt, fused=fused, fused_convexity_losses=True, fused_layer_by_layer=fused,
                       fused_segmentation=fused and hip_share)
-    losses, paths = [], []
+    losses, paths, rec = [], [], TR.new_record()
     for s in range(steps):
         crit.extra_penalty = s >= hook
         inputs, target = items[s % 2]
         loss, _ = tr.perform_step(s % 2, inputs, target)
         losses.append(float(loss))
         paths.append(tr._path)
-    return dict(losses=losses, paths=paths, rows=bank.params.detach().cpu().clone(), rows0=rows0, tr=tr, net=net,
+        if force is not None:
+            TR.record_and_force(rec, net, opt, force, s)
+    return dict(rec, losses=losses, paths=paths, rows=bank.params.detach().cpu().clone(), rows0=rows0, tr=tr, net=net,
                 seg_w=torch.cat([p.detach().reshape(-1) for p in net.parameters()]).cpu(), mom=_moments(tr, opt, wrapper.prior_module))
+
+
+B_GRAD = 6e-6
+
+
+def _assert_forced(r, ref, name, fused, hip_share=False):
+    """A forced _run_convexity against its float64 reference: the route it took, then TR.check_forced at B_GRAD.
+
+    B_GRAD = 6e-6 of each gradient tensor's max, per step: four times what the float32 torch autograd step shows against the same
+    reference on the MI355X (1.3e-6 at 40 x 44; on the CPU 6e-7), rounded up to one digit.  Measured there: fused with the torch share
+    1.3e-6, with the HIP share 6.0e-7; at 20 x 23 1.6e-6 and 1.4e-6 (profiles/NOTES.md).  Exact zeros where the
+    reference has them are asked of the HIP segmentation share only: torch's convolution backward on the GPU leaves about 1e-11 max|g|
+    in a few such entries (profiles/NOTES.md), which are held to B_GRAD like the rest."""
+    steps = len(ref["losses"])
+    if fused:
+        assert r["paths"] == ["fused"] * steps and r["tr"]._fused_plan["wide"]
+        assert (r["tr"].cnnseg_status is not None) == hip_share
+        assert int(r["tr"].last_status[0]) == 0
+    else:
+        assert r["paths"] == ["autograd"] * steps
+    assert not torch.equal(r["rows"], r["rows0"])
+    return TR.check_forced(r, ref, B_GRAD, name, zeros_exact=fused and hip_share)
 
 
 @pytest.mark.parametrize("hip_share", [False, True], ids=["torch_share", "hip_share"])
 def test_joint_trainer_convexity_route_with_the_switch_matches_autograd(dev, hip_share):
     """Six steps on two images, the hook firing at step 3: _perform_step_prior_share dispatches to inrfit_wide_joint_prior_step (with
-    the torch and with the HIP segmentation share), every step fused; losses, backbone weights (they see the soft align's dseg), rows
-    and moments match the autograd run.  Bars: this route's own, tests/test_gpu_joint_convexity.py::_assert_same."""
+    the torch and with the HIP segmentation share), every step fused.  Free-running, losses, rows and moments match the autograd run
+    (bars: this route's own, tests/test_gpu_joint_convexity.py::_assert_same).  The backbone (it sees the soft align's dseg) is judged
+    step by step instead: the same route with its backbone forced to the float64 reference after every step (_run_convexity(force=),
+    tests/trainer_reference.py), every step's gradient per parameter tensor against the reference's at B_GRAD.
+
+    The free-running backbone weights are no observable.  This test used to hold them to rtol 2e-4, atol 2e-6 against the autograd run
+    and failed on a correct build, always on 64 of 5521 weights (worst 6.5e-5).  The same six steps in plain torch on the CPU, no
+    kernel of this project involved: float32 against float64, the gradients differ by 4-6e-7 max|g| per tensor and 0 of 5521 final
+    weights are over those bars; +-3e-7 max|g| of noise on the float64 run's non-zero gradients puts 58 to 159 of 5521 over them,
+    depending on the draw (worst 1.4e-4 to 1.9e-4), 1e-6 puts 140 over and moves later gradients by 1e-4 max|g|, while the prior's
+    rows move by < 1e-8 and the losses by < 1e-7 relative.  Adam divides each weight's gradient by its own running magnitude, so a weight whose gradient sits at the noise
+    floor of its float32 sum moves by about +-lr per step whatever the noise is: no float32 producer of the gradient meets
+    element-wise bars on such weights, torch's own included (tests/test_trainer_reference_host.py pins this).  The forced check
+    resolves gradient errors a hundred times below the 1e-4 max|g| at which free-running runs already part by step 2.  It also
+    found the one place where these six steps are ill-posed for float32, and with it what made the old line fail: at step 4 one
+    ReLU pre-activation is 3e-9, torch's GPU convolutions and float64 (and inrfit_cnnseg_forward) put it on different sides of
+    zero, and the gradients below it move by up to 4e-3 of their max.  A float64 run that takes the other side at that step alone
+    ends with exactly the old failure, 64 of 5521 weights over the bars, worst 6.5e-5 (same host test).  The reference hands out
+    both sides there (TR.KINK_TOL)."""
     f = _run_convexity(dev, True, 6, 3, hip_share=hip_share)
     a = _run_convexity(dev, False, 6, 3)
     assert f["paths"] == ["fused"] * 6 and a["paths"] == ["autograd"] * 6 and f["tr"]._fused_plan["wide"]
     assert (f["tr"].cnnseg_status is not None) == hip_share
     np.testing.assert_allclose(f["losses"], a["losses"], rtol=2e-5, atol=1e-7)
-    np.testing.assert_allclose(f["seg_w"].numpy(), a["seg_w"].numpy(), rtol=2e-4, atol=2e-6)
     np.testing.assert_allclose(f["rows"].numpy(), a["rows"].numpy(), rtol=1e-3, atol=2e-5)
     np.testing.assert_allclose(f["mom"].numpy(), a["mom"].numpy(), rtol=1e-3, atol=2e-4 * float(a["mom"].abs().max()))
     assert not torch.equal(f["rows"], f["rows0"])
+    ref = _convexity_ref(6, 3)
+    _assert_forced(_run_convexity(dev, True, 6, 3, hip_share=hip_share, force=ref), ref, "hip share" if hip_share else "torch share",
+                   True, hip_share)
+
+
+def test_joint_trainer_convexity_autograd_route_matches_float64_step_by_step(dev):
+    """The autograd step of the same six steps (the prior through the HIP autograd bridges, the backbone through torch's convolutions)
+    is a subject like the fused routes, forced to the same float64 reference: its gradient ratio is the yardstick B_GRAD is set by."""
+    ref = _convexity_ref(6, 3)
+    _assert_forced(_run_convexity(dev, False, 6, 3, force=ref), ref, "autograd", False)
+
+
+@pytest.mark.parametrize("hip_share", [False, True], ids=["torch_share", "hip_share"])
+def test_joint_trainer_convexity_route_at_460_points_matches_float64_step_by_step(dev, hip_share):
+    """The forced check on the file's edge shape, 20 x 23: 460 points, a multiple of neither 16 nor the output pass's 128."""
+    ref = _convexity_ref(6, 3, H, W)
+    _assert_forced(_run_convexity(dev, True, 6, 3, hip_share=hip_share, Hc=H, Wc=W, force=ref), ref,
+                   "20x23 " + ("hip share" if hip_share else "torch share"), True, hip_share)
 
 
 def test_nan_with_the_hip_segmentation_share_zeroes_the_backbone_gradient(dev):
