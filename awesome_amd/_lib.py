@@ -88,6 +88,11 @@ class InrFcSegDesc(C.Structure):   # inrfit_fcseg_*: the convexity benchmark's F
                 ("inversion", C.c_int32), ("g", C.c_float), ("n_rows", C.c_int64), ("data_count", C.c_int64)]
 
 
+class InrUNetDesc(C.Structure):   # inrfit_unet_*: the UNet backbone's evaluation pass
+    _fields_ = [("in_chn", C.c_int32), ("out_chn", C.c_int32), ("base_width", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("strip_points", C.c_int32), ("bn_eps", C.c_float)]
+
+
 class InrStarDesc(C.Structure):
     _fields_ = [("n_hidden", C.c_int32)]
 
@@ -220,6 +225,11 @@ EXPORTS = {
     "inrfit_fcseg_step": (C.c_int, [C.POINTER(InrFcSegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_void_p]),
+    "inrfit_unet_packed_floats": (C.c_int64, [C.POINTER(InrUNetDesc)]),
+    "inrfit_unet_workspace_bytes": (C.c_int64, [C.POINTER(InrUNetDesc)]),
+    "inrfit_unet_pack": (C.c_int, [C.POINTER(InrUNetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "inrfit_unet_forward": (C.c_int, [C.POINTER(InrUNetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -31,6 +31,7 @@
 #include "star.h"
 #include "cnnseg.h"
 #include "fcseg.h"
+#include "unet.h"
 
 #include <type_traits>
 #include <vector>
@@ -3524,6 +3525,45 @@ int inrfit_fcseg_step(const InrFcSegDesc* desc, const float* const* weights, con
     FcReduceArgs r{w.slab, w.blocks, w.P + 1, w.P, desc->g, (float)w.count, grads, status, loss_out, w.loss};
     hipLaunchKernelGGL(fc_reduce_kernel, dim3(1), dim3(FC_REDUCE_BLOCK), 0, s, r);
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+}  // extern "C"
+
+// ---- the UNet backbone's evaluation pass (csrc/unet.h) ---------------------------------------------------------------------------------
+extern "C" {
+
+int64_t inrfit_unet_packed_floats(const InrUNetDesc* desc) {
+    const int rc = unet_desc_rc(desc);
+    return rc ? rc : unet_plan(desc).packed_floats;
+}
+
+int64_t inrfit_unet_workspace_bytes(const InrUNetDesc* desc) {
+    const int rc = unet_desc_rc(desc);
+    return rc ? rc : unet_plan(desc).bytes;
+}
+
+int inrfit_unet_pack(const InrUNetDesc* desc, const float* const* conv_w, const float* const* conv_b, const float* const* bn_gamma,
+                     const float* const* bn_beta, const float* const* bn_mean, const float* const* bn_var, float* packed, void* stream) {
+    if (!desc || !conv_w || !conv_b || !bn_gamma || !bn_beta || !bn_mean || !bn_var || !packed) return INR_EINVAL;
+    for (int i = 0; i < UNET_CONVS; ++i)
+        if (!conv_w[i] || !conv_b[i]) return INR_EINVAL;
+    for (int i = 0; i < UNET_CONVS - 1; ++i)
+        if (!bn_gamma[i] || !bn_beta[i] || !bn_mean[i] || !bn_var[i]) return INR_EINVAL;
+    if (((uintptr_t)packed) & 15) return INR_EINVAL;
+    const int rc = unet_desc_rc(desc);
+    if (rc) return rc;
+    return unet_pack(desc, unet_plan(desc), conv_w, conv_b, bn_gamma, bn_beta, bn_mean, bn_var, packed, (hipStream_t)stream);
+}
+
+int inrfit_unet_forward(const InrUNetDesc* desc, const float* packed, const float* input, float* logits, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    if (!desc || !packed || !input || !logits || !workspace) return INR_EINVAL;
+    if ((((uintptr_t)packed) | ((uintptr_t)workspace)) & 15) return INR_EINVAL;
+    const int rc = unet_desc_rc(desc);
+    if (rc) return rc;
+    const UNetPlan p = unet_plan(desc);
+    if (workspace_bytes < p.bytes) return INR_EWORKSPACE;
+    return unet_forward(desc, p, packed, input, logits, (float*)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -10,3 +10,4 @@ from .encoded_mlp import FourierFeatureNet, SineLayerNet  # noqa: F401,E402
 from .symmetric_net import RotationSymmetricNet, polar_symmetry_features  # noqa: F401,E402
 from .star_net import StarShapedNet  # noqa: F401,E402
 from .cnn_net import CNNNet, concat_input  # noqa: F401,E402
+from .unet import UNet  # noqa: F401,E402

@@ -45,6 +45,7 @@ ALIASES: Dict[str, str] = {
     "awesome.model.noisy_path_connected_net.NoisyPathConnectedNet": "awesome_amd.model.NoisyPathConnectedNet",
     "awesome.model.fc_net.FCNet": "awesome_amd.model.FCNet",
     "awesome.model.cnn_net.CNNNet": "awesome_amd.model.CNNNet",
+    "awesome.model.unet.UNet": "awesome_amd.model.UNet",
     "awesome.model.forward_module.ForwardModule": "awesome_amd.model.ForwardModule",
     "awesome.model.wrapper_module.WrapperModule": "awesome_amd.model.WrapperModule",
     "awesome.model.zoo.Zoo": "awesome_amd.model.Zoo",

@@ -625,6 +625,41 @@ int inrfit_fcseg_step(const InrFcSegDesc* desc, const float* const* weights, con
                       const float* feature_rows, const float* target, const float* dseg, int reuse_forward, float* logits, float* seg,
                       float* loss_out, float* grads, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the UNet segmentation backbone in evaluation mode (awesome/model/unet.py UNet, csrc/unet.h) ------------------------------------
+ * InConv, 4 x Down (2 x 2 max-pool + two 3 x 3 convolutions), 4 x Up (bilinear x2 upsampling with align_corners, zero-padded to the skip
+ * map's size and concatenated behind it, two 3 x 3 convolutions), OutConv (1 x 1); every 3 x 3 convolution is followed by a BatchNorm2d
+ * in evaluation mode (running statistics) and a ReLU.  Channel widths base_width (1, 2, 4, 8, 8) going down and base_width (4, 2, 1, 1)
+ * coming up (the reference: base_width 64).  fp32, one image per call, planar maps [channels][height * width].
+ * inrfit_unet_pack folds every convolution + BatchNorm pair into one matrix (done once per set of weights, on the device);
+ * inrfit_unet_forward runs the network from the packed weights: per convolution a gather kernel and a product of csrc/gemm.h, strip
+ * by strip over the pixels (strip_points pixels, rounded up to a multiple of 128; 0: the default of 2048).  Results do not depend on
+ * anything but the arguments: two calls give the same bits.
+ * Argument errors are answered before the first HIP call: null pointers (table entries included), height or width < 16, non-positive
+ * channel counts: INR_EINVAL; base_width not a multiple of 4 or above 64, out_chn above 8, in_chn above 1024, a side above 4096:
+ * INR_EUNSUPPORTED; workspace too small: INR_EWORKSPACE. */
+typedef struct InrUNetDesc {
+    int32_t in_chn;
+    int32_t out_chn;
+    int32_t base_width;
+    int32_t height;
+    int32_t width;
+    int32_t strip_points;   /* 0: default */
+    float bn_eps;
+} InrUNetDesc;
+
+/* floats of the packed weights / bytes of the workspace; negative: the error code of the descriptor */
+int64_t inrfit_unet_packed_floats(const InrUNetDesc* desc);
+int64_t inrfit_unet_workspace_bytes(const InrUNetDesc* desc);
+/* conv_w / conv_b: host arrays of 19 device pointers, the convolutions' torch tensors in state_dict order (inc.conv.conv.{0,3},
+ * down1..4.mpconv.1.conv.{0,3}, up1..4.conv.conv.{0,3}, outc.conv); bn_gamma / bn_beta / bn_mean / bn_var: host arrays of 18 device
+ * pointers, the BatchNorms behind the first 18 (weight, bias, running_mean, running_var).  packed: [inrfit_unet_packed_floats] device
+ * floats, 16-byte aligned.  The packed weights do not depend on height, width or strip_points. */
+int inrfit_unet_pack(const InrUNetDesc* desc, const float* const* conv_w, const float* const* conv_b, const float* const* bn_gamma,
+                     const float* const* bn_beta, const float* const* bn_mean, const float* const* bn_var, float* packed, void* stream);
+/* input [in_chn][height * width] -> logits [out_chn][height * width]; workspace 16-byte aligned.  No host sync. */
+int inrfit_unet_forward(const InrUNetDesc* desc, const float* packed, const float* input, float* logits, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 const char* inrfit_strerror(int code);
 
 #pragma GCC visibility pop

@@ -12,7 +12,8 @@ prior_model_type / prior_model_args (dotted type strings, resolved like awesome/
 `awesome.model.*` names map to the drop-in modules), agent_args.pretrain_args (criterion, num_epochs, lr, reuse_state, zoo ...),
 loss_type / loss_args, optimizer_type / optimizer_args, the extra-penalty hook fields, seed, device, output_folder; a reference
 YAML runs with `--dataset-type / --dataset-args / --segmentation-model-type` replacing what is not in the image.
-Everything else the reference runner does (tensorboard, plots, UNet joint training) is out of scope.
+`awesome.model.unet.UNet` maps to awesome_amd.model.UNet (its evaluation pass runs in HIP, training on torch) and takes the config's
+`segmentation_model_state_dict_path`.  Everything else the reference runner does (tensorboard, plots) is out of scope.
 """
 import argparse
 import importlib
@@ -58,6 +59,8 @@ def get_config(argv=None) -> AwesomeConfig:
         v = getattr(args, k)
         if v is not None:
             cfg[k] = v
+    if args.segmentation_model_type is not None:   # the config's checkpoint belongs to the backbone that was just replaced
+        cfg["segmentation_model_state_dict_path"] = None
     if args.num_epochs is not None:   # this entrypoint's shorthand: the flag also sets the per-image fit's epochs
         cfg.agent_args = dict(cfg.agent_args or {})
         cfg.agent_args["pretrain_args"] = dict(cfg.agent_args.get("pretrain_args") or {}, num_epochs=args.num_epochs)
@@ -304,6 +307,9 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
             first = ((mine[0], None), ds.pixel_item(mine[0])) if pixel_mode else ds[mine[0]]
             seg_args = segmentation_model_args(cfg, seg_args, first)
         seg = seg_type(**seg_args).to(device)
+        sd_path = cfg.get("segmentation_model_state_dict_path")     # awesome_runner.py: a trained backbone's checkpoint
+        if sd_path:
+            seg.load_state_dict(torch.load(sd_path, map_location=device, weights_only=True))
         prior = wrapper.prior_module
         if pixel_mode:       # awesome_runner.py:147-162: the 2d configs' wrapper reads pixel rows, the prior the clean coordinates
             jw = WrapperModule(seg, prior, use_segmentation_output_inversion=True, input_mode="pixel",
