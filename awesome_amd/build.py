@@ -19,17 +19,18 @@ def hipcc_path() -> str:
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm)")
 
 
-def needs_build() -> bool:
-    if not os.path.exists(OUT):
+def needs_build(out: str = OUT) -> bool:
+    if not os.path.exists(out):
         return True
     deps = [SRC, MAP, os.path.join(INCLUDE, "inrfit.h")] + [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps)
+    return any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    """Compile the HIP C-ABI library for gfx950.  Cross-compiles without a GPU."""
-    if not force and not needs_build():
-        return OUT
+def build(force: bool = False, verbose: bool = True, out: str = OUT, extra_flags=()) -> str:
+    """Compile the HIP C-ABI library for gfx950.  Cross-compiles without a GPU.  `out` / `extra_flags`: an A/B or stamps variant
+    (tools/build_variant.sh), compiled exactly like the library it is compared with."""
+    if not force and not needs_build(out):
+        return out
     # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf().  With the default (fast) contraction the
     #   compiler decides per build which a*b+c pairs it fuses, and that decision moved with an unrelated switch
     #   (-fno-slp-vectorize): same source, two roundings, and after 2000 chaotic optimizer steps masks 4 pixels apart
@@ -44,9 +45,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
     def command(flags):
         shown = " ".join(["-O3", "-ffp-contract=off"] + flags)
-        return base + flags + [f'-DINRFIT_BUILD_FLAGS="{shown}"', SRC, "-o", OUT]
+        return base + flags + [f'-DINRFIT_BUILD_FLAGS="{shown}"', SRC, "-o", out]
 
-    cmd = command(tuning)
+    cmd = command(tuning + list(extra_flags))
     if verbose:
         print("[awesome_amd.build]", " ".join(cmd), flush=True)
     if subprocess.run(cmd, stderr=subprocess.DEVNULL if not verbose else None).returncode != 0:
@@ -55,10 +56,13 @@ def build(force: bool = False, verbose: bool = True) -> str:
         # loud on purpose, and inrfit_build_info() / the bench line say which build is loaded.
         print("[awesome_amd.build] WARNING: compile with the tuning switches failed; building WITHOUT "
               + " ".join(tuning) + " (same results, ~1 % slower step kernel)", file=sys.stderr, flush=True)
-        subprocess.run(command([]), check=True)
-    return OUT
+        subprocess.run(command(list(extra_flags)), check=True)
+    return out
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
-    print(OUT)
+    # python -m awesome_amd.build [--force] [--out PATH] [-DFLAG=.. ...]
+    args = [a for a in sys.argv[1:] if a != "--force"]
+    out = os.path.abspath(args.pop(args.index("--out") + 1)) if "--out" in args else OUT
+    extra = [a for a in args if a != "--out"]
+    print(build(force="--force" in sys.argv or bool(extra), out=out, extra_flags=extra))

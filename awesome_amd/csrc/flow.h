@@ -148,7 +148,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 //   * mask-specialised bodies (no scratch, no select chains) and branch-free tanh / exp (~19 / 5 instructions; libm's are longer but
 //     skip whole branches when a wave agrees): the forward kernels did not move (55.7 vs 53.2 us at configs[3], 18.2 vs 18.3 at
 //     256x256) - and by SQ_INSTS_VALU the instruction count did not fall either (270 vs 246 per wave and flow);
-//   * the scalar data path (image read from HBM through a constant-address-space pointer -> s_load_dwordx4/x8 into SGPRs, RecK below;
+//   * the scalar data path (image read from HBM through a constant-address-space pointer -> s_load_dwordx4/x8 into SGPRs;
 //     no LDS traffic at all): 2-3x SLOWER (coupling-flow forward 64 vs 21.5 us): the scalar cache cannot feed the loop;
 //   * Q = 2 / 4 points per lane (a record read serves Q points; 64-thread blocks so the fewer waves still spread over all CUs):
 //     1.1-1.6x SLOWER, with and without the pipelining below: not LDS return bandwidth either;
@@ -157,23 +157,12 @@ __device__ __forceinline__ float fast_tanh(float x) {
 //     forward kernels +-1 us, configs[3] (4 waves per SIMD) unchanged.  KEPT.
 // What is left is the size of the problem: one 256x256 image is 1024 waves for 1024 SIMDs - ONE wave per SIMD, 66 clocks per hidden
 // unit for 16 clocks of VALU issue - and a fit step is a chain of such launches.
-typedef const float __attribute__((address_space(4))) kfloat;
-typedef const f32x4 __attribute__((address_space(4))) kf32x4;
-struct RecK {   // image in global memory, scalar loads
-    static constexpr bool SCALAR = true;
-    const kfloat* p;
-    __device__ __forceinline__ f32x4 v4(int off) const { return *(const kf32x4*)(p + off); }
-    __device__ __forceinline__ float f(int off) const { return p[off]; }
-    __device__ __forceinline__ RecK at(int off) const { return RecK{p + off}; }
-};
 struct RecL {   // image in LDS
-    static constexpr bool SCALAR = false;
     const float* p;
     __device__ __forceinline__ f32x4 v4(int off) const { return *(const f32x4*)(p + off); }
     __device__ __forceinline__ float f(int off) const { return p[off]; }
     __device__ __forceinline__ RecL at(int off) const { return RecL{p + off}; }
 };
-__device__ __forceinline__ RecK rec_global(const float* image) { return RecK{(const kfloat*)image}; }
 
 // Launch shape of the point kernels: U lanes per point, Q points per lane, 256 threads.  A launch with at least two waves per SIMD
 // runs at (1, 1): more points per lane were measured slower at every size (profiles/NOTES.md).  A small launch (one image of 256x256:
@@ -273,13 +262,7 @@ __device__ __forceinline__ void nb_pair_forward(const Rec e, int W, const float 
     auto unit = [&](const f32x4& lo, const f32x4& hi) {   // lo = (w1s, w1t, b1s, b1t), hi = (w2's, w2't, w1s w2's, w1t w2't)
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            f32x2 h;   // relu(pre) 2^-32 (pk_fma_clamp_bcast)
-            if constexpr (Rec::SCALAR) {   // (experiment path: one SGPR pair per instruction)
-                const f32x2 pre = f32x2{lo[0], lo[1]} * splat2(u[q]) + f32x2{lo[2], lo[3]};
-                h = f32x2{fminf(fmaxf(pre[0], 0.f), 1.f), fminf(fmaxf(pre[1], 0.f), 1.f)};
-            } else {
-                h = pk_fma_clamp_bcast(f32x2{lo[0], lo[1]}, u[q], f32x2{lo[2], lo[3]});
-            }
+            const f32x2 h = pk_fma_clamp_bcast(f32x2{lo[0], lo[1]}, u[q], f32x2{lo[2], lo[3]});   // relu(pre) 2^-32
             acc[q] = pk_fma(f32x2{hi[0], hi[1]}, h, acc[q]);
             if (DU) d[q] = pk_fma(f32x2{hi[2], hi[3]}, step01(h), d[q]);
         }

@@ -39,9 +39,7 @@
 
 namespace {
 
-#ifndef GM_WAVES
-#define GM_WAVES 4   // waves per SIMD the V4 kernels are compiled for (<= 128 VGPRs)
-#endif
+constexpr int GM_WAVES = 4;   // waves per SIMD the V4 kernels are compiled for (<= 128 VGPRs)
 constexpr int GM_BM = 128, GM_BN = 128, GM_BK = 16;
 constexpr int GM_LDK = 20;            // [row][k] layout: floats per row
 constexpr int GM_LDF = GM_BM + 4;     // [k][free] layout: floats per k-row
@@ -90,12 +88,6 @@ struct GemmArgs {
 //   operand contiguous along its free index, tile [16 k][128]: chunk h = k row tid >> 4, offset 4 (tid & 15) + 64 h  (16 lanes = 256 bytes)
 // (round 4 measured the k-loop of the three products at 73 / 84 / 72.5 us with 8 consecutive floats per thread - neighbouring lanes 32
 // bytes apart, in two instructions - against 62 - 63 us without any global load.)
-#if defined(GM_EXP) && (GM_EXP & 16)   // timing experiment: no LDS reads in the k-loop
-#define GM_LDS_READ(ptr, alt) (alt)
-#else
-#define GM_LDS_READ(ptr, alt) (*(const f32x4*)(ptr))
-#endif
-
 template <int V>
 __device__ __forceinline__ void gemm_load4(const float* __restrict__ base, int ld, int r, int rmax, int c, int cmax, f32x4& v) {
     const bool rok = r < rmax;
@@ -149,11 +141,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE ? GM_W
     const int m0 = by * GM_BM, n0 = bx * GM_BN;
     const int k_lo = bz * a.k_per_split;
     const int k_hi = min(a.K, k_lo + a.k_per_split);
-#if defined(GM_EXP) && (GM_EXP & 2)   // timing experiment: the epilogue alone
-    const int steps = 0;
-#else
     const int steps = (k_hi - k_lo + GM_BK - 1) / GM_BK;
-#endif
 
     // ---- global -> registers -> LDS: every thread owns two 16-byte chunks of each operand tile (gemm_load4) ----------------------------
     // flavours of the operands' interior k-steps (a contiguous-k operand's last, partial step may need another: see load_tiles)
@@ -189,12 +177,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE ? GM_W
                 ra[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, oa, 0, 0));
                 rb[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, ob, 0, 0));
             } else if (V4) {
-#if !(defined(GM_EXP) && (GM_EXP & 256))   // (timing experiment: the A tiles of the k-loop are not loaded)
                 gemm_load4<4>(a.A, a.lda, rA, rmaxA, cA, cmaxA, ra[h]);
-#endif
-#if !(defined(GM_EXP) && (GM_EXP & 512))   // (... the B tiles)
                 gemm_load4<4>(a.B, a.ldb, rB, rmaxB, cB, cmaxB, rb[h]);
-#endif
             } else {
                 gemm_load4_any(fa, a.A, a.lda, rA, rmaxA, cA, cmaxA, ra[h]);
                 gemm_load4_any(fb, a.B, a.ldb, rB, rmaxB, cB, cmaxB, rb[h]);
@@ -243,12 +227,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE ? GM_W
         if (!TA && TB) {          // both contiguous along k: one read per tile; the B tiles in two halves (24 operand registers, not 32)
             f32x4 av[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) av[i] = GM_LDS_READ(sa + (wm * 64 + 16 * i + l15) * GM_LDK + 4 * g, ra[0]);
+            for (int i = 0; i < 4; ++i) av[i] = *(const f32x4*)(sa + (wm * 64 + 16 * i + l15) * GM_LDK + 4 * g);
 #pragma unroll
             for (int jh = 0; jh < 2; ++jh) {
                 f32x4 bv[2];
 #pragma unroll
-                for (int j = 0; j < 2; ++j) bv[j] = GM_LDS_READ(sb + (wn * 64 + 16 * (2 * jh + j) + l15) * GM_LDK + 4 * g, rb[0]);
+                for (int j = 0; j < 2; ++j) bv[j] = *(const f32x4*)(sb + (wn * 64 + 16 * (2 * jh + j) + l15) * GM_LDK + 4 * g);
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -260,17 +244,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE ? GM_W
             f32x4 av[4], bv[4];   // k-contiguous operand: [tile]; free-contiguous operand: read per kk
             if (!TA) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) av[i] = GM_LDS_READ(sa + (wm * 64 + 16 * i + l15) * GM_LDK + 4 * g, ra[0]);
+                for (int i = 0; i < 4; ++i) av[i] = *(const f32x4*)(sa + (wm * 64 + 16 * i + l15) * GM_LDK + 4 * g);
             }
             if (TB) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) bv[j] = GM_LDS_READ(sb + (wn * 64 + 16 * j + l15) * GM_LDK + 4 * g, rb[0]);
+                for (int j = 0; j < 4; ++j) bv[j] = *(const f32x4*)(sb + (wn * 64 + 16 * j + l15) * GM_LDK + 4 * g);
             }
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 f32x4 af, bf;
-                if (TA) af = GM_LDS_READ(sa + (4 * g + kk) * GM_LDF + wm * 64 + 4 * l15, ra[0]);
-                if (!TB) bf = GM_LDS_READ(sb + (4 * g + kk) * GM_LDF + wn * 64 + 4 * l15, rb[0]);
+                if (TA) af = *(const f32x4*)(sa + (4 * g + kk) * GM_LDF + wm * 64 + 4 * l15);
+                if (!TB) bf = *(const f32x4*)(sb + (4 * g + kk) * GM_LDF + wn * 64 + 4 * l15);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -284,30 +268,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE ? GM_W
     // loads were issued" with "no stores follow" and puts a vmcnt(0) between the A and the B loads of a conditional version.)
     for (int s = 0; s + 1 < steps; ++s) {
         const int cur = s & 1;
-#if !(defined(GM_EXP) && (GM_EXP & 4))
         load_tiles(k_lo + (s + 1) * GM_BK, ra, rb);
-#endif
         __builtin_amdgcn_sched_barrier(0);   // the loads are issued in front of the step's MFMAs and waited for behind them (hipcc's
         multiply(cur);                       // scheduler would move both into the MFMA sequence, half a step apart)
         __builtin_amdgcn_sched_barrier(0);
-#if !(defined(GM_EXP) && (GM_EXP & 4))
         store_tiles(k_lo + (s + 1) * GM_BK, As[cur ^ 1], Bs[cur ^ 1], ra, rb);
-#endif
-#if !(defined(GM_EXP) && (GM_EXP & 8))
         __syncthreads();
-#endif
     }
     if (steps > 0) multiply((steps - 1) & 1);
 
-#if defined(GM_EXP) && (GM_EXP & 1)   // timing experiment: the k-loop alone (one store keeps it alive)
-    {
-        float t = 0.f;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j)
-                for (int r = 0; r < 4; ++r) t += acc[i][j][r];
-        if (t != 12345.678f) return;
-    }
-#endif
     // ---- epilogue: acc[i][j][r] = C[m][n] with m = m0 + 64 wm + mrow(i, 4 g + r), n = n0 + 64 wn + ncol(j, l15) ---------------------
     // Whatever the epilogue reads per output row (the point's coordinates; the mask values) is requested for FOUR rows at a time from
     // clamped addresses, ahead of the arithmetic that uses it: one wait per four rows instead of one per element.

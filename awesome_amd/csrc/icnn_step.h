@@ -308,43 +308,13 @@ __device__ __forceinline__ float sum_over_groups(float v) {  // the 4 lanes shar
     return v;
 }
 
-#ifndef INR_SCHED_HINTS
-#define INR_SCHED_HINTS 1
-#endif
-#if INR_SCHED_HINTS
 #define SGB(mask, n) __builtin_amdgcn_sched_group_barrier((mask), (n), 0)
-#else
-#define SGB(mask, n)
-#endif
 // Keep successive k-steps of MFMAs in program order (everything else may still move across): without it hipcc regroups
 // the products per accumulator, i.e. into dependent chains that pay the 40-cycle latency instead of the 32-cycle issue.
-#ifndef INR_BWD_B128
-#define INR_BWD_B128 0   // 1: the backward product reads the weight operand of a k-step as TM / 4 16-byte LDS reads (column-permuted tiles) instead of TM 4-byte ones: 343 fewer instructions per chunk, bit-identical, NOT faster (profiles/r04_issue_slot_budget.md section 5)
-#endif
-#ifndef INR_STAGE_Z0_EARLY
-#define INR_STAGE_Z0_EARLY 1
-#endif
-#ifndef INR_PROLOGUE_EARLY
-#define INR_PROLOGUE_EARLY 1   // 1: the parameter image goes to LDS by LDS-DMA, and everything that does not read it (kernel arguments, the first chunk's point, the accumulator zeroing) sits between the copy's issue and its wait; 0: register-staged copy, wait, barrier, then the rest (A/B in DESIGN.md 6)
-#endif
-#ifndef INR_SLAB_NT
-#define INR_SLAB_NT 1   // the slab tiles are written once and read once by another kernel: non-temporal stores (A/B in DESIGN.md 6)
-#endif
-#ifndef INR_TILES_SPREAD
-#define INR_TILES_SPREAD 1   // 1: the dW tile stores behind the chunk loop go out piece by piece between the cross-lane sums that follow them (a wave issues in order: a burst of 18 KB per wave holds it until the chip has accepted all 17 MB, and the sums wait); 0: all of them in front of the sums (A/B in DESIGN.md 6)
-#endif
-#ifndef INR_MFMA_ORDER
-#define INR_MFMA_ORDER 1
-#endif
-#if INR_MFMA_ORDER
 #define MFMA_STEP_FENCE() __builtin_amdgcn_sched_barrier(0x7F6)
 // ... and one that LDS reads may not cross either: operand reads written ahead of a block of MFMAs stay ahead of it
 // (hipcc otherwise sinks each read to just before its use and waits for it there, one LDS latency per pair of MFMAs).
 #define OPERAND_FENCE() __builtin_amdgcn_sched_barrier(0x676)
-#else
-#define MFMA_STEP_FENCE()
-#define OPERAND_FENCE()
-#endif
 
 // Diagnostic build only (-DINR_STAMPS=1): per-phase cycle sums of workgroup 0 / wave 0, read back by tools/stamps.py.
 // Never enabled in the shipped library (stamps fence the schedule; read their SHARES, not the run time).
@@ -400,12 +370,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     static_assert(!DX || ACT0 == INR_ACT_RELU, "the coordinate-gradient kernels are built for relu networks only");
     using G = Cfg<H, C>;
     constexpr int TM = G::TM, KG = G::KG, HM = G::HM, HR = G::HR, S = G::S, PT = G::PT, RPW = G::RPW, NEXT = G::NEXT;
-    // Backward product dZ0 = dZ1 . W1: with B128 a lane reads the weight row of a k-step as 16-byte vectors, columns 4 l15 .. 4 l15 + 3 of
-    // every 64-column block - element j of block u is the operand of tile 4 u + j, which therefore holds hidden unit 64 u + 4 l15 + j where
-    // the 4-byte reads' tile t holds 16 t + l15.  Everything dZ0 meets afterwards (the layer-0 relu mask, the layer-0 gradient's rows,
-    // W_in for the coordinate gradients) is indexed through bcol; each output element is the same sum in the same order.
-    constexpr bool B128 = INR_BWD_B128 && (TM % 4 == 0);
-    auto bcol = [](int t, int l) { return B128 ? 64 * (t >> 2) + 4 * l + (t & 3) : 16 * t + l; };
+    auto bcol = [](int t, int l) { return 16 * t + l; };   // hidden unit of tile t in lane column l
     constexpr int HRA = HR > 0 ? HR : 1;  // array extent (zero-length arrays are not allowed)
     static_assert(TM % RPW == 0, "row tiles must split evenly over the waves that own rows");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -432,29 +397,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 
     // ---- copy the parameter image into LDS ------------------------------------------------------------------------
     const float* __restrict__ gimg = a.wimg + (size_t)img * G::IMG_FLOATS;
-#if INR_PROLOGUE_EARLY
     // LDS-DMA; awaited by the barrier in image_arrived() below, behind everything in this prologue that does not read the image
     static_assert(WG_THREADS == 256, "image_to_lds_issue");
     const f32x4 img_tail = image_to_lds_issue<G::IMG_FLOATS>(gimg, smem, tid, lane, wave);
     __builtin_amdgcn_sched_barrier(0);
-#else
-    {   // register-staged (all loads in flight at once)
-        const f32x4* __restrict__ src = (const f32x4*)gimg;
-        constexpr int NV4 = G::IMG_FLOATS / 4;
-        constexpr int NIT = (NV4 + WG_THREADS - 1) / WG_THREADS;
-        f32x4 tmp[NIT];
-#pragma unroll
-        for (int k = 0; k < NIT; ++k) {
-            const int i = tid + k * WG_THREADS;
-            if (i < NV4) tmp[k] = src[i];
-        }
-#pragma unroll
-        for (int k = 0; k < NIT; ++k) {
-            const int i = tid + k * WG_THREADS;
-            if (i < NV4) ((f32x4*)smem)[i] = tmp[k];
-        }
-    }
-#endif
     float cfg_ = 0.f, cbg_ = 0.f;
     if (TRAIN) {
         cfg_ = a.coef[2 * img];
@@ -471,9 +417,6 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 #pragma unroll
         for (int u = 0; u < HRA; ++u) wol[u] = HR > 0 ? woT[HM + u] : 0.f;
     };
-#if !INR_PROLOGUE_EARLY
-    image_arrived();
-#endif
 
     // per-lane LDS addresses
     const float* const wf = Wimg + l15 * S + 4 * g;  // forward A operand: row 16t + l15, columns 16tk + 4g ..+3
@@ -491,7 +434,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     float dwol[HRA];       // ... leftover units (lane group 0 only)
     float dWl[HRA][KG];    // leftover rows of dW1ext: column 16b + l15, partial over this lane group's points
     float dL0l[HRA][NEXT]; // leftover rows of the layer-0 gradient (lane group 0 only)
-    // (With INR_PROLOGUE_EARLY these zeros still land behind the image's barrier: hipcc materialises them at the end of the block in
+    // (These zeros still land behind the image's barrier: hipcc materialises them at the end of the block in
     // front of the loop wherever the source writes them.  Pinning them in front of the wait takes one asm statement per register, and
     // that moved the chunk loop's allocation: +85 v_accvgpr moves per chunk.)
     float loss_acc = 0.f, dbo = 0.f, dso[C];
@@ -558,12 +501,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         return q;
     };
     PointIn nxt = load_point(wg);   // (a workgroup without a chunk loads the clamped, valid address and never uses it)
-#if INR_PROLOGUE_EARLY
     __builtin_amdgcn_sched_barrier(0);
     image_tail_to_lds<G::IMG_FLOATS>(smem, tid, img_tail);
     image_arrived();
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #if INR_STAMPS
     unsigned long long st_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
@@ -688,10 +629,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 #pragma unroll
                 for (int r = 0; r < 4; ++r) z0[tk + 1][r] = act0_f<ACT0>(zn[r], a.act_omega);
             }
-#if INR_STAGE_Z0_EARLY
             // z0 tile tk has served as this k-group's operand; all that is left for it is to be the dW product's staged operand
             if (TRAIN && tk < TM) *(f32x4*)(stB + (wave * 16 + l15) * G::SB + 4 * g + 16 * tk) = z0[tk];
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
 
@@ -715,9 +654,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         for (int t = 0; t < TM; ++t) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-#if !(defined(INR_EXP_NOVALU) && (INR_EXP_NOVALU & 1))   // (timing experiment: wrong results)
                 acc[t][r] = relu0(acc[t][r]);  // z1
-#endif
                 ypart = fmaf(wo[t][r], acc[t][r], ypart);
             }
         }
@@ -782,16 +719,9 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 for (int r = 0; r < 4; ++r) {
                     const float z1 = acc[t][r];
                     dwo[t][r] = fmaf(dy, z1, dwo[t][r]);
-#if defined(INR_EXP_NOVALU) && (INR_EXP_NOVALU & 2)
-                    acc[t][r] = dy * wot[r];
-#else
                     acc[t][r] = z1 > 0.f ? dy * wot[r] : 0.f;
-#endif
                 }
                 *(f32x4*)(sa + 16 * t) = acc[t];
-#if !INR_STAGE_Z0_EARLY
-                *(f32x4*)(sb + 16 * t) = z0[t];
-#endif
             };
             if (HR > 0 && g == 0) {
                 f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -818,25 +748,18 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             float dzlg = 0.f;   // this lane group's leftover dz1
 #pragma unroll
             for (int u = 0; u < HR; ++u) dzlg = g == u ? dzl[u] : dzlg;
-            float bq[2][B128 ? 1 : TM];          // B operands (weights): row o of this k-step, columns 16t + l15
-            f32x4 bq4[2][B128 ? TM / 4 : 1];     // B128: the same row as 16-byte reads, columns 64 u + 4 l15 .. + 3
+            float bq[2][TM];      // B operands (weights): row o of this k-step, columns 16t + l15
             f32x4 wcq[2][HRA];    // leftover input columns W1[o][HM+u] at this lane's positions of a tile
             auto b_row = [&](int ks) -> const float* {  // LDS row of the weight operand for k-step ks
                 const int tk = ks >> 2, r = ks & 3;
                 if (tk < TM) return wb + (16 * tk + 4 * g + r) * S;
                 return wb + (g < HR ? (HM + g) * S : 0);  // leftover output u lives in lane group u (others: A = 0)
             };
-            auto b_vec = [&](int ks, int u) { return *(const f32x4*)(b_row(ks) + 3 * l15 + 64 * u); };   // (wb = Wimg + l15)
             dz1_tile(0);
             {
                 const float* br = b_row(0);
-                if constexpr (B128) {
 #pragma unroll
-                    for (int u = 0; u < TM / 4; ++u) bq4[0][u] = b_vec(0, u);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < TM; ++t) bq[0][t] = br[16 * t];
-                }
+                for (int t = 0; t < TM; ++t) bq[0][t] = br[16 * t];
                 if (DX) bqx[0] = br[16 * TM];
 #pragma unroll
                 for (int u = 0; u < HR; ++u) wcq[0][u] = *(const f32x4*)(WcT + u * PT + 4 * g);
@@ -856,13 +779,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 const float bop = tk < TM ? acc[tk < TM ? tk : 0][r] : dzlg;
 #pragma unroll
                 for (int t = 0; t < TM; ++t) {  // D = dZ0 with POINTS on the rows; next k-step's operand reads one per product
-                    if constexpr (B128) {
-                        dz0[t] = MFMA16(bop, bq4[ks & 1][t >> 2][t & 3], ks == 0 ? (f32x4{0.f, 0.f, 0.f, 0.f}) : dz0[t]);
-                        if (ks + 1 < KS && (t & 3) == 0) bq4[(ks + 1) & 1][t >> 2] = b_vec(ks + 1, t >> 2);
-                    } else {
-                        dz0[t] = MFMA16(bop, bq[ks & 1][t], ks == 0 ? (f32x4{0.f, 0.f, 0.f, 0.f}) : dz0[t]);
-                        if (ks + 1 < KS) bq[(ks + 1) & 1][t] = b_row(ks + 1)[16 * t];
-                    }
+                    dz0[t] = MFMA16(bop, bq[ks & 1][t], ks == 0 ? (f32x4{0.f, 0.f, 0.f, 0.f}) : dz0[t]);
+                    if (ks + 1 < KS) bq[(ks + 1) & 1][t] = b_row(ks + 1)[16 * t];
                     OPERAND_FENCE();
                 }
                 if (DX) dzx = MFMA16(bop, bqx[ks & 1], dzx);
@@ -891,12 +809,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 for (int t = 0; t < TM; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-#if defined(INR_EXP_NOVALU) && (INR_EXP_NOVALU & 4)
-                        asm volatile("" ::"v"(z0p[t][r]));
-#else
                         if constexpr (ACT0 == INR_ACT_RELU) dz0[t][r] = z0p[t][r] > 0.f ? dz0[t][r] : 0.f;
                         else dz0[t][r] *= dact0_f<ACT0>(z0p[t][r], a.act_omega);
-#endif
                     }
                 auto swap32 = [](float& u, float& v) {   // lane groups 2, 3 of u <-> lane groups 0, 1 of v
                     const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(v), false, false);
@@ -1061,16 +975,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         // ---- dW1ext tiles of this wave: one 16-byte store per lane and tile, in accumulator order (Cfg: gradient slab) --------
         // A wave issues in order, and its RPW KG tile stores (18 KB at h = 130; 17 MB over the chip, all waves at once) are accepted only as
         // fast as the chip drains them: as one burst they hold the wave for ~4 k cycles while the ~1000 instructions of sums below wait
-        // behind them.  INR_TILES_SPREAD cuts those sums into UW units of work - the reduction of one dw_o tile counts as four columns of
-        // the leftover rows - and lets the tiles that fall to a unit leave behind it: the queue drains while the VALU adds.  (The store
+        // behind them.  So the sums are cut into UW units of work - the reduction of one dw_o tile counts as four columns of
+        // the leftover rows - and the tiles that fall to a unit leave behind it: the queue drains while the VALU adds.  (The store
         // block is a file of its own, included once per place: as a lambda over dW it moves hipcc's allocation of the whole kernel.)
         constexpr int NTILES = RPW * KG, UW = 4 * TM + HR * KG;
-#if !INR_TILES_SPREAD
-        {
-            constexpr int tile_from = 0, tile_to = NTILES;
-#include "icnn_step_tiles.h"
-        }
-#endif
         // ---- everything that was summed per lane: reduce within the wave, then over the waves through LDS -------------
         constexpr int SC_DWO = 0;                    // [PT]            dw_o by position
         constexpr int SC_DWL = SC_DWO + PT;          // [HRA][PT]       leftover rows of dW1ext by column position
@@ -1087,12 +995,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 const float v = sum_over_points(dwo[t][r]);
                 if (l15 == 0) scr[SC_DWO + 16 * t + 4 * g + r] = v;
             }
-#if INR_TILES_SPREAD
             {
                 const int tile_from = 4 * t * NTILES / UW, tile_to = (4 * t + 4) * NTILES / UW;
 #include "icnn_step_tiles.h"
             }
-#endif
         }
 #pragma unroll
         for (int u = 0; u < HR; ++u) {
@@ -1102,12 +1008,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             for (int b = 0; b < KG; ++b) {
                 const float w = sum_over_groups(dWl[u][b]);
                 if (g == 0) scr[SC_DWL + u * PT + 16 * b + l15] = w;
-#if INR_TILES_SPREAD
                 {
                     const int tile_from = (4 * TM + u * KG + b) * NTILES / UW, tile_to = (4 * TM + u * KG + b + 1) * NTILES / UW;
 #include "icnn_step_tiles.h"
                 }
-#endif
             }
 #pragma unroll
             for (int e = 0; e < NEXT; ++e) {

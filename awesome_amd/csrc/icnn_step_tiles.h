@@ -1,9 +1,7 @@
 // icnn_step_tiles.h - the dW tile stores of icnn_step_kernel, a block of its code behind the chunk loop (no header of its own right:
 // icnn_step.h includes it at every place where tiles leave).  `slab` is this workgroup's gradient slab; the tiles (row tile j, column
 // tile b) with tile_from <= j KG + b < tile_to are stored, and nothing is scheduled across the block.
-#if INR_TILES_SPREAD
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (row_ok) {
 #pragma unroll
             for (int j = 0; j < RPW; ++j) {
@@ -17,18 +15,12 @@
                     }
                     if (used && j * KG + b >= tile_from && j * KG + b < tile_to) {
                         f32x4* dst = (f32x4*)(slab + ((((wave * RPW + j) * KG + b) * 64 + lane) << 2));
-#if INR_SLAB_NT
-                        __builtin_nontemporal_store(dW[j][b], dst);
-#else
-                        *dst = dW[j][b];
-#endif
+                        __builtin_nontemporal_store(dW[j][b], dst);   // written once, read once by another kernel
                     }
                 }
             }
         }
-#if INR_TILES_SPREAD
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #if INR_STAMPS
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_store)::"memory");   // a tile store has been issued (the last one's stays)
         __builtin_amdgcn_sched_barrier(0);

@@ -111,9 +111,6 @@ __host__ __device__ __forceinline__ int user_param_index(const ImgMap& m, int h,
     return base_u + h + (j - m.p_bo);        // out.ln.bias, out.skp.weight [C]
 }
 
-#ifndef INR_UPD_SLABS_FIRST
-#define INR_UPD_SLABS_FIRST 1   // 1: the update's slab loads are a block's first memory instructions; 0: behind the index arithmetic and the p / m / v requests
-#endif
 constexpr int UPD_MAX_PARAMS = 256;  // most parameters per block
 constexpr int UPD_GROUPS = 16;       // slab groups summed in parallel, then combined in fixed order
 
@@ -195,9 +192,7 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
         }
         __builtin_amdgcn_sched_barrier(0);
     };
-#if INR_UPD_SLABS_FIRST
     request_slabs();
-#endif
     // then the header
     float* __restrict__ st = u.opt_state + (size_t)img * (2 * (size_t)u.Pu + INR_OPT_HEADER_FLOATS);
     float* __restrict__ hdr = st + 2 * (size_t)u.Pu;
@@ -215,10 +210,6 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
         m_old = st[ju];
         v_old = st[u.Pu + ju];
     }
-#if !INR_UPD_SLABS_FIRST
-    __builtin_amdgcn_sched_barrier(0);
-    request_slabs();
-#endif
     // what the optimizer's tail needs of the index alone: the image slots, the range tests
     int slot[2] = {0, 0}, n_slots = 0;
     bool never_updated = false, clamped = false;
@@ -3357,6 +3348,7 @@ int inrfit_pack_masks(const float* values, int n_images, int64_t n_points, float
 }
 
 #if INR_STAMPS
+#pragma GCC visibility push(default)   // diagnostic readers, not in include/inrfit.h: tools/stamps*.py find them by name
 int inrfit_debug_updtimes(unsigned long long* host_out) {   // [512][4] of the last update launch
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_updtimes), sizeof(unsigned long long) * 2048) == hipSuccess ? 0 : -4;
 }
@@ -3377,6 +3369,7 @@ int inrfit_debug_wgtimes(unsigned long long* host_out) {   // [1024][4], then cl
     static unsigned long long zeros[4096];
     return hipMemcpyToSymbol(HIP_SYMBOL(g_wgtimes), zeros, sizeof(zeros)) == hipSuccess ? 0 : -4;
 }
+#pragma GCC visibility pop
 #endif
 
 const char* inrfit_strerror(int code) {

@@ -26,10 +26,6 @@
 #pragma once
 #include "flow.h"
 
-#ifndef RNVP_FWD_CLAMP
-#define RNVP_FWD_CLAMP 1   // the forward kernels use the clamped asm form too (0: fma + 2 x v_max; see rnvp_nets)
-#endif
-
 namespace {
 
 constexpr int RNVP_MAX_FLOWS = 32;
@@ -194,11 +190,11 @@ __global__ __launch_bounds__(256) void rnvp_pack_kernel(const RnvpPackArgs a) {
 // unit.  Read from LDS that is one ds_read_b128 pair per unit and wave, and the LDS return path (128 B per clock and CU) delivers
 // 64 lanes x 16 B = 8 clocks per read whatever the address pattern: 64 reads per flow x 8 clocks x 16 waves per CU put the LDS pipe at
 // 100 % - rounds 1-2 called these kernels "VALU-issue bound" at 0.62 VALU busy; they were LDS-return bound (the arithmetic gives
-// 61 us for configs[3]'s forward, measured 53).  Uniform data belongs on the SCALAR data path: the packed image in HBM is read through
-// a constant-address-space pointer with uniform addresses, which hipcc selects as s_load_dwordx4/x8 into SGPRs (scalar cache, no LDS,
-// no VGPRs); VALU instructions take one SGPR pair as an operand directly.  (One SGPR pair per instruction: pre = w1 z + b1 is issued
-// as v_pk_mul + v_pk_add instead of v_mov x2 + v_pk_fma.)  The one-flow init / unit-gradient kernels keep their small LDS image.
-// (RecK / RecL: flow.h)
+// 61 us for configs[3]'s forward, measured 53).  Uniform data would belong on the SCALAR data path - the packed image in HBM read
+// through a constant-address-space pointer with uniform addresses, which hipcc selects as s_load_dwordx4/x8 into SGPRs (scalar cache,
+// no LDS, no VGPRs), one SGPR pair per VALU instruction (pre = w1 z + b1 as v_pk_mul + v_pk_add instead of v_mov x2 + v_pk_fma) - but
+// round 3 measured that path 2-3x slower (flow.h header; profiles/NOTES.md): the scalar cache cannot feed the loop.  Every kernel
+// reads the records from its LDS image (RecL: flow.h).
 
 // pre-activation outputs o[q][k] = (o_s, o_t) of the two MLPs of one flow for the NOUT active output channels of Q points
 // per lane (a record read from LDS serves all Q); DU: also J[q][k][m] = d o[k] / d zin[m] (packed for both nets).
@@ -224,13 +220,7 @@ __device__ __forceinline__ void rnvp_nets(const Rec rec, int HID, const float (&
                 f32x2 pre = f32x2{v[2 * NIN], v[2 * NIN + 1]};
 #pragma unroll
                 for (int mm = 0; mm + 1 < NIN; ++mm) pre = pk_fma(f32x2{v[2 * mm], v[2 * mm + 1]}, splat2(zin[q][mm]), pre);
-                f32x2 h;   // relu(pre) 2^-32
-                if constexpr (DU || RNVP_FWD_CLAMP) {
-                    h = pk_fma_clamp_bcast(f32x2{v[2 * (NIN - 1)], v[2 * (NIN - 1) + 1]}, zin[q][NIN - 1], pre);
-                } else {
-                    pre = pk_fma(f32x2{v[2 * (NIN - 1)], v[2 * (NIN - 1) + 1]}, splat2(zin[q][NIN - 1]), pre);
-                    h = f32x2{fmaxf(pre[0], 0.f), fmaxf(pre[1], 0.f)};
-                }
+                const f32x2 h = pk_fma_clamp_bcast(f32x2{v[2 * (NIN - 1)], v[2 * (NIN - 1) + 1]}, zin[q][NIN - 1], pre);   // relu(pre) 2^-32
                 if (DU) {
                     const f32x2 st = step01(h);
                     f32x2 t[NIN];
@@ -291,27 +281,14 @@ __device__ __forceinline__ void rnvp_nets(const Rec rec, int HID, const float (&
         const float v[8] = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            f32x2 h;   // relu(pre) 2^-32: the last fma of the pre-activation carries the clamp (flow.h, pk_fma_clamp_bcast)
-            if constexpr (Rec::SCALAR) {   // (experiment path) one SGPR pair per instruction: mul, (fma,) add
-                f32x2 pre = f32x2{v[0], v[1]} * splat2(zin[q][0]);
+            f32x2 pre = f32x2{v[2 * NIN], v[2 * NIN + 1]};
 #pragma unroll
-                for (int mm = 1; mm < NIN; ++mm) pre = pk_fma(f32x2{v[2 * mm], v[2 * mm + 1]}, splat2(zin[q][mm]), pre);
-                pre = pre + f32x2{v[2 * NIN], v[2 * NIN + 1]};
-                h = f32x2{fminf(fmaxf(pre[0], 0.f), 1.f), fminf(fmaxf(pre[1], 0.f), 1.f)};
-            } else {
-                f32x2 pre = f32x2{v[2 * NIN], v[2 * NIN + 1]};
-#pragma unroll
-                for (int mm = 0; mm + 1 < NIN; ++mm) pre = pk_fma(f32x2{v[2 * mm], v[2 * mm + 1]}, splat2(zin[q][mm]), pre);
-                if constexpr (DU || RNVP_FWD_CLAMP) {
-                    h = pk_fma_clamp_bcast(f32x2{v[2 * (NIN - 1)], v[2 * (NIN - 1) + 1]}, zin[q][NIN - 1], pre);
-                } else {
-                    // (RNVP_FWD_CLAMP = 0) fma + 2 x v_max on the scaled records.  The clamped asm form was first measured SLOWER in the
-                    // forward kernels (16.95 vs 14.7 us at 256x256, 55.8 vs 53.9 at configs[3]): hipcc does not unroll a loop around an asm
-                    // statement, so every unit paid its own LDS round trip; with the batches of 4 written out it is faster (13.8 / 52.0 us).
-                    pre = pk_fma(f32x2{v[2 * (NIN - 1)], v[2 * (NIN - 1) + 1]}, splat2(zin[q][NIN - 1]), pre);
-                    h = f32x2{fmaxf(pre[0], 0.f), fmaxf(pre[1], 0.f)};
-                }
-            }
+            for (int mm = 0; mm + 1 < NIN; ++mm) pre = pk_fma(f32x2{v[2 * mm], v[2 * mm + 1]}, splat2(zin[q][mm]), pre);
+            // relu(pre) 2^-32: the last fma of the pre-activation carries the clamp (flow.h, pk_fma_clamp_bcast), in the forward kernels
+            // too.  Against fma + 2 x v_max on the scaled records the clamped asm form was first measured SLOWER there (16.95 vs 14.7 us
+            // at 256x256, 55.8 vs 53.9 at configs[3]): hipcc does not unroll a loop around an asm statement, so every unit paid its own
+            // LDS round trip; with the batches of 4 written out it is faster (13.8 / 52.0 us).
+            const f32x2 h = pk_fma_clamp_bcast(f32x2{v[2 * (NIN - 1)], v[2 * (NIN - 1) + 1]}, zin[q][NIN - 1], pre);
             if (DU) {
                 const f32x2 st = step01(h);
                 f32x2 t[NIN];
@@ -358,16 +335,13 @@ __device__ __forceinline__ void rnvp_nets(const Rec rec, int HID, const float (&
                 eval4(rb);
             }
         }
-    } else if constexpr (DU || RNVP_FWD_CLAMP) {   // batches of 4 written out: hipcc does not unroll a loop around an asm statement
-                                                 // (step01 / the clamped fma); one register set (the C = 3 kernels run 4 waves per SIMD)
+    } else {   // batches of 4 written out: hipcc does not unroll a loop around an asm statement (step01 / the clamped fma); one
+               // register set (the C = 3 kernels run 4 waves per SIMD)
         for (; j + 4 <= HID; j += 4) {
             f32x4 r[8];
             load4(r, j);
             eval4(r);
         }
-    } else {   // hipcc's own order (it also narrows the record reads to what is used): the forward kernels are faster with it
-#pragma unroll 4
-        for (; j < HID; ++j) unit(rec.v4(RNVP_REC * j), rec.v4(RNVP_REC * j + 4));
     }
     for (; j < HID; ++j) unit(rec.v4(RNVP_REC * j), rec.v4(RNVP_REC * j + 4));
 }

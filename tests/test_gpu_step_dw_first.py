@@ -1,7 +1,7 @@
 """GPU parity of the L = 1 step kernel around the point where its dW tiles leave for the gradient slab (icnn_step.h).
 Written for the order "dW product first, the tiles of a workgroup's LAST chunk leave from inside the chunk loop" (measured slower
 and not shipped, profiles/NOTES.md); what ships moves the same stores the other way, in between the cross-lane sums behind the loop
-(INR_TILES_SPREAD).  Either way the same few things can go wrong: which chunk a workgroup takes for its last one, a tile stored
+(icnn_step_tiles.h).  Either way the same few things can go wrong: which chunk a workgroup takes for its last one, a tile stored
 before its last chunk was added, stored twice or never, a slab column of the sums clobbered by a tile.  So the launches here are tiny and the
 slab base is set by hand (inrfit_debug_set_slab_base) to choose the chunks per workgroup:
 

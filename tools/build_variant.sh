@@ -1,8 +1,4 @@
 #!/bin/bash
-# build_variant.sh NAME [-DFLAG=..]...  ->  gpurun_variants/libinrfit_NAME.so   (A/B builds for tools/kbench.py via INRFIT_LIB)
+# build_variant.sh NAME [-DFLAG=..]...  ->  variants/libinrfit_NAME.so   (A/B and stamps builds, loaded through INRFIT_LIB)
 set -e
-cd "$(dirname "$0")/.."
-mkdir -p variants
-name=$1; shift
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form -shared -fPIC -Iinclude "$@" awesome_amd/csrc/inrfit.hip -o variants/libinrfit_$name.so
-echo variants/libinrfit_$name.so
+cd "$(dirname "$0")/.." && mkdir -p variants && python -m awesome_amd.build --force --out "variants/libinrfit_$1.so" "${@:2}"
