@@ -2,7 +2,8 @@
 Written for the order "dW product first, the tiles of a workgroup's LAST chunk leave from inside the chunk loop" (measured slower
 and not shipped, profiles/NOTES.md); what ships moves the same stores the other way, in between the cross-lane sums behind the loop
 (icnn_step_tiles.h).  Either way the same few things can go wrong: which chunk a workgroup takes for its last one, a tile stored
-before its last chunk was added, stored twice or never, a slab column of the sums clobbered by a tile.  So the launches here are tiny and the
+before its last chunk was added, stored twice or never, a slab column of the sums clobbered by a tile.  (The L = 2 kernel's counterpart, with its W2 re-fetch: tests/test_gpu_step2_chunks.py.)
+So the launches here are tiny and the
 slab base is set by hand (inrfit_debug_set_slab_base) to choose the chunks per workgroup:
 
     base 8, N = 64 * 10 + 17   11 chunks on 8 workgroups: 0-2 take two, 3-7 take one, the last chunk is ragged
