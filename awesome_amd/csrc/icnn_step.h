@@ -635,11 +635,14 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
         }
 
         STAMP(2);
-        // relu mask of layer 0 in the transposed layout of the backward product (rows = points): z0^T is the layer-0 product
-        // with swapped operands, TM more MFMAs - issued here, where the matrix pipe would otherwise idle under the VALU work
-        // of the output layer and the data term.
+        // Layer-0 derivative in the transposed layout of the backward product (rows = points).  relu nets need no arithmetic for it:
+        // relu(pre) > 0 is pre > 0, and z0 = relu(pre) of this wave's points already sits in its own stage-B rows (staged by the
+        // forward product above), so the backward product reads the mask from there behind its last k-steps (zm below).  The sin / cos
+        // encode nets need the pre-activation itself: z0^T is the layer-0 product with swapped operands, TM more MFMAs - issued here,
+        // where the matrix pipe would otherwise idle under the VALU work of the output layer and the data term.
+        constexpr bool MASK_STAGED = TRAIN && ACT0 == INR_ACT_RELU;
         f32x4 z0p[TM];
-        if (TRAIN) {
+        if (TRAIN && !MASK_STAGED) {
             float wie[TM];
 #pragma unroll
             for (int t = 0; t < TM; ++t) wie[t] = WinE[g * PT + bcol(t, l15)];   // (the columns the backward product's tile t holds)
@@ -755,6 +758,15 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 if (tk < TM) return wb + (16 * tk + 4 * g + r) * S;
                 return wb + (g < HR ? (HM + g) * S : 0);  // leftover output u lives in lane group u (others: A = 0)
             };
+            // relu nets: the layer-0 mask is the sign of z0, unit 16t + l15 at point 4g + r, read back from this wave's own stage-B rows
+            // (written by this wave in the forward product; the b32 pattern of the dW product's bf reads, conflict-free).  One read
+            // behind every second product of the last eight k-steps: requested late, and no wait in front of an MFMA.
+            f32x4 zm[TM];
+            const float* const zrow = stB + (wave * 16 + 4 * g) * G::SB + l15;
+            constexpr int MK0 = KS > 8 ? KS - 8 : 0;   // first k-step that carries mask reads
+            auto mask_read = [&](int i) {
+                if (MASK_STAGED && i < 4 * TM) zm[i % TM][i / TM] = zrow[(i / TM) * G::SB + 16 * (i % TM)];
+            };
             dz1_tile(0);
             {
                 const float* br = b_row(0);
@@ -781,6 +793,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 for (int t = 0; t < TM; ++t) {  // D = dZ0 with POINTS on the rows; next k-step's operand reads one per product
                     dz0[t] = MFMA16(bop, bq[ks & 1][t], ks == 0 ? (f32x4{0.f, 0.f, 0.f, 0.f}) : dz0[t]);
                     if (ks + 1 < KS) bq[(ks + 1) & 1][t] = b_row(ks + 1)[16 * t];
+                    if (ks >= MK0 && (((ks - MK0) * TM + t) & 1)) mask_read(((ks - MK0) * TM + t) >> 1);
                     OPERAND_FENCE();
                 }
                 if (DX) dzx = MFMA16(bop, bqx[ks & 1], dzx);
@@ -799,56 +812,36 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                 MFMA_STEP_FENCE();
             }
             STAMP(4);
-            // relu mask of layer 0 (z0p, computed before the output layer); then the layer-0 gradient dW_in += dZ0^T . (1, x) over this
-            // wave's 16 points.  On the VALU: the product has NEXT useful columns, a matrix-pipe tile pads them to 16 (4 TM MFMAs for 6
-            // MFMAs' worth of arithmetic).  dz0[t][r] holds point 4g + r of unit (t, l15); a 4 x 4 transpose between lane
-            // groups and tiles (four permlane swaps per four registers) hands lane group g the tiles 4q + g for the points of ALL lane
-            // groups, and every parameter is then one FMA chain in the matrix pipe's own order: the same bits as the MFMA form.
-            {
+            // Layer-0 derivative (relu nets: the mask zm read from stage B; encode nets: z0p, computed before the output layer); then the
+            // layer-0 gradient dW_in += dZ0^T . (1, x) over this wave's 16 points.  On the VALU: the product has NEXT useful columns, a
+            // matrix-pipe tile pads them to 16 (4 TM MFMAs for 6 MFMAs' worth of arithmetic).  dz0[t][r] holds point
+            // 4g + r of unit (t, l15); a 4 x 4 transpose between lane groups and tiles (four permlane swaps per four registers) hands
+            // lane group g the tiles 4q + g for the points of ALL lane groups, and every parameter is then one FMA chain in the matrix
+            // pipe's own order: the same bits as the MFMA form.  Nothing in front of the chunk-end barrier needs these sums, and the
+            // block is latency, not issue (six dependent chains): only the mask is applied here, the transpose and the chains run as 16
+            // slices behind the k-steps of the dW product below (icnn_step_l0.h), r-major, then k - every chain adds in the same order.
 #pragma unroll
-                for (int t = 0; t < TM; ++t)
+            for (int i = (KS - MK0) * TM / 2; i < 4 * TM; ++i) mask_read(i);   // (shapes with fewer than eight k-steps)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if constexpr (ACT0 == INR_ACT_RELU) dz0[t][r] = z0p[t][r] > 0.f ? dz0[t][r] : 0.f;
-                        else dz0[t][r] *= dact0_f<ACT0>(z0p[t][r], a.act_omega);
-                    }
-                auto swap32 = [](float& u, float& v) {   // lane groups 2, 3 of u <-> lane groups 0, 1 of v
-                    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(v), false, false);
-                    u = __uint_as_float(s[0]);
-                    v = __uint_as_float(s[1]);
-                };
-                auto swap16 = [](float& u, float& v) {   // lane groups 1, 3 of u <-> lane groups 0, 2 of v
-                    const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(v), false, false);
-                    u = __uint_as_float(s[0]);
-                    v = __uint_as_float(s[1]);
-                };
-                const float* const xrow = stB + wave * 16 * G::SB;   // this wave's stage-B rows: one address per wave, LDS broadcasts
+            for (int t = 0; t < TM; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float D[NQ][4];   // D[q][k]: dz0 of unit (4q + g, l15) at point 4k + r
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) D[q][j] = 4 * q + j < TM ? dz0[4 * q + j < TM ? 4 * q + j : 0][r] : 0.f;
-                        swap32(D[q][0], D[q][2]);
-                        swap32(D[q][1], D[q][3]);
-                        swap16(D[q][0], D[q][1]);
-                        swap16(D[q][2], D[q][3]);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        float xp[C];
-#pragma unroll
-                        for (int c = 0; c < C; ++c) xp[c] = xrow[(4 * k + r) * G::SB + G::ext_pos(1 + c)];
-#pragma unroll
-                        for (int q = 0; q < NQ; ++q) {
-                            dL0[q][0] += D[q][k];
-#pragma unroll
-                            for (int c = 0; c < C; ++c) dL0[q][1 + c] = fmaf(D[q][k], xp[c], dL0[q][1 + c]);
-                        }
-                    }
+                    if constexpr (MASK_STAGED) dz0[t][r] = zm[t][r] > 0.f ? dz0[t][r] : 0.f;
+                    else dz0[t][r] *= dact0_f<ACT0>(z0p[t][r], a.act_omega);
                 }
-            }
+            auto swap32 = [](float& u, float& v) {   // lane groups 2, 3 of u <-> lane groups 0, 1 of v
+                const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(v), false, false);
+                u = __uint_as_float(s[0]);
+                v = __uint_as_float(s[1]);
+            };
+            auto swap16 = [](float& u, float& v) {   // lane groups 1, 3 of u <-> lane groups 0, 2 of v
+                const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(v), false, false);
+                u = __uint_as_float(s[0]);
+                v = __uint_as_float(s[1]);
+            };
+            const float* const xrow = stB + wave * 16 * G::SB;   // this wave's stage-B rows: one address per wave, LDS broadcasts
+            float D[NQ][4];   // slices (r, .): D[q][k] = dz0 of unit (4q + g, l15) at point 4k + r
+            float xpq[4][C];  // slice (r, k): coordinates of point 4k + r
             // leftover rows of the layer-0 gradient (lane group 0, VALU)
             float hx[C];  // DX: the contributions that live per point on lane l15: s_o dy + W_in[HM+u] dz0l[u]
 #pragma unroll
@@ -939,6 +932,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
 #pragma unroll
                             for (int b = 0; b < KG; ++b) dWl[u][b] = fmaf(dl[u], bf[cur][b], dWl[u][b]);
                     }
+                    // k-step `it` also requests the coordinates of layer-0 slice (r, k) = (it >> 2, it & 3), point 4k + r of this wave,
+                    // behind its own operand reads (nothing writes stage B between the barriers around this product)
+                    constexpr int XS = RPW * KG > RPW + KG ? RPW * KG - (RPW + KG) : 0;   // products left over for them
+                    auto xp_read = [&](int i) {
+                        if (i >= 0 && i < C) xpq[it & 3][i] = xrow[(4 * (it & 3) + (it >> 2)) * G::SB + G::ext_pos(1 + i)];
+                    };
                     if (row_ok) {
 #pragma unroll
                         for (int j = 0; j < RPW; ++j)
@@ -946,17 +945,30 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                             for (int b = 0; b < KG; ++b) {
                                 dW[j][b] = MFMA16(af[cur][j], bf[cur][b], dW[j][b]);
                                 next_read(j * KG + b);
+                                xp_read(j * KG + b - (RPW + KG));
                                 OPERAND_FENCE();
                             }
+#pragma unroll
+                        for (int i = XS; i < C; ++i) xp_read(i);
                     } else {
 #pragma unroll
                         for (int i = 0; i < RPW + KG; ++i) next_read(i);
+#pragma unroll
+                        for (int i = 0; i < C; ++i) xp_read(i);
                     }
                     if (RPW * KG < RPW + KG) {
 #pragma unroll
                         for (int i = RPW * KG; i < RPW + KG; ++i) next_read(i);
                     }
                     __builtin_amdgcn_sched_barrier(0);
+                    // The layer-0 gradient in the shadow of this product: slice (r, k) = (it >> 2, it & 3) as one burst behind k-step `it`
+                    // (one burst per k-step measured faster than one per four, profiles/NOTES.md).  The last slice is done in front of
+                    // the chunk-end barrier; stage B keeps this chunk's coordinates until this wave stages the next chunk's.
+                    {
+                        const int r = it >> 2, k = it & 3;
+#include "icnn_step_l0.h"
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
             }
             STAMP(7);
