@@ -230,6 +230,12 @@ EXPORTS = {
     "inrfit_unet_pack": (C.c_int, [C.POINTER(InrUNetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "inrfit_unet_forward": (C.c_int, [C.POINTER(InrUNetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_unet_param_count": (C.c_int64, [C.POINTER(InrUNetDesc)]),
+    "inrfit_unet_train_workspace_bytes": (C.c_int64, [C.POINTER(InrUNetDesc)]),
+    "inrfit_unet_train_forward": (C.c_int, [C.POINTER(InrUNetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_unet_train_backward": (C.c_int, [C.POINTER(InrUNetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -32,6 +32,7 @@
 #include "cnnseg.h"
 #include "fcseg.h"
 #include "unet.h"
+#include "unet_train.h"
 
 #include <type_traits>
 #include <vector>
@@ -3557,6 +3558,56 @@ int inrfit_unet_forward(const InrUNetDesc* desc, const float* packed, const floa
     const UNetPlan p = unet_plan(desc);
     if (workspace_bytes < p.bytes) return INR_EWORKSPACE;
     return unet_forward(desc, p, packed, input, logits, (float*)workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- the UNet backbone's training step (csrc/unet_train.h) ------------------------------------------------------------------------------
+extern "C" {
+
+int64_t inrfit_unet_param_count(const InrUNetDesc* desc) {
+    const int rc = unet_desc_rc(desc);
+    return rc ? rc : unet_train_plan(desc).param_count;
+}
+
+int64_t inrfit_unet_train_workspace_bytes(const InrUNetDesc* desc) {
+    const int rc = unet_train_desc_rc(desc);
+    return rc ? rc : unet_train_plan(desc).bytes;
+}
+
+int inrfit_unet_train_forward(const InrUNetDesc* desc, const float* const* conv_w, const float* const* conv_b, const float* const* bn_gamma,
+                              const float* const* bn_beta, float* const* running_mean, float* const* running_var, float momentum,
+                              const float* input, float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!desc || !conv_w || !conv_b || !bn_gamma || !bn_beta || !running_mean || !running_var || !input || !logits || !workspace)
+        return INR_EINVAL;
+    for (int i = 0; i < UNET_CONVS; ++i)
+        if (!conv_w[i] || !conv_b[i]) return INR_EINVAL;
+    for (int i = 0; i < UNET_CONVS - 1; ++i)
+        if (!bn_gamma[i] || !bn_beta[i] || !running_mean[i] || !running_var[i]) return INR_EINVAL;
+    if (((uintptr_t)workspace) & 15) return INR_EINVAL;
+    if (!(momentum >= 0.f && momentum <= 1.f)) return INR_EINVAL;
+    const int rc = unet_train_desc_rc(desc);
+    if (rc) return rc;
+    const UNetTrainPlan t = unet_train_plan(desc);
+    if (workspace_bytes < t.bytes) return INR_EWORKSPACE;
+    return unet_train_forward(desc, t, conv_w, conv_b, bn_gamma, bn_beta, running_mean, running_var, momentum, input, logits,
+                              (float*)workspace, (hipStream_t)stream);
+}
+
+int inrfit_unet_train_backward(const InrUNetDesc* desc, const float* const* conv_w, const float* const* conv_b, const float* const* bn_gamma,
+                               const float* const* bn_beta, const float* input, const float* dlogits, float* grads, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    if (!desc || !conv_w || !conv_b || !bn_gamma || !bn_beta || !input || !dlogits || !grads || !workspace) return INR_EINVAL;
+    for (int i = 0; i < UNET_CONVS; ++i)
+        if (!conv_w[i] || !conv_b[i]) return INR_EINVAL;
+    for (int i = 0; i < UNET_CONVS - 1; ++i)
+        if (!bn_gamma[i] || !bn_beta[i]) return INR_EINVAL;
+    if (((uintptr_t)workspace) & 15) return INR_EINVAL;
+    const int rc = unet_train_desc_rc(desc);
+    if (rc) return rc;
+    const UNetTrainPlan t = unet_train_plan(desc);
+    if (workspace_bytes < t.bytes) return INR_EWORKSPACE;
+    return unet_train_backward(desc, t, conv_w, bn_gamma, input, dlogits, grads, (float*)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

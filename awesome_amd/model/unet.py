@@ -6,7 +6,9 @@ the reference's sub-module names and in its construction order, so a seeded cons
 `base_width` (1, 2, 4, 8, 8) going down and `base_width` (4, 2, 1, 1) coming up; the reference is base_width 64.
 
 In evaluation mode under no_grad - what the pre-fit loops and inference do with a frozen checkpoint - an fp32 network on the GPU runs
-in HIP (awesome_amd.unet, csrc/unet.h).  Everything else (training with batch statistics, autograd) is the plain torch modules."""
+in HIP (awesome_amd.unet, csrc/unet.h).  With `hip_training=True` a training step on one image - the forward pass with batch statistics
+and the whole backward pass - runs in HIP as well (csrc/unet_train.h), as an autograd function over the parameters.  Everything else
+(a batch of several images, inputs that require grad, other dtypes) is the plain torch modules."""
 from __future__ import annotations
 
 from typing import Optional
@@ -18,6 +20,7 @@ import torch.nn.functional as F
 from .cnn_net import _batcherize
 
 MIN_HIP_SIDE = 16     # four max-pools must leave a pixel
+MAX_HIP_SIDE = 4096
 
 
 class DoubleConv(nn.Module):
@@ -76,8 +79,9 @@ class OutConv(nn.Module):
 
 class UNet(nn.Module):
     def __init__(self, in_chn: Optional[int] = None, out_chn: int = 1, dtype: torch.dtype = torch.float32, decoding: bool = False, *,
-                 base_width: int = 64):
+                 base_width: int = 64, hip_training: bool = False):
         super().__init__()
+        self.hip_training = bool(hip_training)     # a switch, not a weight: no part of the state_dict
         if decoding:
             return
         b = int(base_width)
@@ -110,10 +114,8 @@ class UNet(nn.Module):
         x = self.up4(x, x1)
         return self.outc(x)
 
-    def hip_route(self, image, feature_encoding) -> bool:
-        """Evaluation mode, no autograd, fp32 on a GPU, at least 16 x 16 - and a shape the library holds kernels for."""
-        if self.training or torch.is_grad_enabled():
-            return False
+    def _hip_shape(self, image, feature_encoding) -> bool:
+        """fp32 tensors on one GPU, parameters and buffers included, at a shape the library holds kernels for."""
         if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in (image, feature_encoding)):
             return False
         if image.shape[-2] < MIN_HIP_SIDE or image.shape[-1] < MIN_HIP_SIDE or image.shape[-2:] != feature_encoding.shape[-2:]:
@@ -123,9 +125,35 @@ class UNet(nn.Module):
         return all(t.is_cuda and t.device == image.device and (t.dtype == torch.float32 or not t.is_floating_point())
                    for t in list(self.parameters()) + list(self.buffers()))
 
+    def hip_route(self, image, feature_encoding) -> bool:
+        """Evaluation mode, no autograd, fp32 on a GPU, at least 16 x 16 - and a shape the library holds kernels for."""
+        if self.training or torch.is_grad_enabled():
+            return False
+        return self._hip_shape(image, feature_encoding)
+
+    def hip_train_route(self, image, feature_encoding) -> bool:
+        """`hip_training`, train() with autograd on, one image whose tensors do not require grad, fp32 on one GPU, BatchNorms with
+        affine weights, running statistics, one eps and one float momentum, at least two values per channel at the bottom level."""
+        if not getattr(self, "hip_training", False) or not self.training or not torch.is_grad_enabled():
+            return False
+        if not self._hip_shape(image, feature_encoding) or image.device != feature_encoding.device:
+            return False
+        if image.requires_grad or feature_encoding.requires_grad or image.dim() != 4 or image.shape[0] != 1 or feature_encoding.shape[0] != 1:
+            return False
+        h, w = image.shape[-2:]
+        if (h >> 4) * (w >> 4) < 2 or h > MAX_HIP_SIDE or w > MAX_HIP_SIDE:
+            return False
+        if any(not p.is_contiguous() for p in self.parameters()):
+            return False
+        from ..unet import train_momentum
+        return train_momentum(self) is not None
+
     def forward(self, image, feature_encoding, *args, **kwargs):
         image, feature_encoding = _batcherize(image, feature_encoding)
         if self.hip_route(image, feature_encoding):
             from ..unet import unet_forward
             return unet_forward(self, image, feature_encoding)
+        if self.hip_train_route(image, feature_encoding):
+            from ..unet import unet_train_forward
+            return unet_train_forward(self, image, feature_encoding)
         return self.forward_torch(image, feature_encoding)

@@ -1,4 +1,5 @@
-"""The UNet backbone's evaluation pass on the device (include/inrfit.h: inrfit_unet_*, csrc/unet.h).
+"""The UNet backbone on the device (include/inrfit.h: inrfit_unet_*): the evaluation pass (csrc/unet.h) and, further down, the training
+step on one image (csrc/unet_train.h; `unet_train_forward`, an autograd function over the module's parameters).
 
 `unet_forward(net, image, features)` is what awesome_amd.model.UNet.forward does in eval() under no_grad with an fp32 network on the GPU:
 every Conv2d + BatchNorm2d pair is folded into one matrix on the device (inrfit_unet_pack), and the network runs from those matrices,
@@ -103,3 +104,119 @@ def unet_forward(net, image: Tensor, features: Optional[Tensor], strip_points: i
                                          ws.numel() * 4, _stream_ptr(dev))
             L.check(rc, "inrfit_unet_forward")
     return out
+
+
+# ---- the training step (include/inrfit.h: inrfit_unet_train_*, csrc/unet_train.h) ---------------------------------------------------------
+def train_momentum(net) -> Optional[float]:
+    """The BatchNorms' one float momentum; None where the training step does not apply (no affine weights or running statistics,
+    momentum=None or differing momenta / eps)."""
+    _, bns = _layers(net)
+    if any(not bn.affine or not bn.track_running_stats or bn.momentum is None or bn.running_mean is None for bn in bns):
+        return None
+    if len({float(bn.eps) for bn in bns}) != 1 or len({float(bn.momentum) for bn in bns}) != 1:
+        return None
+    m = float(bns[0].momentum)
+    return m if 0.0 <= m <= 1.0 else None
+
+
+def _train_workspace(net, desc, dev) -> Tensor:
+    """One workspace per (shape, device), cached on the module.  It carries the forward's maps to the backward, so it is never
+    reallocated between the two (not under L.POISON either, see _segnet.SegDriver.workspace); a forward that finds the cached one still
+    waiting for its backward takes a fresh one and leaves the old one to the graph that holds it."""
+    cache = net.__dict__.setdefault(_CACHE, {})
+    key = (desc.height, desc.width, desc.strip_points, str(dev))
+    if cache.get("train_key") != key or cache.get("train_busy"):
+        nbytes = int(L.load().inrfit_unet_train_workspace_bytes(C.byref(desc)))
+        if nbytes < 0:
+            L.check(nbytes, "inrfit_unet_train_workspace_bytes")
+        cache["train_ws"], cache["train_key"] = L.scratch(nbytes // 4, dtype=torch.float32, device=dev), key
+    cache["train_busy"] = True
+    return cache["train_ws"]
+
+
+def _train_tables(net, params):
+    """Pointer tables (conv_w, conv_b, gamma, beta) from the parameters in parameters() order: per convolution weight, bias, and the
+    BatchNorm's weight and bias; OutConv's weight and bias last."""
+    n = len(params) // 4
+    convs = list(range(0, 4 * n, 4)) + [4 * n]
+    return [_table([params[i] for i in convs]), _table([params[i + 1] for i in convs]),
+            _table([params[4 * i + 2] for i in range(n)]), _table([params[4 * i + 3] for i in range(n)])]
+
+
+class UNetTrainFunction(torch.autograd.Function):
+    """logits of `net` in training mode on x (1, in_chn, H, W); the parameters are inputs, so autograd hands their gradients on."""
+
+    @staticmethod
+    def forward(ctx, net, x, strip_points, *params):
+        dev = x.device
+        _, c, H, W = x.shape
+        desc = make_desc(net, H, W, strip_points)
+        lib = L.load()
+        momentum = train_momentum(net)
+        if momentum is None:
+            raise L.InrfitError("the UNet's BatchNorms must share one eps and one float momentum and carry affine weights and running statistics")
+        _, bns = _layers(net)
+        params = [p.detach() for p in params]
+        with torch.cuda.device(dev):
+            ws = _train_workspace(net, desc, dev)
+            tables = _train_tables(net, params)
+            means, variances = _table([bn.running_mean for bn in bns]), _table([bn.running_var for bn in bns])
+            logits = L.scratch(1, int(net.out_chn), H, W, dtype=torch.float32, device=dev)
+            rc = lib.inrfit_unet_train_forward(C.byref(desc), *[t[0] for t in tables], means[0], variances[0], momentum, x.data_ptr(),
+                                               logits.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
+            L.check(rc, "inrfit_unet_train_forward")
+            for bn in bns:
+                bn.num_batches_tracked.add_(1)
+        net.__dict__[_CACHE].pop("sig", None)      # the running statistics changed under the evaluation pass's packed weights
+        ws.generation = getattr(ws, "generation", 0) + 1     # which forward's maps the workspace holds
+        ctx.net, ctx.desc, ctx.x, ctx.ws, ctx.generation = net, desc, x, ws, ws.generation
+        ctx.save_for_backward(*params)
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        net, desc, x, ws = ctx.net, ctx.desc, ctx.x, ctx.ws
+        params = list(ctx.saved_tensors)
+        if ws.generation != ctx.generation:
+            raise L.InrfitError("the UNet's training workspace holds a later forward pass: backward through this graph ran after its "
+                                "workspace was handed on (a second backward of a retained graph)")
+        dev = x.device
+        lib = L.load()
+        dlogits = dlogits.contiguous().float()
+        with torch.cuda.device(dev):
+            n = int(lib.inrfit_unet_param_count(C.byref(desc)))
+            grads = L.scratch(n, dtype=torch.float32, device=dev)
+            tables = _train_tables(net, params)
+            rc = lib.inrfit_unet_train_backward(C.byref(desc), *[t[0] for t in tables], x.data_ptr(), dlogits.data_ptr(), grads.data_ptr(),
+                                                ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
+            L.check(rc, "inrfit_unet_train_backward")
+        cache = net.__dict__.get(_CACHE, {})
+        if cache.get("train_ws") is ws:
+            cache["train_busy"] = False
+        out, at = [], 0
+        for i, p in enumerate(params):
+            out.append(grads[at:at + p.numel()].view(p.shape) if ctx.needs_input_grad[3 + i] else None)
+            at += p.numel()
+        return (None, None, None, *out)
+
+
+def unet_train_forward(net, image: Tensor, features: Optional[Tensor], strip_points: int = 0) -> Tensor:
+    """logits (1, out_chn, H, W) of `net` in training mode (batch statistics; the running statistics and num_batches_tracked are updated)
+    on [image | features] (1, C, H, W), fp32 on the GPU, differentiable with respect to the parameters - forward and backward run in
+    HIP.  strip_points: pixels per strip of the column matrices (0: sized per layer)."""
+    x = image if features is None else torch.cat((image, features), dim=1)
+    if x.dim() == 3:
+        x = x[None]
+    x = _check_dev(x.detach(), "image")
+    if x.shape[0] != 1:
+        raise L.InrfitError(f"the UNet's training step takes one image per call, got a batch of {x.shape[0]}")
+    if x.shape[1] != net.in_chn:
+        raise L.InrfitError(f"the UNet takes {net.in_chn} input channels, got {x.shape[1]}")
+    params = list(net.parameters())
+    if len(params) != 74:
+        raise L.InrfitError("the UNet's training step needs the 18 convolutions with bias and affine BatchNorms, and OutConv")
+    for p in params:
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device):
+            raise L.InrfitError("the UNet's parameters must be contiguous float32 tensors on the input's GPU")
+    return UNetTrainFunction.apply(net, x, int(strip_points), *params)

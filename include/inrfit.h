@@ -660,6 +660,28 @@ int inrfit_unet_pack(const InrUNetDesc* desc, const float* const* conv_w, const 
 int inrfit_unet_forward(const InrUNetDesc* desc, const float* packed, const float* input, float* logits, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* ---- the UNet backbone's training step (csrc/unet_train.h) ---------------------------------------------------------------------------
+ * The same network on one image in training mode: every BatchNorm normalises with the mean and biased variance of its own input over
+ * the image's pixels, and the backward pass yields the gradient of every parameter.  Pointer tables as for inrfit_unet_pack (19
+ * convolutions, 18 BatchNorms: weight = gamma, bias = beta).  Strips of the column matrices are sized per layer from one budget;
+ * strip_points > 0 forces one size.  Every reduction has a fixed order: two calls give the same bits.  No host sync.
+ * Errors as for inrfit_unet_forward; in addition (height >> 4) * (width >> 4) < 2 is INR_EUNSUPPORTED (a single value per channel at
+ * the bottom level has no batch variance) and a momentum outside [0, 1] is INR_EINVAL. */
+/* number of parameters = floats of the gradient buffer, in torch's parameters() order: per convolution weight [cout][cin][3][3], bias,
+ * gamma, beta; then OutConv's weight and bias.  Does not depend on height, width or strip_points. */
+int64_t inrfit_unet_param_count(const InrUNetDesc* desc);
+int64_t inrfit_unet_train_workspace_bytes(const InrUNetDesc* desc);
+/* input [in_chn][height * width] -> logits [out_chn][height * width].  running_mean / running_var are updated in place as torch does:
+ * running = (1 - momentum) running + momentum stat, with the unbiased variance.  The workspace keeps what the backward needs. */
+int inrfit_unet_train_forward(const InrUNetDesc* desc, const float* const* conv_w, const float* const* conv_b, const float* const* bn_gamma,
+                              const float* const* bn_beta, float* const* running_mean, float* const* running_var, float momentum,
+                              const float* input, float* logits, void* workspace, int64_t workspace_bytes, void* stream);
+/* dlogits [out_chn][height * width] -> grads [inrfit_unet_param_count], every element written.  workspace: as inrfit_unet_train_forward
+ * left it for the same descriptor, weights and input. */
+int inrfit_unet_train_backward(const InrUNetDesc* desc, const float* const* conv_w, const float* const* conv_b, const float* const* bn_gamma,
+                               const float* const* bn_beta, const float* input, const float* dlogits, float* grads, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+
 const char* inrfit_strerror(int code);
 
 #pragma GCC visibility pop
