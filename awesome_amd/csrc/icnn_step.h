@@ -103,7 +103,9 @@ struct Cfg {
     static_assert(IMG_FLOATS % 4 == 0 && OFF_W % 4 == 0, "image must be float4-copyable / aligned");
     static constexpr int OFF_STA = IMG_FLOATS;
     static constexpr int OFF_STB = OFF_STA + SP * SA + 16;
-    static constexpr int LDS_FLOATS = OFF_STB + SP * SB + 16;
+    static constexpr int OFF_LIVE = OFF_STB + SP * SB + 16;      // [2][4] ints: "this wave has a non-zero dy", by chunk-iteration parity
+    static_assert(OFF_LIVE % 4 == 0, "the four words of one parity are read as one 16-byte vector");
+    static constexpr int LDS_FLOATS = OFF_LIVE + 8;
     static constexpr int LDS_BYTES = LDS_FLOATS * 4;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget exceeded");
 
@@ -383,6 +385,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     float* const woT = smem + G::OFF_WO;
     float* const stA = smem + G::OFF_STA;
     float* const stB = smem + G::OFF_STB;
+    int* const liveF = (int*)(smem + G::OFF_LIVE);
 
 #if INR_STAMPS
     const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
@@ -513,6 +516,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
     const unsigned long long rt_loop = __builtin_amdgcn_s_memrealtime();
     unsigned long long st_store = 0;   // the last dW tile store has been issued
 #endif
+    int par = 0;   // parity of this workgroup's chunk iteration (TRAIN: which half of liveF the iteration uses)
     for (int chunk = wg; chunk < n_chunks; chunk += a.wgs) {
 #if INR_STAMPS
         if (chunk == wg) {   // everything in front of the first MFMA has been issued; wait for the point, then stamp
@@ -715,17 +719,6 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             const int pl = wave * 16 + l15;  // this lane's row in the stages
             float* const sa = stA + pl * G::SA + 4 * g;
             float* const sb = stB + pl * G::SB + 4 * g;
-            // dz1 of tile t (in place over acc), dw_o accumulation, staging of dz1 (A) and z0ext (B)
-            auto dz1_tile = [&](int t) {
-                const f32x4 wot = wo[t];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float z1 = acc[t][r];
-                    dwo[t][r] = fmaf(dy, z1, dwo[t][r]);
-                    acc[t][r] = z1 > 0.f ? dy * wot[r] : 0.f;
-                }
-                *(f32x4*)(sa + 16 * t) = acc[t];
-            };
             if (HR > 0 && g == 0) {
                 f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -734,101 +727,31 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             }
             if (g < 3) *(f32x4*)(sb + HM) = z0[TM];
 
-            STAMP(3);
-            // ---- backward through layer 1 (MFMA, pipelined): dZ0 = dZ1 . W1 ----------------------------------------
-            // Operands swapped w.r.t. the forward product (same registers): the D tile comes out transposed - rows =
-            // this wave's points 4g+r, columns = hidden unit 16t + l15 - so every lane holds dz0 of ONE hidden unit per tile for
-            // four of the wave's own points: the layer-0 gradient dW_in = dZ0^T . (1, x) is per-lane FMAs, no staging, no barrier.
-            f32x4 dz0[TM];
-            f32x4 dzx = f32x4{0.f, 0.f, 0.f, 0.f};  // DX: same product for the columns of k-group TM (skip-path inputs)
-            float bqx[2] = {0.f, 0.f};
-            float dz0l[HRA];
+            // ---- chunks without a gradient ------------------------------------------------------------------------
+            // Where the sigmoid has saturated in fp32 (pr == 1.f: 1 - pr is +0), and on padding, masked and noneclass points, dy is
+            // exactly +-0, and so is every product of the backward pass: dz1, the backward product (accumulators that start at +0 and
+            // add +-0 stay +0), every FMA into a gradient sum and every k-step of the dW product return their accumulator bit for bit.
+            // A wave whose 16 dy are all +-0 therefore stages zeros and skips its backward block; a chunk in which no wave has a live dy
+            // skips the dW phase and the chunk-end barrier as well.  NaN is not zero: a NaN logit still reaches every gradient.
+            const bool live_dy = __builtin_amdgcn_ballot_w64(!(dy == 0.f)) != 0;
+            const bool live_w = DX || live_dy;   // DX: dcoords is written for every point, so that backward block stays dense
+            // one word per wave for the block's decision behind barrier 1, double-buffered by the iteration's parity: with the chunk-end
+            // barrier skipped a fast wave publishes chunk i + 1's word while a slow one still reads chunk i's; barrier 1 of chunk i + 1
+            // stands between those reads and the words of chunk i + 2
+            if (lane == 0) liveF[4 * par + wave] = live_dy ? 1 : 0;
+            f32x4 dz0[TM];   // dL/dz0pre, masked: unit (t, l15) at point 4g + r
+            if (live_w) {
+#include "icnn_step_bwd.h"
+            } else {
+                // the other waves may be live: they read these rows in the dW product.  dz0 = 0 feeds the layer-0 slices there.
 #pragma unroll
-            for (int u = 0; u < HRA; ++u) dz0l[u] = 0.f;
-            // k-steps over the hidden outputs.  The HR <= 4 leftover outputs share ONE k-step: dzl[] is the same in all four lane
-            // groups, so lane group u < HR carries leftover unit u (operand dzl[u], weight row HM + u), the others feed zeros.
-            constexpr int KS = 4 * TM + (HR > 0 ? 1 : 0);
-            float dzlg = 0.f;   // this lane group's leftover dz1
-#pragma unroll
-            for (int u = 0; u < HR; ++u) dzlg = g == u ? dzl[u] : dzlg;
-            float bq[2][TM];      // B operands (weights): row o of this k-step, columns 16t + l15
-            f32x4 wcq[2][HRA];    // leftover input columns W1[o][HM+u] at this lane's positions of a tile
-            auto b_row = [&](int ks) -> const float* {  // LDS row of the weight operand for k-step ks
-                const int tk = ks >> 2, r = ks & 3;
-                if (tk < TM) return wb + (16 * tk + 4 * g + r) * S;
-                return wb + (g < HR ? (HM + g) * S : 0);  // leftover output u lives in lane group u (others: A = 0)
-            };
-            // relu nets: the layer-0 mask is the sign of z0, unit 16t + l15 at point 4g + r, read back from this wave's own stage-B rows
-            // (written by this wave in the forward product; the b32 pattern of the dW product's bf reads, conflict-free).  One read
-            // behind every second product of the last eight k-steps: requested late, and no wait in front of an MFMA.
-            f32x4 zm[TM];
-            const float* const zrow = stB + (wave * 16 + 4 * g) * G::SB + l15;
-            constexpr int MK0 = KS > 8 ? KS - 8 : 0;   // first k-step that carries mask reads
-            auto mask_read = [&](int i) {
-                if (MASK_STAGED && i < 4 * TM) zm[i % TM][i / TM] = zrow[(i / TM) * G::SB + 16 * (i % TM)];
-            };
-            dz1_tile(0);
-            {
-                const float* br = b_row(0);
-#pragma unroll
-                for (int t = 0; t < TM; ++t) bq[0][t] = br[16 * t];
-                if (DX) bqx[0] = br[16 * TM];
-#pragma unroll
-                for (int u = 0; u < HR; ++u) wcq[0][u] = *(const f32x4*)(WcT + u * PT + 4 * g);
+                for (int t = 0; t < TM; ++t) {
+                    *(f32x4*)(sa + 16 * t) = f32x4{0.f, 0.f, 0.f, 0.f};
+                    dz0[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
             }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int tk = ks >> 2, r = ks & 3;
-                if (ks + 1 < KS) {
-                    const float* br = b_row(ks + 1);
-                    if (DX) bqx[(ks + 1) & 1] = br[16 * TM];
-                }
-                if (r == 0 && (tk + 1) * 4 < KS) {
-#pragma unroll
-                    for (int u = 0; u < HR; ++u) wcq[(tk + 1) & 1][u] = *(const f32x4*)(WcT + u * PT + 16 * (tk + 1) + 4 * g);
-                }
-                OPERAND_FENCE();
-                const float bop = tk < TM ? acc[tk < TM ? tk : 0][r] : dzlg;
-#pragma unroll
-                for (int t = 0; t < TM; ++t) {  // D = dZ0 with POINTS on the rows; next k-step's operand reads one per product
-                    dz0[t] = MFMA16(bop, bq[ks & 1][t], ks == 0 ? (f32x4{0.f, 0.f, 0.f, 0.f}) : dz0[t]);
-                    if (ks + 1 < KS) bq[(ks + 1) & 1][t] = b_row(ks + 1)[16 * t];
-                    if (ks >= MK0 && (((ks - MK0) * TM + t) & 1)) mask_read(((ks - MK0) * TM + t) >> 1);
-                    OPERAND_FENCE();
-                }
-                if (DX) dzx = MFMA16(bop, bqx[ks & 1], dzx);
-                MFMA_STEP_FENCE();
-                if (r == 1 && tk + 1 < TM) dz1_tile(tk + 1);  // next tile's dz1 + staging, in the shadow of the MFMAs
-                // leftover hidden inputs: dz0l[u] += W1[:, HM+u] . dz1 - this k-step's share (HR FMAs per MFMA block, not 4 HR
-                // in one gap every fourth block)
-#pragma unroll
-                for (int u = 0; u < HR; ++u) {
-                    if (tk < TM) dz0l[u] = fmaf(wcq[tk & 1][u][r], acc[tk < TM ? tk : 0][r], dz0l[u]);
-                    else if (g == 0) {   // the leftover outputs' share stays ONE chain in lane group 0 (output HM + 0, then HM + 1, ..)
-#pragma unroll
-                        for (int v = 0; v < HR; ++v) dz0l[u] = fmaf(wcq[tk & 1][u][v], dzl[v], dz0l[u]);
-                    }
-                }
-                MFMA_STEP_FENCE();
-            }
-            STAMP(4);
-            // Layer-0 derivative (relu nets: the mask zm read from stage B; encode nets: z0p, computed before the output layer); then the
-            // layer-0 gradient dW_in += dZ0^T . (1, x) over this wave's 16 points.  On the VALU: the product has NEXT useful columns, a
-            // matrix-pipe tile pads them to 16 (4 TM MFMAs for 6 MFMAs' worth of arithmetic).  dz0[t][r] holds point
-            // 4g + r of unit (t, l15); a 4 x 4 transpose between lane groups and tiles (four permlane swaps per four registers) hands
-            // lane group g the tiles 4q + g for the points of ALL lane groups, and every parameter is then one FMA chain in the matrix
-            // pipe's own order: the same bits as the MFMA form.  Nothing in front of the chunk-end barrier needs these sums, and the
-            // block is latency, not issue (six dependent chains): only the mask is applied here, the transpose and the chains run as 16
-            // slices behind the k-steps of the dW product below (icnn_step_l0.h), r-major, then k - every chain adds in the same order.
-#pragma unroll
-            for (int i = (KS - MK0) * TM / 2; i < 4 * TM; ++i) mask_read(i);   // (shapes with fewer than eight k-steps)
-#pragma unroll
-            for (int t = 0; t < TM; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (MASK_STAGED) dz0[t][r] = zm[t][r] > 0.f ? dz0[t][r] : 0.f;
-                    else dz0[t][r] *= dact0_f<ACT0>(z0p[t][r], a.act_omega);
-                }
+            __builtin_amdgcn_sched_barrier(0);
+
             auto swap32 = [](float& u, float& v) {   // lane groups 2, 3 of u <-> lane groups 0, 1 of v
                 const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(v), false, false);
                 u = __uint_as_float(s[0]);
@@ -842,77 +765,28 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
             const float* const xrow = stB + wave * 16 * G::SB;   // this wave's stage-B rows: one address per wave, LDS broadcasts
             float D[NQ][4];   // slices (r, .): D[q][k] = dz0 of unit (4q + g, l15) at point 4k + r
             float xpq[4][C];  // slice (r, k): coordinates of point 4k + r
-            // leftover rows of the layer-0 gradient (lane group 0, VALU)
-            float hx[C];  // DX: the contributions that live per point on lane l15: s_o dy + W_in[HM+u] dz0l[u]
-#pragma unroll
-            for (int c = 0; c < C; ++c) hx[c] = s_o[c] * dy;
-#pragma unroll
-            for (int u = 0; u < HR; ++u) {
-                const float d = sum_over_groups(dz0l[u]);
-                // position HM + u lives in lane group 0, k-step u (DX needs it in every lane group)
-                const float z0u = DX ? __shfl(z0[TM][u], l15) : z0[TM][u];
-                float dm;
-                if constexpr (ACT0 == INR_ACT_RELU) dm = z0u > 0.f ? d : 0.f;
-                else dm = d * dact0_f<ACT0>(z0lpre[u], a.act_omega);   // (used in lane group 0 only, where z0lpre[u] is unit HM + u)
-                if (DX) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) hx[c] = fmaf(WinT[c * 16 + u], dm, hx[c]);
-                }
-                if (g == 0) {
-                    dL0l[u][0] += dm;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) dL0l[u][1 + c] = fmaf(dm, x[c], dL0l[u][1 + c]);
-                }
-            }
-            if (DX) {
-                // dL/dx_c of point 4g + r: sum over hidden units (lanes l15, tiles t) of W_in[.,c] dz0, plus the skip
-                // path (column ext_pos(1+c) of the transposed product dzx), plus the per-point terms of that point.
-                float part[4][C];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < C; ++c) part[r][c] = (l15 == G::ext_pos(1 + c) - HM) ? dzx[r] : 0.f;
-#pragma unroll
-                for (int t = 0; t < TM; ++t)
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float w = WinE[c * PT + bcol(t, l15)];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) part[r][c] = fmaf(w, dz0[t][r], part[r][c]);
-                    }
-                // lane (g, l15 = r) keeps the value of point 4g + r: C coalesced stores per wave instead of 4C masked ones
-                float dxv[C];
-#pragma unroll
-                for (int c = 0; c < C; ++c) dxv[c] = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float v = sum_over_points(part[r][c]);   // in every lane of the lane group
-                        dxv[c] = l15 == r ? v : dxv[c];
-                    }
-                const int pp = chunk * SP + wave * 16 + 4 * g + l15;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float v = dxv[c] + __shfl(hx[c], 4 * g + l15);   // hx lives on lane (0, point)
-                    if (l15 < 4 && pp < (int)N) a.dcoords[((size_t)img * C + c) * N + pp] = v;
-                }
-            }
             STAMP(5);
             __syncthreads();
             STAMP(6);
 
             // ---- dW1ext += dZ1^T Z0ext over the 64 staged points (MFMA, pipelined); leftover rows on the VALU ------
+            // The four waves' words first, the first k-step's operands written next to them (hipcc sinks those reads into the branch all
+            // the same; pinned in front of it they measured no faster, profiles/NOTES.md).  No live wave: every dz1 row of the stage is
+            // zero, the phase and the chunk-end barrier are skipped (nothing reads a stage again before this wave writes the next
+            // chunk's rows).
+            auto stage_pt = [&](int it) { const int s = (it + wave) & 15; return 16 * (s >> 2) + (s & 3) + 4 * g; };
+            float af[2][RPW], bf[2][KG];
+            const int4 lf = *(const int4*)(liveF + 4 * par);
             {
-                auto stage_pt = [&](int it) { const int s = (it + wave) & 15; return 16 * (s >> 2) + (s & 3) + 4 * g; };
-                float af[2][RPW], bf[2][KG];
-                {
-                    const int pt = stage_pt(0);
+                const int pt = stage_pt(0);
 #pragma unroll
-                    for (int j = 0; j < RPW; ++j) af[0][j] = stA[pt * G::SA + arow + 16 * j];
+                for (int j = 0; j < RPW; ++j) af[0][j] = stA[pt * G::SA + arow + 16 * j];
 #pragma unroll
-                    for (int b = 0; b < KG; ++b) bf[0][b] = stB[pt * G::SB + 16 * b + l15];
-                }
+                for (int b = 0; b < KG; ++b) bf[0][b] = stB[pt * G::SB + 16 * b + l15];
+            }
+            const bool live_b = __builtin_amdgcn_readfirstlane(lf.x | lf.y | lf.z | lf.w) != 0;
+            par ^= 1;
+            if (live_b) {
 #pragma unroll
                 for (int it = 0; it < SP / 4; ++it) {
                     const int cur = it & 1, nx = cur ^ 1;
@@ -970,10 +844,11 @@ __global__ __launch_bounds__(WG_THREADS, 1) void icnn_step_kernel(const StepArgs
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
+                STAMP(7);
+                __syncthreads();
+                STAMP(8);
             }
-            STAMP(7);
-            __syncthreads();
-            STAMP(8);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
 #if INR_STAMPS
