@@ -2781,6 +2781,8 @@ int joint_step_run(B b, F f, const InrModelDesc* model, float* params, float* op
 
 }  // namespace
 
+#include "sequence.h"
+
 extern "C" {
 
 int64_t inrfit_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrGridDesc* grid) {

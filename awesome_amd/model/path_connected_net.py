@@ -303,8 +303,6 @@ class PathConnectedNet(nn.Module, PriorFitMixin):
         if wrapper_module is None:
             raise ValueError("Wrapper model must be provided for pretraining.")
         from .pretrainable_module import decompose_training_item
-        opts = dict(self._pretrain_defaults(), batch_size=1, dataloader_shuffle=False)
-        opts.update(kwargs)
         ds = agent.training_dataset
         device = torch.device(device)
         was, training_state = getattr(wrapper_module, "evaluate_prior", True), wrapper_module.training
@@ -321,31 +319,59 @@ class PathConnectedNet(nn.Module, PriorFitMixin):
                 g = pargs[0] if pargs[0].dim() == 4 else pargs[0][None]
                 coords.append(g[0].reshape(g.shape[1], -1).to(torch.float32))
                 unaries.append(un.reshape(-1).to(torch.float32))
+                frame_hw = tuple(g.shape[-2:])
         finally:
             wrapper_module.evaluate_prior = was
             wrapper_module.train(training_state)
         frame_coords, frame_unaries = torch.stack(coords), torch.stack(unaries)          # (T, C, HW), (T, HW)
-        T = frame_coords.shape[0]
+        return self.pretrain_frames(frame_coords, frame_unaries, frame_hw, agent=agent, **kwargs)
+
+    def pretrain_frames(self, frame_coords: torch.Tensor, frame_unaries: torch.Tensor, frame_hw: Tuple[int, int], agent=None, **kwargs):
+        """The stages of the spatio-temporal pretraining on the frames' tensors: frame_coords (T, C, H*W), frame_unaries (T, H*W) on
+        the device, frame_hw = (H, W); kwargs = the pretrain_args.  Two of them are this build's, both default False:
+        `reference_prefits` - the pre-fit stages are the reference's (:577-631): the identity pre-fit on create_normalized_grid((T, H, W))
+        in shuffled mini-batches of `batch_size` frames, the convex pre-fit on frames 0 and T - 1 only (off: both full-batch over every
+        frame of the frames' own grid); `sequence_device_loop` - the mini-batched pre-fit and the main epochs are one device call each
+        (learn_flow_identity / fit_sequence with device_loop).  With either, the frame orders are those of torch's DataLoader."""
+        opts = dict(self._pretrain_defaults(), batch_size=1, dataloader_shuffle=False, reference_prefits=False,
+                    sequence_device_loop=False)
+        opts.update(kwargs)
+        ref_prefits, dev_loop = bool(opts["reference_prefits"]), bool(opts["sequence_device_loop"])
+        T, device = frame_coords.shape[0], frame_coords.device
         whole = K.Grid.explicit(frame_coords.permute(1, 0, 2).reshape(frame_coords.shape[1], -1).contiguous())
         if opts.get("prefit_flow_net_identity", False):
-            self.learn_flow_identity(whole, lr=float(opts["prefit_flow_net_identity_lr"]),
-                                     weight_decay=float(opts["prefit_flow_net_identity_weight_decay"]),
-                                     max_iter=int(opts["prefit_flow_net_identity_num_epochs"]), zoo=opts.get("zoo"))
+            kw = dict(lr=float(opts["prefit_flow_net_identity_lr"]), weight_decay=float(opts["prefit_flow_net_identity_weight_decay"]),
+                      max_iter=int(opts["prefit_flow_net_identity_num_epochs"]), zoo=opts.get("zoo"))
+            if ref_prefits:   # the reference's stage (:587-601): the normalized (T, H, W) grid in shuffled mini-batches of frames
+                self.learn_flow_identity(self.create_normalized_grid((T, *frame_hw)).to(device), batch_size=int(opts["batch_size"]),
+                                         device_loop=dev_loop, **kw)
+            else:
+                self.learn_flow_identity(whole, **kw)
         if opts.get("prefit_convex_net", False):
-            self.learn_convex_net(whole, frame_unaries.reshape(1, -1), lr=float(opts["prefit_convex_net_lr"]),
-                                  weight_decay=float(opts["prefit_convex_net_weight_decay"]),
-                                  max_iter=int(opts["prefit_convex_net_num_epochs"]))
+            kw = dict(lr=float(opts["prefit_convex_net_lr"]), weight_decay=float(opts["prefit_convex_net_weight_decay"]),
+                      max_iter=int(opts["prefit_convex_net_num_epochs"]))
+            if ref_prefits:   # the reference's stage (:602-631): the first and the last frame stacked, nothing in between
+                ends = [0, T - 1]
+                two = K.Grid.explicit(frame_coords[ends].permute(1, 0, 2).reshape(frame_coords.shape[1], -1).contiguous())
+                self.learn_convex_net(two, frame_unaries[ends].reshape(1, -1).contiguous(), **kw)
+            else:
+                self.learn_convex_net(whole, frame_unaries.reshape(1, -1), **kw)
         from ..measures import criterion_targets, criterion_to_desc
         crit = opts.get("criterion")
         kind, wmode, _ = criterion_to_desc(crit, "targets") if crit is not None else ("se", "none", 1.0)
         frame_unaries = self._sequence_unaries(frame_unaries, opts, agent)
         # criterion_to_desc unwraps UnariesConversionLoss; its effect - binarised targets - is applied here (ADVICE r03)
         frame_unaries = criterion_targets(crit, frame_unaries).contiguous()
+        seq_kw = {}
+        if ref_prefits or dev_loop:   # the orders of the reference's loaders (a new DataLoader per epoch, :662-668)
+            seq_kw = dict(device_loop=dev_loop,
+                          orders=R.sequence_orders(T, min(int(opts["batch_size"]), T), int(opts["num_epochs"]),
+                                                   shuffle=bool(opts["dataloader_shuffle"]), one_loader=False))
         self.pretrain_epoch_losses = self.fit_sequence(frame_coords, frame_unaries, num_epochs=int(opts["num_epochs"]),
                                                        lr=float(opts["lr"]), flow_weight_decay=float(opts["flow_weight_decay"]),
                                                        batch_size=min(int(opts["batch_size"]), T),
                                                        dataloader_shuffle=bool(opts["dataloader_shuffle"]), loss=kind,
-                                                       weight_mode=wmode, optimizer=opts.get("optimizer", "adamax"))
+                                                       weight_mode=wmode, optimizer=opts.get("optimizer", "adamax"), **seq_kw)
         for m in self.flow_net.net.network.flows:
             if hasattr(m, "data_dep_init_done"):
                 m.data_dep_init_done.fill_(1.0)
@@ -479,11 +505,83 @@ class PathConnectedNet(nn.Module, PriorFitMixin):
             chans.append(grid.ts[0].expand(chans[0].numel()))
         return torch.stack(chans, 0)
 
+    @classmethod
+    def create_coordinate_grid(cls, grid_shape: Tuple[int, ...]) -> torch.Tensor:
+        """path_connected_net.py:252-272: (x, y[, z]) arange coordinates; a 3-D shape (T, H, W) gives (T, 3, H, W)."""
+        aranges = [torch.arange(n).float() for n in grid_shape]
+        grid = torch.stack(torch.meshgrid(*aranges, indexing="ij")[::-1])
+        if grid.dim() == 4:
+            grid = grid.swapaxes(0, 1)
+        return grid
+
+    @classmethod
+    def create_normalized_grid(cls, grid_shape: Tuple[int, ...]) -> torch.Tensor:
+        """path_connected_net.py:274-296: the coordinate grid MinMax-ed to [0, 1] per channel over dims (0, 2, 3), B x C x H x W."""
+        grid = cls.create_coordinate_grid(grid_shape)
+        if grid.dim() == 3:
+            grid = grid.unsqueeze(0)
+        lo, hi = grid.amin(dim=(0, 2, 3), keepdim=True), grid.amax(dim=(0, 2, 3), keepdim=True)
+        return (grid - lo) / (hi - lo) * (1.0 - 0.0) + 0.0
+
+    def _learn_flow_identity_batched(self, x: torch.Tensor, lr: float, weight_decay: float, max_iter: int, zoo, batch_size: int,
+                                     orders, device_loop: bool) -> torch.Tensor:
+        """The reference's own loop (path_connected_net.py:200-236): x (T, C, H, W) through DataLoader(TensorDataset(x, x), batch_size,
+        shuffle=True) - max_iter epochs of ceil(T / batch_size) Adamax steps, loss_hist[i] = the last batch's loss of epoch i.  Host
+        loop: one `inrfit_rnvp_fit_identity(steps=1)` per batch; device_loop: one `inrfit_rnvp_fit_identity_sequence` call."""
+        if x.dim() != 4:
+            x = x.unsqueeze(0)
+        T, Cc = x.shape[0], x.shape[1]
+        zoo_config = None
+        if zoo is not None:
+            from .zoo import tensor_hash
+            zoo_config = dict(lr=lr, weight_decay=weight_decay, max_iter=max_iter, criterion="SE(mean)", x_data=tensor_hash(x),
+                              batch_size=batch_size)
+            loaded, context = zoo.load_model_state("flow_identity", self.flow_net, config=zoo_config)
+            if loaded:
+                return context.get("loss_hist", None)
+        if orders is None:
+            orders = R.sequence_orders(T, batch_size, max_iter, shuffle=True, one_loader=True)
+        orders = torch.as_tensor(orders).to("cpu", torch.int64).reshape(max_iter, T)
+        dev = next(self.parameters()).device
+        frames = x.to(dev, torch.float32).reshape(T, Cc, -1).contiguous()
+        bs = min(int(batch_size), T)
+        gather = lambda ids: frames[ids].permute(1, 0, 2).reshape(Cc, -1).contiguous()  # noqa: E731
+        if max_iter > 0:
+            self._actnorm_init_if_needed(gather(orders[0][:bs].tolist()))   # ActNorm's first forward sees the first batch drawn
+        _, rspec, _, flow = self._ordered_params()
+        fp = self._flat(flow).to(dev)
+        if device_loop:
+            hist, _ = R.fit_identity_sequence(rspec, fp, frames, orders, bs, lr=lr, weight_decay=weight_decay)
+        else:
+            fopt = torch.zeros(1, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+            hist, k = torch.zeros(max_iter, dtype=torch.float32, device=dev), 0
+            for e in range(max_iter):
+                order = orders[e].tolist()
+                for i in range(0, T, bs):
+                    h, _ = R.fit_identity(rspec, fp, K.Grid.explicit(gather(order[i:i + bs])), steps=1, lr=lr, weight_decay=weight_decay,
+                                          flow_opt_state=fopt, step0=k)
+                    hist[e] = h[0, 0]
+                    k += 1
+        new = R.unpack_rnvp_params(rspec, fp[0])
+        own = dict(self.named_parameters())
+        with torch.no_grad():
+            for k_, v in new.items():
+                if not k_.startswith("linear."):
+                    own[k_].copy_(v.to(own[k_].device))
+        if zoo is not None:
+            zoo.save_model_state("flow_identity", self.flow_net, config=zoo_config, context=dict(loss_hist=hist.cpu()))
+        return hist
+
     def learn_flow_identity(self, grid: "K.Grid", lr: float = 1e-2, weight_decay: float = 1e-5, max_iter: int = 1000,
-                            zoo=None) -> torch.Tensor:
+                            zoo=None, batch_size: Optional[int] = None, orders=None, device_loop: bool = False) -> torch.Tensor:
         """path_connected_net.py:155-250 on the HIP path: Adamax on the flow_net alone towards flow_net(x) = x; updates this
         module's flow parameters in place and returns the loss history.  `zoo` (awesome_amd.model.zoo.Zoo): like the reference
-        (:177-194, :246-248) a stored flow for this architecture, grid and hyper-parameters is loaded instead of fitted."""
+        (:177-194, :246-248) a stored flow for this architecture, grid and hyper-parameters is loaded instead of fitted.
+        batch_size=None: full batch on `grid` (a K.Grid).  With a batch size, `grid` is the frame tensor x (T, C, H, W) and the loop is
+        the reference's mini-batch loop (`orders`: explicit (max_iter, T) frame orders instead of the DataLoader's; `device_loop`: all
+        epochs in one device call); the zoo key then gains batch_size and hashes x (:182-189)."""
+        if batch_size is not None:
+            return self._learn_flow_identity_batched(grid, lr, weight_decay, max_iter, zoo, int(batch_size), orders, device_loop)
         zoo_config = None
         if zoo is not None:
             from .zoo import tensor_hash
@@ -597,25 +695,51 @@ class PathConnectedNet(nn.Module, PriorFitMixin):
 
     def fit_sequence(self, frame_coords: torch.Tensor, frame_unaries: torch.Tensor, num_epochs: int = 2000, lr: float = 1e-3,
                      flow_weight_decay: float = 1e-5, batch_size: int = 1, dataloader_shuffle: bool = False, loss: str = "se",
-                     weight_mode: str = "none", optimizer: str = "adamax", plateau=None, generator=None):
+                     weight_mode: str = "none", optimizer: str = "adamax", plateau=None, generator=None, device_loop: bool = False,
+                     orders=None):
         """_non_prior_based_pretrain (path_connected_net.py:511-728): ONE network over all frames of a sequence, trained in
         mini-batches of `batch_size` frames - one optimizer step per batch on the mean loss of the batch's pixels, Adamax over the
         same parameter groups, enforce_convexity after every step, ReduceLROnPlateau stepped once per EPOCH with the mean of the
         batch losses (:700-713).  frame_coords (T, C, H*W), frame_unaries (T, H*W).  Every step is one `inrfit_pcn_fit(steps=1)`
         call that continues the optimizer state; the epoch loss and the learning rate live on the host.  With
         batch_size == T this is `fit_images` on the whole (x, y, t) grid (full batch), which is the fast form.
-        Updates this module's parameters in place; returns the list of epoch losses."""
+        Updates this module's parameters in place; returns the list of epoch losses.
+        `orders`: an explicit (num_epochs, T) integer tensor of frame ids, one permutation per epoch, instead of the orders drawn
+        here; ActNorm's data-dependent init then sees the first batch actually drawn.  `device_loop`: the whole fit is ONE
+        `inrfit_pcn_fit_sequence` call - the same steps on the same batches, the epoch mean and the scheduler on the device - and the
+        epoch losses are read back once at the end; a non-finite batch loss freezes the network there and raises the reference's
+        ValueError("Loss is nan or inf!") here."""
         T, dev = frame_coords.shape[0], frame_coords.device
-        self._actnorm_init_if_needed(frame_coords[:batch_size].permute(1, 0, 2).reshape(frame_coords.shape[1], -1))
+        first = slice(0, batch_size)   # orders drawn here: ActNorm initialises on frames 0 .. batch_size - 1, host and device loop alike
+        if orders is not None:
+            orders = torch.as_tensor(orders).to("cpu", torch.int64).reshape(num_epochs, T)
+            if num_epochs > 0:
+                first = orders[0][:batch_size].tolist()
+        elif device_loop:   # the orders the host loop below would draw, drawn up front
+            orders = torch.stack([torch.randperm(T, generator=generator) if dataloader_shuffle else torch.arange(T)
+                                  for _ in range(num_epochs)]) if num_epochs > 0 else torch.zeros(0, T, dtype=torch.int64)
+        self._actnorm_init_if_needed(frame_coords[first].permute(1, 0, 2).reshape(frame_coords.shape[1], -1))
         ispec, rspec, icnn, flow = self._ordered_params()
         ip, fp = self._flat(icnn).to(dev), self._flat(flow).to(dev)
+        pl = dict(patience=200, factor=0.5) if plateau is None else (plateau or None)
+        if device_loop:
+            res = R.pcn_fit_sequence(ispec, rspec, ip, fp, frame_coords, frame_unaries, orders, batch_size, lr=float(lr),
+                                     optimizer=optimizer, loss=loss, weight_mode=weight_mode, flow_weight_decay=flow_weight_decay,
+                                     plateau=pl)
+            back = torch.cat([res.epoch_loss, res.status.to(torch.float32)]).cpu()   # the one read-back of the fit
+            self.load_flat(ip[0], fp[0])
+            if float(back[-1]) != 0.0:
+                raise ValueError("Loss is nan or inf!")
+            return [float(v) for v in back[:-1]]
         iopt = K.new_opt_state(ispec, 1, dev)
         fopt = torch.zeros(1, 2 * rspec.n_params, dtype=torch.float32, device=dev)
-        pl = dict(patience=200, factor=0.5) if plateau is None else (plateau or None)
         cur_lr, best, num_bad = float(lr), float("inf"), 0
         epoch_losses, k = [], 0
-        for _ in range(num_epochs):
-            order = torch.randperm(T, generator=generator).tolist() if dataloader_shuffle else list(range(T))
+        for e in range(num_epochs):
+            if orders is not None:
+                order = orders[e].tolist()
+            else:
+                order = torch.randperm(T, generator=generator).tolist() if dataloader_shuffle else list(range(T))
             batches = [order[i:i + batch_size] for i in range(0, T, batch_size)]
             acc = torch.zeros((), device=dev)
             for b in batches:

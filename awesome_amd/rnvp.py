@@ -6,6 +6,9 @@
   pcn_loss_grad <- criterion(sigmoid(model(grid)), unaries).backward()  w.r.t. every parameter
   pcn_fit       <- the inner loop of _prior_based_pretrain          (:937-962, Adamax + param groups :922-929)
   actnorm_init  <- the data-dependent first forward of nf.flows.ActNorm
+  pcn_fit_sequence      <- the mini-batch epochs of _non_prior_based_pretrain (:634-713) in one device call
+  fit_identity_sequence <- the mini-batched learn_flow_identity (:200-236) in one device call
+  sequence_orders       <- the frame orders of the reference's DataLoaders
 
 The flow itself (MaskedAffineFlow / ActNorm / MLP) is normflows==1.7.3 code that is not part of the reference checkout:
 parity for this variant is UNPINNED; the flow is built as awesome/model/net_factory.py:70-114 builds it.
@@ -292,3 +295,110 @@ def pcn_fit(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, flow_params
                                  ws.numel() * 4, K._stream_ptr(dev))
     L.check(rc, "inrfit_pcn_fit")
     return PcnFitResult(ip, fp, icnn_opt_state, flow_opt_state, hist[:, :steps] if hist is not None else None, logits, status)
+
+
+# ---- sequence pretraining: all mini-batch epochs in one device call (include/inrfit.h, "sequence pretraining") --------------------
+def sequence_orders(T: int, batch_size: int, num_epochs: int, shuffle: bool = True, one_loader: bool = False) -> Tensor:
+    """Frame orders (num_epochs, T) from torch's own sampler: a DataLoader over range(T) with the caller's batch size, iterated on the
+    host under the global torch RNG - the same torch.manual_seed therefore gives the orders the reference's loaders draw.
+    one_loader: ONE loader iterated num_epochs times (learn_flow_identity, path_connected_net.py:200-220); else a new loader per epoch
+    (the main loop of _non_prior_based_pretrain, :662-668)."""
+    from torch.utils.data import DataLoader, TensorDataset
+    ds = TensorDataset(torch.arange(T))
+    new = lambda: DataLoader(ds, batch_size=int(batch_size), shuffle=bool(shuffle))  # noqa: E731
+    loader = new() if one_loader else None
+    rows = []
+    for _ in range(int(num_epochs)):
+        rows.append(torch.cat([b[0] for b in (loader if one_loader else new())]))
+    return torch.stack(rows).to(torch.int64) if rows else torch.zeros(0, T, dtype=torch.int64)
+
+
+def _orders_host(orders, num_epochs: int, T: int):
+    """(num_epochs, T) integer tensor -> the host int32 array the C ABI reads (validated there: a permutation per row)."""
+    o = torch.as_tensor(orders).detach().to("cpu", torch.int64).reshape(-1, T)
+    if o.shape[0] != num_epochs:
+        raise ValueError(f"orders must have one row of {T} frame ids per epoch ({num_epochs}), got {tuple(o.shape)}")
+    flat = o.reshape(-1).clamp(-2 ** 31, 2 ** 31 - 1).tolist()
+    return (C.c_int32 * max(len(flat), 1))(*flat)
+
+
+def _seq_ws(ispec: Optional[K.IcnnSpec], rspec: RnvpSpec, HW: int, T: int, batch_size: int, device) -> Tensor:
+    md = ispec.desc() if ispec is not None else None
+    rd = rspec.desc()
+    nbytes = L.load().inrfit_pcn_sequence_workspace_bytes(C.byref(md) if md is not None else None, C.byref(rd), int(HW), int(T),
+                                                         int(batch_size))
+    if nbytes < 0:
+        L.check(int(nbytes), "inrfit_pcn_sequence_workspace_bytes")
+    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=device)
+
+
+@dataclass
+class PcnSequenceResult:
+    icnn_params: Tensor
+    flow_params: Tensor
+    icnn_opt_state: Tensor
+    flow_opt_state: Tensor
+    epoch_loss: Tensor     # [num_epochs], on the device
+    status: Tensor
+
+
+def pcn_fit_sequence(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, flow_params: Tensor, frame_coords: Tensor,
+                     frame_targets: Tensor, orders, batch_size: int, lr: float = 1e-3, optimizer: str = "adamax", loss: str = "se",
+                     weight_mode: str = "none", ratio: float = 1.0, flow_weight_decay: float = 1e-5, betas=(0.9, 0.999),
+                     eps: float = 1e-8, plateau: Optional[dict] = None, icnn_opt_state: Optional[Tensor] = None,
+                     flow_opt_state: Optional[Tensor] = None) -> PcnSequenceResult:
+    """The mini-batch epochs of _non_prior_based_pretrain (path_connected_net.py:634-713) in ONE `inrfit_pcn_fit_sequence` call: per
+    batch of `orders[e]` what pcn_fit(steps=1) runs, per epoch the mean batch loss and ReduceLROnPlateau, nothing read back in
+    between.  icnn_params [1, P], flow_params [1, RP] (in place); frame_coords (T, C, HW), frame_targets (T, HW)."""
+    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
+    fc, ft = K._check_dev(frame_coords, "frame_coords"), K._check_dev(frame_targets, "frame_targets")
+    dev = ip.device
+    T, HW = int(fc.shape[0]), int(fc.shape[2])
+    num_epochs = int(torch.as_tensor(orders).reshape(-1, T).shape[0])
+    order = _orders_host(orders, num_epochs, T)
+    if icnn_opt_state is None:
+        icnn_opt_state = K.new_opt_state(ispec, 1, dev)
+    if flow_opt_state is None:
+        flow_opt_state = torch.zeros(1, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+    epoch_loss = L.scratch(max(num_epochs, 1), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    pl = plateau or {}
+    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 1,
+                      int(plateau is not None), int(pl.get("patience", 200)), float(pl.get("factor", 0.5)),
+                      float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)), float(pl.get("eps", 1e-8)), 0, 0, 0)
+    # the scheduler's numbers as the Python loop carries them (doubles)
+    schedule = (C.c_double * 5)(float(lr), float(pl.get("factor", 0.5)), float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)),
+                                float(pl.get("eps", 1e-8)))
+    ws = _seq_ws(ispec, rspec, HW, T, batch_size, dev)
+    md, rd, ld = ispec.desc(), rspec.desc(), K._loss_desc(loss, weight_mode, ratio, 0.0, 0.0)
+    rc = L.load().inrfit_pcn_fit_sequence(C.byref(md), C.byref(rd), ip.data_ptr(), fp.data_ptr(), icnn_opt_state.data_ptr(),
+                                          flow_opt_state.data_ptr(), fc.data_ptr(), ft.data_ptr(), order, T, HW, int(batch_size),
+                                          num_epochs, C.byref(ld), C.byref(od), schedule, float(flow_weight_decay), 0,
+                                          epoch_loss.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                          K._stream_ptr(dev))
+    L.check(rc, "inrfit_pcn_fit_sequence")
+    return PcnSequenceResult(ip, fp, icnn_opt_state, flow_opt_state, epoch_loss[:num_epochs], status)
+
+
+def fit_identity_sequence(rspec: RnvpSpec, flow_params: Tensor, frame_coords: Tensor, orders, batch_size: int, lr: float = 1e-2,
+                          weight_decay: float = 1e-5, optimizer: str = "adamax", betas=(0.9, 0.999), eps: float = 1e-8,
+                          flow_opt_state: Optional[Tensor] = None, step0: int = 0) -> Tuple[Tensor, Tensor]:
+    """The mini-batched learn_flow_identity (path_connected_net.py:200-236) in ONE `inrfit_rnvp_fit_identity_sequence` call, in place
+    on flow_params [1, RP]; frame_coords (T, C, HW).  Returns (loss_hist [num_epochs]: every epoch's LAST batch loss, opt_state)."""
+    fp, fc = K._check_dev(flow_params, "flow_params"), K._check_dev(frame_coords, "frame_coords")
+    dev = fp.device
+    T, HW = int(fc.shape[0]), int(fc.shape[2])
+    num_epochs = int(torch.as_tensor(orders).reshape(-1, T).shape[0])
+    order = _orders_host(orders, num_epochs, T)
+    if flow_opt_state is None:
+        flow_opt_state = torch.zeros(1, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+    hist = L.scratch(max(num_epochs, 1), dtype=torch.float32, device=dev)
+    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 0, 0,
+                      0, 0.0, 0.0, 0.0, 0.0)
+    ws = _seq_ws(None, rspec, HW, T, batch_size, dev)
+    rd = rspec.desc()
+    rc = L.load().inrfit_rnvp_fit_identity_sequence(C.byref(rd), fp.data_ptr(), flow_opt_state.data_ptr(), fc.data_ptr(), order, T,
+                                                    HW, int(batch_size), num_epochs, C.byref(od), int(step0), hist.data_ptr(),
+                                                    ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
+    L.check(rc, "inrfit_rnvp_fit_identity_sequence")
+    return hist[:num_epochs], flow_opt_state

@@ -334,6 +334,38 @@ int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* ic
                    float* loss_hist, float* final_logits, int32_t* status, void* workspace, int64_t workspace_bytes,
                    void* stream);
 
+/* ---- sequence pretraining: ONE network over the T frames of a sequence, trained in mini-batches of `batch_size` frames
+ * (PathConnectedNet._non_prior_based_pretrain, awesome/model/path_connected_net.py:634-713, and the mini-batched learn_flow_identity,
+ * :200-236), all epochs in one call: plain stream launches, nothing is read on the host in between.
+ * frame_coords [T][C][HW] (channel-planar per frame), frame_targets [T][HW]; order: HOST array [num_epochs][T] of int32 frame ids, one
+ * permutation of 0..T-1 per epoch (torch's DataLoader order).  It is validated on the host before the first launch - an entry outside
+ * [0, T) or a row that is no permutation: INR_EINVAL - and the ids reach the gather kernel as launch arguments, never through memory.
+ * Epoch e takes the batches order[e][0:b], order[e][b:2b], ... (b = min(batch_size, T); the last one may be shorter: its step runs on
+ * its own points and its mean loss is over them).  Per batch: the frames are gathered into a staging grid [C][b HW] and staging
+ * targets, then exactly what inrfit_pcn_fit(steps = 1, step0 = number of steps so far) launches for that explicit grid.  Per epoch:
+ * epoch_loss[e] (device, [num_epochs]) = sum over the batches, in batch order, of loss_b / n_batches in fp32, and - with opt->plateau -
+ * torch's ReduceLROnPlateau(mode 'min', relative threshold) stepped with it, comparisons and learning rate in double; the learning
+ * rate goes to the ICNN header ([2] and the slot of the next step), which both halves of the update read.  schedule: NULL, or a HOST
+ * array of 5 doubles {lr, factor, threshold, min_lr, eps} that replaces opt's float fields in the scheduler's arithmetic (a Python
+ * loop carries them as doubles: 0.1 is not a float), lr being the learning rate the fit starts with.  step0 must be 0 (else INR_EINVAL): a sequence fit is a cold
+ * fit - the header keeps the scheduler's `best` in fp32, so a continued call would not be the uninterrupted one; opt_state is left as
+ * inrfit_pcn_fit leaves it.  inrfit_rnvp_fit_identity_sequence has no scheduler and continues with step0 = steps taken so far.
+ * A non-finite batch loss freezes the network at the parameters in front of that step for the rest of the call and sets status[0].
+ * ICNN shapes: those with a fused kernel (the layer-by-layer shapes: INR_EUNSUPPORTED).  model = NULL in the size query: the
+ * workspace of inrfit_rnvp_fit_identity_sequence. */
+int64_t inrfit_pcn_sequence_workspace_bytes(const InrModelDesc* model, const InrRnvpDesc* rnvp, int64_t HW, int T, int batch_size);
+int inrfit_pcn_fit_sequence(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,
+                            float* icnn_opt_state, float* flow_opt_state, const float* frame_coords, const float* frame_targets,
+                            const int32_t* order, int T, int64_t HW, int batch_size, int num_epochs, const InrLossDesc* loss,
+                            const InrOptDesc* opt, const double* schedule, float flow_weight_decay, int step0, float* epoch_loss,
+                            int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same skeleton over inrfit_rnvp_fit_identity's step (flow parameters only, constant learning rate opt->lr, weight decay
+ * opt->weight_decay): learn_flow_identity over DataLoader(TensorDataset(x, x), batch_size, shuffle) with x = frame_coords.
+ * loss_hist [num_epochs] (device): the LAST batch's loss of every epoch, as the reference records it (:234). */
+int inrfit_rnvp_fit_identity_sequence(const InrRnvpDesc* rnvp, float* flow_params, float* flow_opt_state, const float* frame_coords,
+                                      const int32_t* order, int T, int64_t HW, int batch_size, int num_epochs, const InrOptDesc* opt,
+                                      int step0, float* loss_hist, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- joint segmentation + prior training: the composite losses on the device (row a12).
  * INR_JOINT_FBMS - FBMSJointLoss (awesome/measures/fbms_joint_loss.py:35-59).  output [batch][2][hw] = [seg, prior] probabilities (the
  * WrapperModule's output, image mode), target [batch][hw]:

@@ -411,11 +411,27 @@ def _run_sequence(cfg, A, parallel, rank, world, device, model_type, model_args,
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     cache, ious, error = {}, [], None
+    # pretrain_args.reference_prefits / sequence_device_loop (config/c4_sequence128x16_reference.yaml): the mini-batch form
+    minibatch, seq_losses = bool(pre.get("reference_prefits") or pre.get("sequence_device_loop")), []
     try:
         for i in mine:
             torch.manual_seed(int(cfg.get("seed", 42)) + i)
             model = model_type(**model_args).to(device)
             un = criterion_targets(criterion, dataset.batch([i]).to(device))
+            if minibatch:
+                # the reference's own loop: mini-batches of `batch_size` frames (PathConnectedNet.pretrain_frames)
+                T, S = dataset.frames, dataset.size
+                fc = grid.coords.reshape(3, T, S * S).permute(1, 0, 2).contiguous()
+                args = {k: v for k, v in pre.items() if k != "zoo"}
+                args.update(num_epochs=num_epochs, criterion=criterion, zoo=kw.get("zoo"))
+                raw = dataset.batch([i]).to(device)   # pretrain_frames applies the criterion's target rule itself, behind the pre-fits
+                model.pretrain_frames(fc, raw.reshape(T, S * S).contiguous(), (S, S), **args)
+                seq_losses.append([float(v) for v in model.pretrain_epoch_losses])
+                with torch.no_grad():
+                    logits = model(grid.coords.t().contiguous()).reshape(1, -1)
+                ious.append(float(A.miou(torch.sigmoid(logits), un)[0]))
+                cache[str(i)] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+                continue
             res = model.fit_images(grid, un, **kw)
             if int(res.status[0]) != 0:
                 raise ValueError(f"Loss is nan or inf! (sequence {i})")
@@ -452,6 +468,9 @@ def _run_sequence(cfg, A, parallel, rank, world, device, model_type, model_args,
         summary = {"images": len(dataset), "ranks": world, "epochs": num_epochs, "seconds": round(dt, 4),
                    "fits_per_s": round(len(dataset) / dt, 4), "ForegroundBinaryMIOU_vs_unaries": round(float(iou_all.mean()), 5),
                    "retries": [0] * len(dataset), "priors_saved": len(merged["cache"]), "output": out_dir}
+        if minibatch and seq_losses:   # (rank 0's first sequence)
+            summary["epoch_losses"] = [round(v, 6) for v in seq_losses[0]]
+            summary["sequence_device_loop"] = bool(pre.get("sequence_device_loop"))
         with open(os.path.join(out_dir, "summary.json"), "w") as f:
             json.dump(summary, f, indent=1)
         print(json.dumps(summary))
