@@ -171,6 +171,14 @@ EXPORTS = {
     "inrfit_rnvp_fit_identity_sequence": (C.c_int, [C.POINTER(InrRnvpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                                     C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(InrOptDesc), C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_minibatch_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrFlowDesc), C.c_int64, C.c_int]),
+    "inrfit_fit_minibatch": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.POINTER(C.c_int32), C.c_int64, C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_cdn_fit_minibatch": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrFlowDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
+                                           C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_fit": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p,
                              C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -2681,7 +2681,21 @@ int loss_grad_run(B b, F f, const InrModelDesc* model, const float* params, cons
 }
 
 // One optimizer step: the deformation's forward (all images) | per unit: the training pass, then (unless F::update owns it) the ICNN's
-// update | the deformation's backward seeded from dxd and its update.
+// update | the deformation's backward seeded from dxd and its update.  `step`: the 0-based number of the step (t = step + 1);
+// `packed`: the update of the step in front has left the deformation's packed parameters in this workspace.
+template <class B, class F>
+int fit_step(B& b, F& f, float* params, const TrainPass& a, const InrOptDesc* opt, int step, int hist_idx, bool packed, hipStream_t s) {
+    b.set_step(step, opt, step + 1, hist_idx);
+    f.forward(true, packed, s);
+    for (int k = 0; k < b.units(); ++k) {
+        if (const int rc = b.train(k, params, a, s)) return rc;
+        if constexpr (!update_merged<B, F>)
+            if (const int rc = b.update(k, s)) return rc;
+    }
+    f.update(b, true, s);
+    return INR_OK;
+}
+
 template <class B, class F>
 int fit_run(B b, F f, const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* targets,
             const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist, float* final_logits,
@@ -2703,15 +2717,8 @@ int fit_run(B b, F f, const InrModelDesc* model, float* params, float* opt_state
     a.dxd = f.dxd;
     a.freeze_input = opt->freeze_input;
     for (int it = 0; it < steps; ++it) {
-        b.set_step(step0 + it, opt, step0 + it + 1, it);
         a.logits = gate_logits && it == steps - 1 ? final_logits : nullptr;
-        f.forward(true, it > 0, s);
-        for (int k = 0; k < b.units(); ++k) {
-            if ((rc = b.train(k, params, a, s))) return rc;
-            if constexpr (!update_merged<B, F>)
-                if ((rc = b.update(k, s))) return rc;
-        }
-        f.update(b, true, s);
+        if ((rc = fit_step(b, f, params, a, opt, step0 + it, it, it > 0, s))) return rc;
     }
     if (hipGetLastError() != hipSuccess) return INR_ELAUNCH;
     if (final_logits && !gate_logits) {
@@ -2782,6 +2789,7 @@ int joint_step_run(B b, F f, const InrModelDesc* model, float* params, float* op
 }  // namespace
 
 #include "sequence.h"
+#include "minibatch.h"
 
 extern "C" {
 

@@ -120,6 +120,41 @@ class _IcnnModule(nn.Module, PriorFitMixin):
                 p.copy_(flat[off:off + n].reshape(p.shape))
                 off += n
 
+    def _load_fitted(self, flat: torch.Tensor) -> None:
+        """One fitted row back into the module's own parameters, in place."""
+        if hasattr(self, "unpack_flat"):   # a key layout of its own (the encoded MLPs, FCNet)
+            self.load_state_dict({k: v.to(flat.device) for k, v in self.unpack_flat(flat.detach().cpu()).items()})
+        else:
+            self.load_flat_parameters(flat)
+
+    def fit_minibatch(self, pixel_info: torch.Tensor, labels: torch.Tensor, num_epochs: int, number: int = None,
+                      batch_size: int = None, lr: float = 1e-2, loss: str = "se", class_weights=(1.0, 1.0),
+                      batch_index: torch.Tensor = None, counts=None, generator: torch.Generator = None, optimizer: str = "adam",
+                      state: dict = None):
+        """The teaser notebooks' pixel-minibatch loops as one device-resident call (awesome_amd/minibatch.py): pixel_info (N, C)
+        coordinates, labels (N,) likelihoods ((N, O) for several outputs).  `number`: per epoch `number` random background (label <
+        0.5) + `number` random foreground pixels, loss w_bg mean(bg) + w_fg mean(fg) with class_weights = (w_bg, w_fg) (convex.ipynb
+        cell 3, repeating.ipynb cell 4).  `batch_size`: DataLoader(batch_size, shuffle=True) steps with a short last batch, num_epochs
+        passes over the pixels, the plain mean (imageRepresentationTest.ipynb cell 6).  `batch_index` ([steps, batch] pixel numbers,
+        with `counts`) replaces the draw.  Sigmoid -> loss -> optimizer(lr) -> this model's projection, on the model's `fit_options`.
+        `state` (a dict this call fills: opt_state, epoch) continues an earlier call.  The parameters are updated in place; returns
+        the FitResult (loss_hist [1, steps])."""
+        from .. import minibatch as MB
+        dev = next(self.parameters()).device
+        pixel_info = pixel_info.to(device=dev, dtype=torch.float32)
+        labels = labels.to(device=dev, dtype=torch.float32)
+        targets = (labels.reshape(1, -1) if self.spec.n_out == 1 else labels.reshape(-1, self.spec.n_out).t()[None]).contiguous()
+        batch_index, counts, weights = MB.module_batches(labels, pixel_info.shape[0], num_epochs, number, batch_size, class_weights,
+                                                         batch_index, counts, generator)
+        state = {} if state is None else state
+        flat = self.flat_parameters()[None].contiguous().to(dev)
+        res = MB.fit_minibatch(self.spec, flat, pixel_info.t().contiguous(), targets, batch_index, counts, lr=lr, loss=loss,
+                               optimizer=optimizer, opt_state=state.get("opt_state"), step0=int(state.get("epoch", 0)), **weights,
+                               **dict(getattr(self, "fit_options", None) or dict(clamp=True)))
+        state["opt_state"], state["epoch"] = res.opt_state, int(state.get("epoch", 0)) + int(batch_index.shape[0])
+        self._load_fitted(flat[0])
+        return res
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B,C,H,W) -> (B,1,H,W)  or  (N,C) -> (N,1); the @pixelize contract of awesome/util/pixelize.py:7-53."""
         if not x.is_cuda:

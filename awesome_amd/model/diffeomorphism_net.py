@@ -544,6 +544,42 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
     def enforce_convexity(self) -> None:
         self.convex_net.enforce_convexity()
 
+    def fit_minibatch(self, pixel_info: torch.Tensor, labels: torch.Tensor, num_epochs: int, number: int = None,
+                      batch_size: int = None, lr: float = 1e-2, loss: str = "bce", class_weights=(1.0, 1.0),
+                      batch_index: torch.Tensor = None, counts=None, generator: torch.Generator = None,
+                      weight_decay_on_weight_g: float = 0.0, clamp: bool = False, state: dict = None):
+        """diffeo_convex.ipynb cells 9-11 as one device-resident call (awesome_amd/minibatch.py): per epoch `number` random background
+        (label < 0.5) + `number` random foreground pixels of pixel_info (N, 2) / labels (N,), loss w_bg BCE(bg) + w_fg BCE(fg) with
+        class_weights = (w_bg, w_fg), Adam(lr) over every parameter, no projection unless `clamp`.  `batch_size`, `batch_index` /
+        `counts` and `state` (opt_state, flow_opt_state, epoch) as on the ICNN modules.  The parameters are updated in place; returns
+        the CdnFitResult (loss_hist [1, steps]).  The fused composite only (a coupling-flow backbone over a fused ICNN shape)."""
+        from .. import minibatch as MB
+        if self._generic():
+            raise NotImplementedError("fit_minibatch runs the fused composite: a 'resnet' flow backbone or an ICNN shape without a fused "
+                                      "kernel has none")
+        ispec, fspec, icnn, flow = self._ordered_params()
+        dev = self.linear.weight.device
+        pixel_info = pixel_info.to(device=dev, dtype=torch.float32)
+        labels = labels.to(device=dev, dtype=torch.float32)
+        batch_index, counts, weights = MB.module_batches(labels, pixel_info.shape[0], num_epochs, number, batch_size, class_weights,
+                                                         batch_index, counts, generator)
+        state = {} if state is None else state
+        ip = torch.cat([p.detach().reshape(-1) for p in icnn]).to(torch.float32)[None].contiguous()
+        fp = torch.cat([p.detach().reshape(-1) for p in flow]).to(torch.float32)[None].contiguous()
+        res = MB.cdn_fit_minibatch(ispec, fspec, ip, fp, pixel_info.t().contiguous(), labels.reshape(1, -1).contiguous(), batch_index,
+                                   counts, lr=lr, loss=loss, weight_decay_on_weight_g=weight_decay_on_weight_g, clamp=clamp,
+                                   icnn_opt_state=state.get("opt_state"), flow_opt_state=state.get("flow_opt_state"),
+                                   step0=int(state.get("epoch", 0)), **weights)
+        state["opt_state"], state["flow_opt_state"] = res.icnn_opt_state, res.flow_opt_state
+        state["epoch"] = int(state.get("epoch", 0)) + int(batch_index.shape[0])
+        with torch.no_grad():
+            for flat, group in ((ip[0], icnn), (fp[0], flow)):
+                off = 0
+                for p in group:
+                    p.copy_(flat[off:off + p.numel()].reshape(p.shape))
+                    off += p.numel()
+        return res
+
     def fit_images(self, grid: "K.Grid", unaries: torch.Tensor, num_epochs: int = 2000, lr: float = 3e-3, loss: str = "bce",
                    weight_decay_on_weight_g: float = 5e-5, plateau=None, init_from_self: bool = True):
         """Fused device-resident form of `pretrain`'s inner loop (convex_diffeomorphism_net.py:405-430) for a batch of

@@ -33,6 +33,8 @@ class FCNet(nn.Module, PriorFitMixin):
     # -- PriorFitMixin engine (the same per-image loop as the ICNN priors, on this module's own key layout) -------------------
     _pretrain_defaults = _IcnnModule._pretrain_defaults
     _engine_fit = _IcnnModule._engine_fit
+    fit_minibatch = _IcnnModule.fit_minibatch   # in_type='xy' only (the coordinate network)
+    _load_fitted = _IcnnModule._load_fitted
 
     def _engine_pack(self, sd):
         keep = {k: v.detach().clone() for k, v in self.state_dict().items()}

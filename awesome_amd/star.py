@@ -159,15 +159,7 @@ def notebook_minibatches(labels: Tensor, steps: int, number: int = 500, generato
     """[steps, 2 * number] pixel numbers: per epoch `number` random background pixels (label > 0.5: cell 3's labels = 1 - likelihood)
     followed by `number` random foreground pixels, each a uniformly random subset without repetition - what
     `torch.randperm(n)[:number]` of cell 3 draws.  Random keys + top-k on the device, `chunk` epochs at a time."""
-    dev = labels.device
+    from .minibatch import draw_class_batches
     back = torch.nonzero(labels.reshape(-1) > 0.5).reshape(-1)
     fore = torch.nonzero(labels.reshape(-1) <= 0.5).reshape(-1)
-    if back.numel() < number or fore.numel() < number:
-        raise ValueError(f"need at least {number} pixels of each class (background {back.numel()}, foreground {fore.numel()})")
-    out = torch.empty(steps, 2 * number, dtype=torch.int32, device=dev)
-    for s0 in range(0, steps, chunk):
-        n = min(chunk, steps - s0)
-        for col, pool in ((0, back), (number, fore)):
-            keys = torch.rand(n, pool.numel(), device=dev, generator=generator)
-            out[s0:s0 + n, col:col + number] = pool[torch.topk(keys, number, dim=1).indices].to(torch.int32)
-    return out
+    return draw_class_batches(back, fore, steps, number, generator, chunk)

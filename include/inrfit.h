@@ -366,6 +366,36 @@ int inrfit_rnvp_fit_identity_sequence(const InrRnvpDesc* rnvp, float* flow_param
                                       const int32_t* order, int T, int64_t HW, int batch_size, int num_epochs, const InrOptDesc* opt,
                                       int step0, float* loss_hist, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- pixel-minibatch fits: a coordinate net trained on a fresh subset of a pixel pool at every optimizer step (the teaser notebooks'
+ * loops: convex.ipynb cell 3, repeating.ipynb cell 4, diffeo_convex.ipynb cells 9-11, the DataLoader loop of
+ * imageRepresentationTest.ipynb cell 6), all steps in one call: plain stream launches, nothing is read on the host in between and no
+ * call synchronises.
+ * pool_coords [C][n_pool] (channel-planar) and the index table are shared by all n_images nets; pool_targets [n_images][O][n_pool].
+ * index: DEVICE array [steps][batch] of int32 pixel numbers (drawn on the device; thousands per step, so they do not travel as launch
+ * arguments).  Every entry is clamped into [0, n_pool) before use.  counts: HOST array [steps], the points of step k (1..batch: the
+ * DataLoader's short last batch takes the first counts[k] entries of its row), or NULL: every step takes `batch`.
+ * Step k: the pool is gathered by index[k][0:counts[k]] into a staging grid [C][counts[k]] and staging targets
+ * [n_images][O][counts[k]]; the loss coefficients are taken on the staging targets; then exactly what inrfit_fit(steps = 1, step0 =
+ * step0 + k) - inrfit_cdn_fit for the flow variant - launches for that explicit grid: the same kernels, launch shapes and slab counts.
+ * The optimizer header (learning-rate double buffer, plateau state), the parameters and the "frozen" flag carry over a change of
+ * count, so a finite run ends bit for bit where the per-step host loop ends.  A non-finite batch loss freezes the net at the
+ * parameters in front of that step for the rest of the call and sets status (loss_hist[k] keeps the non-finite value): inrfit_fit's
+ * semantics inside one call.  loss_hist [n_images][steps] or NULL.  There are no final logits: inference over all pixels is
+ * inrfit_forward / inrfit_cdn_forward.  Shapes: everything inrfit_fit / inrfit_cdn_fit take.  The workspace holds the staging buffers
+ * and the step's own workspace for every count in 1..batch (a host computation; flow = NULL: inrfit_fit_minibatch's).
+ * Checks, every one before the first HIP call: INR_EINVAL (a null pointer, n_pool / batch / n_images <= 0, steps / step0 < 0, a count
+ * outside 1..batch, the optimizer, the loss, INR_LOSS_EXTERNAL), then INR_EUNSUPPORTED (the shape), then INR_EWORKSPACE. */
+int64_t inrfit_minibatch_workspace_bytes(const InrModelDesc* model, const InrFlowDesc* flow, int64_t batch, int n_images);
+int inrfit_fit_minibatch(const InrModelDesc* model, float* params, float* opt_state, const float* pool_coords,
+                         const float* pool_targets, int64_t n_pool, const int32_t* index, const int32_t* counts, int64_t batch,
+                         const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist,
+                         int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+int inrfit_cdn_fit_minibatch(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
+                             float* icnn_opt_state, float* flow_opt_state, const float* pool_coords, const float* pool_targets,
+                             int64_t n_pool, const int32_t* index, const int32_t* counts, int64_t batch, const InrLossDesc* loss,
+                             const InrOptDesc* opt, float weight_decay_on_weight_g, int n_images, int steps, int step0,
+                             float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- joint segmentation + prior training: the composite losses on the device (row a12).
  * INR_JOINT_FBMS - FBMSJointLoss (awesome/measures/fbms_joint_loss.py:35-59).  output [batch][2][hw] = [seg, prior] probabilities (the
  * WrapperModule's output, image mode), target [batch][hw]:
