@@ -97,6 +97,10 @@ class InrStarDesc(C.Structure):
     _fields_ = [("n_hidden", C.c_int32)]
 
 
+class InrSymDesc(C.Structure):   # inrfit_sym_*: the pose of the rotation / mirror-symmetry prior
+    _fields_ = [("symmetry_from_step", C.c_int32), ("r_eps", C.c_float)]
+
+
 class InrOptDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("clamp", C.c_int32), ("plateau", C.c_int32), ("plateau_patience", C.c_int32),
@@ -179,6 +183,20 @@ EXPORTS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
                                            C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_sym_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrGridDesc), C.c_int]),
+    "inrfit_sym_minibatch_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.c_int64, C.c_int]),
+    "inrfit_sym_forward": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrSymDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc),
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_sym_loss_grad": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrSymDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc),
+                                       C.c_void_p, C.POINTER(InrLossDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_sym_fit": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrSymDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(InrGridDesc), C.c_void_p, C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_int,
+                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_sym_fit_minibatch": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrSymDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
+                                           C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_fit": (C.c_int, [C.POINTER(InrModelDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p,
                              C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

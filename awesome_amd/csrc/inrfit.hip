@@ -2527,8 +2527,10 @@ struct NoDeform {   // ConvexNet / ConvexNextNet: the ICNN on the caller's grid
         bytes = b.bytes;
         return rc;
     }
+    int in_channels(const InrModelDesc* model) const { return model->in_features; }   // channels of the caller's grid
     int device() { return INR_OK; }
     void begin(hipStream_t) {}
+    void step(int) {}
     void forward(bool, bool, hipStream_t) {}
     void gradients(hipStream_t) {}
     template <class B>
@@ -2557,9 +2559,11 @@ struct FlowDeform : CdnWs {   // ConvexDiffeomorphismNet: the ICNN behind the we
         static_assert(B::fused, "the coupling flow runs over the fused backbone only");
         return check_deformed(*this, b, model, g, n, ws, ws_bytes);
     }
+    int in_channels(const InrModelDesc* model) const { return model->in_features; }
     int device() { return INR_OK; }
     // the flow's effective weights (mode 2): once per call; in the fit, the update kernel rebuilds them after every step
     void begin(hipStream_t s) { launch_flow_update(*this, flow, n_images, 2, params, nullptr, s); }
+    void step(int) {}
     void forward(bool, bool, hipStream_t s) { launch_flow_fwd(*this, grid, n_images, xd, s); }
     void gradients(hipStream_t s) {
         launch_flow_bwd(*this, flow, grid, n_images, s);
@@ -2602,8 +2606,10 @@ struct RnvpDeform : PcnWs {   // PathConnectedNet: the ICNN behind the normflows
     int check(B& b, const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool) {
         return check_deformed(*this, b, model, g, n, ws, ws_bytes);
     }
+    int in_channels(const InrModelDesc* model) const { return model->in_features; }
     int device() { return rnvp_set_lds(); }   // flow records of wide MLPs exceed the default 64 KB of dynamic LDS
     void begin(hipStream_t) {}
+    void step(int) {}
     // the parameters are packed into RE in front of the forward - except in the fit after its first step (`packed`), where the update
     // kernel has refreshed RE (update with fit = true)
     void forward(bool train, bool packed, hipStream_t s) { launch_rnvp_fwd(*this, params, grid, n_images, xd, train, s, false, packed); }
@@ -2686,6 +2692,7 @@ int loss_grad_run(B b, F f, const InrModelDesc* model, const float* params, cons
 template <class B, class F>
 int fit_step(B& b, F& f, float* params, const TrainPass& a, const InrOptDesc* opt, int step, int hist_idx, bool packed, hipStream_t s) {
     b.set_step(step, opt, step + 1, hist_idx);
+    f.step(step);   // (a deformation whose forward depends on the step number: PoseDeform's mirror switch)
     f.forward(true, packed, s);
     for (int k = 0; k < b.units(); ++k) {
         if (const int rc = b.train(k, params, a, s)) return rc;
@@ -2790,6 +2797,220 @@ int joint_step_run(B b, F f, const InrModelDesc* model, float* params, float* op
 
 #include "sequence.h"
 #include "minibatch.h"
+#include "sym.h"
+
+// ---- the rotation / mirror-symmetry prior: the pose as one more deformation (csrc/sym.h) ------------------------------------------------
+namespace {
+
+struct SymWs {
+    float *xd, *dxd, *part;
+    int blocks;          // blocks of the point kernels = rows of `part` per image
+    long long bytes;
+    InrGridDesc dgrid;   // the 3-channel feature grid handed to the backbone
+};
+
+static SymWs carve_sym(const InrGridDesc* grid, int n_images, void* base) {
+    SymWs w;
+    const long long N = grid->n_points;
+    w.blocks = (int)((N + 255) / 256);
+    char* b = (char*)base;
+    long long off = 0;
+    auto take = [&](long long bytes) { float* p = (float*)(b + off); off += align256(bytes); return p; };
+    w.xd = take((long long)n_images * 3 * N * 4);
+    w.dxd = take((long long)n_images * 3 * N * 4);
+    w.part = take((long long)n_images * w.blocks * SYM_POSE * 4);
+    w.dgrid = *grid;
+    w.dgrid.mode = INR_GRID_EXPLICIT;
+    w.dgrid.coords = w.xd;
+    w.dgrid.coords_image_stride = 3 * N;
+    w.bytes = off;
+    return w;
+}
+
+static bool sym_ok(const InrSymDesc* d) { return d && d->r_eps > 0.f && d->r_eps < INFINITY; }
+
+// RotationSymmetricNet: the network 3 -> h -> h -> 1 behind the pose (offset, orientation).  It reads a 2-channel grid and hands the
+// backbone 3 channels; its three parameters take the step FlowDeform's separate update launch takes: the learning rate and the
+// "frozen" flag from the ICNN headers, b.u's status and gscale.
+struct PoseDeform : SymWs {
+    static constexpr bool none = false;
+    const InrSymDesc* sym;
+    float *pose, *opt_state, *grads;     // [n][3]; opt_state [n][6]: fit; grads [n][3]: loss_grad
+    int mirror;                          // this pass mirrors (a fit sets it per step: step)
+    bool by_step;
+    const InrGridDesc* grid = nullptr;   // the caller's
+    int n_images = 0;
+    // mirror_flag < 0: a fit, the switch of sym->symmetry_from_step
+    PoseDeform(const InrSymDesc* d, const float* p, int mirror_flag, float* o = nullptr, float* g = nullptr)
+        : sym(d), pose(const_cast<float*>(p)), opt_state(o), grads(g), mirror(mirror_flag > 0), by_step(mirror_flag < 0) {}
+    bool desc_ok() const { return sym_ok(sym); }
+    int channels_ok(int c) const { return c == 3 ? INR_OK : INR_EUNSUPPORTED; }   // the backbone reads (u, v, r)
+    int in_channels(const InrModelDesc*) const { return 2; }
+    bool grid_rule(const InrGridDesc*) const { return true; }
+    void carve(const InrGridDesc* g, int n, void* ws) {
+        static_cast<SymWs&>(*this) = carve_sym(g, n, ws);
+        grid = g;
+        n_images = n;
+    }
+    template <class B>
+    int check(B& b, const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool) {
+        return check_deformed(*this, b, model, g, n, ws, ws_bytes);
+    }
+    int device() { return INR_OK; }
+    void begin(hipStream_t) {}
+    void step(int k) {
+        if (by_step) mirror = sym->symmetry_from_step >= 0 && k >= sym->symmetry_from_step;
+    }
+    dim3 point_grid() const { return dim3((unsigned)blocks, (unsigned)n_images); }
+    void forward(bool, bool, hipStream_t s) {
+        SymFwdArgs a{};
+        a.grid = *grid;
+        a.pose = pose;
+        a.xd = xd;
+        a.N = grid->n_points;
+        a.eps = sym->r_eps;
+        a.mirror = mirror;
+        hipLaunchKernelGGL(sym_fwd_kernel, point_grid(), dim3(256), 0, s, a);
+    }
+    void backward(hipStream_t s) {
+        SymBwdArgs a{};
+        a.grid = *grid;
+        a.pose = pose;
+        a.dxd = dxd;
+        a.part = part;
+        a.N = grid->n_points;
+        a.eps = sym->r_eps;
+        a.mirror = mirror;
+        a.blocks = blocks;
+        hipLaunchKernelGGL(sym_bwd_kernel, point_grid(), dim3(256), 0, s, a);
+    }
+    void gradients(hipStream_t s) {
+        backward(s);
+        SymUpdArgs u{};
+        u.grads_out = grads;
+        u.part = part;
+        u.blocks = blocks;
+        u.mode = 1;
+        hipLaunchKernelGGL(sym_update_kernel, dim3(n_images), dim3(64), 0, s, u);
+    }
+    // ICNN update (over the fused backbone: this owns it) | pose backward | pose update
+    template <class B>
+    void update(B& b, bool, hipStream_t s) {
+        const UpdArgs& bu = b.u;
+        if constexpr (B::fused) launch_icnn_update(b.e, bu, s);
+        backward(s);
+        SymUpdArgs u{};
+        u.pose = pose;
+        u.opt = opt_state;
+        u.part = part;
+        u.lr_hdr = b.hdr();   // the learning rate of THIS step sits in the ICNN header's [t & 1]
+        u.hdr_stride = b.opt_stride();
+        u.status = b.status();
+        u.gscale = bu.gscale;
+        u.blocks = blocks;
+        u.t = bu.t;
+        u.mode = 0;
+        bias_corrections(&bu.opt, bu.t, &u.bc1, &u.bc2_sqrt);
+        u.one_minus_b1 = (float)(1.0 - (double)bu.opt.beta1);
+        u.one_minus_b2 = (float)(1.0 - (double)bu.opt.beta2);
+        u.beta2 = bu.opt.beta2;
+        u.eps = bu.opt.eps;
+        u.wd = bu.opt.weight_decay;
+        hipLaunchKernelGGL(sym_update_kernel, dim3(n_images), dim3(64), 0, s, u);
+    }
+};
+
+// the shape of the network behind the pose: a fused kernel (C = 3) or the layer-by-layer ICNN form
+static bool sym_shape_ok(const InrModelDesc* model) {
+    return model && model->in_features == 3 && (find_entry(model) || pcn_wide_shape(model));
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t inrfit_sym_workspace_bytes(const InrModelDesc* model, const InrGridDesc* grid, int n_images) {
+    if (!sym_shape_ok(model)) return INR_EUNSUPPORTED;
+    if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
+    const long long own = carve_sym(grid, n_images, nullptr).bytes;
+    if (const KernelEntry* e = find_entry(model)) return own + align256(carve(e, grid->n_points, n_images, nullptr).bytes);
+    return own + carve_wide_behind(make_wide_map(model), grid->n_points, n_images, nullptr).bytes;
+}
+
+int64_t inrfit_sym_minibatch_workspace_bytes(const InrModelDesc* model, int64_t batch, int n_images) {
+    if (!sym_shape_ok(model)) return INR_EUNSUPPORTED;
+    if (!mb_sizes_ok(model, 1, batch, n_images, 0, 0)) return INR_EINVAL;
+    // the step's workspace is carved anew for every count: the largest over 1..batch (the layouts round per count)
+    long long own = 0;
+    InrGridDesc g = seq_grid(nullptr, 1);
+    for (long long c = 1; c <= batch; ++c) {
+        g.n_points = c;
+        const long long o = inrfit_sym_workspace_bytes(model, &g, n_images);
+        if (o < 0) return o;
+        if (o > own) own = o;
+    }
+    return mb_layout(2, 1, batch, n_images, nullptr).head_bytes + align256(own);
+}
+
+int inrfit_sym_forward(const InrModelDesc* model, const InrSymDesc* sym, const float* params, const float* pose_params,
+                       const InrGridDesc* grid, int n_images, int mirror, float* logits, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+    if (!params || !pose_params || !logits || !sym_ok(sym)) return INR_EINVAL;
+    const PoseDeform f(sym, pose_params, mirror ? 1 : 0);
+    if (pcn_wide_shape(model))
+        return forward_run(WideIcnn(), f, model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
+    return forward_run(FusedIcnn(), f, model, params, grid, n_images, logits, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_sym_loss_grad(const InrModelDesc* model, const InrSymDesc* sym, const float* params, const float* pose_params,
+                         const InrGridDesc* grid, const float* targets, const InrLossDesc* loss, int n_images, int mirror,
+                         float* loss_out, float* grads, float* pose_grads, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!params || !pose_params || !targets || !loss_out || !grads || !pose_grads || !sym_ok(sym)) return INR_EINVAL;
+    if (const int rc = check_loss(loss)) return rc;
+    if (loss->kind == INR_LOSS_EXTERNAL) return INR_EINVAL;
+    const PoseDeform f(sym, pose_params, mirror ? 1 : 0, nullptr, pose_grads);
+    if (pcn_wide_shape(model))
+        return loss_grad_run(WideIcnn(), f, model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes,
+                             (hipStream_t)stream);
+    return loss_grad_run(FusedIcnn(), f, model, params, grid, targets, loss, n_images, loss_out, grads, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+}
+
+int inrfit_sym_fit(const InrModelDesc* model, const InrSymDesc* sym, float* params, float* pose_params, float* opt_state,
+                   float* pose_opt_state, const InrGridDesc* grid, const float* targets, const InrLossDesc* loss, const InrOptDesc* opt,
+                   int n_images, int steps, int step0, float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes,
+                   void* stream) {
+    if (!params || !pose_params || !opt_state || !pose_opt_state || !targets || !opt || !sym_ok(sym) || steps < 0 || step0 < 0)
+        return INR_EINVAL;
+    if ((long long)steps + step0 > 0x7fffffffLL) return INR_EINVAL;
+    if (const int rc = check_fit(opt, loss, true)) return rc;   // the pose's optimizer step is Adam's only
+    const PoseDeform f(sym, pose_params, -1, pose_opt_state);
+    if (pcn_wide_shape(model))
+        return fit_run(WideIcnn(), f, model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, nullptr, status,
+                       workspace, workspace_bytes, (hipStream_t)stream);
+    return fit_run(FusedIcnn(), f, model, params, opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist, nullptr, status,
+                   workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_sym_fit_minibatch(const InrModelDesc* model, const InrSymDesc* sym, float* params, float* pose_params, float* opt_state,
+                             float* pose_opt_state, const float* pool_coords, const float* pool_targets, int64_t n_pool,
+                             const int32_t* index, const int32_t* counts, int64_t batch, const InrLossDesc* loss, const InrOptDesc* opt,
+                             int n_images, int steps, int step0, float* loss_hist, int32_t* status, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
+    if (!params || !pose_params || !opt_state || !pose_opt_state || !sym_ok(sym)) return INR_EINVAL;
+    if (const int rc = mb_check_args(model, pool_coords, pool_targets, n_pool, index, counts, batch, loss, opt, n_images, steps, step0,
+                                     true))   // the pose's optimizer step is Adam's only
+        return rc;
+    if (!sym_shape_ok(model)) return INR_EUNSUPPORTED;
+    const PoseDeform f(sym, pose_params, -1, pose_opt_state);
+    if (pcn_wide_shape(model))
+        return mb_run<WideIcnn>(f, model, params, opt_state, pool_coords, pool_targets, n_pool, index, counts, batch, loss, opt, n_images,
+                                steps, step0, loss_hist, status, workspace, workspace_bytes, (hipStream_t)stream);
+    return mb_run<FusedIcnn>(f, model, params, opt_state, pool_coords, pool_targets, n_pool, index, counts, batch, loss, opt, n_images,
+                             steps, step0, loss_hist, status, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
 
 extern "C" {
 

@@ -77,7 +77,7 @@ int mb_run(const F& f0, const InrModelDesc* model, float* params, float* opt_sta
            long long n_pool, const int32_t* index, const int32_t* counts, long long batch, const InrLossDesc* loss, const InrOptDesc* opt,
            int n_images, int steps, int step0, float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t s) {
     if (!workspace) return INR_EINVAL;
-    const int C = model->in_features, O = wide_desc_O(model);
+    const int C = f0.in_channels(model), O = wide_desc_O(model);   // the pool's channels are the deformation's, not the backbone's
     const MbLayout l = mb_layout(C, O, batch, n_images, workspace);
     if (workspace_bytes < l.head_bytes) return INR_EWORKSPACE;
     void* ws = (char*)workspace + l.head_bytes;

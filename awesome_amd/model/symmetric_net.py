@@ -11,14 +11,17 @@
 The pose (`offset`, `orientation`: three scalars) is a handful of elementwise device operations on the (N, 2) coordinates and stays
 in torch so that autograd differentiates it; the network behind it - 3 -> h -> h -> 1, all of the arithmetic - is the fused HIP step
 kernel with C = 3 input features, no skips, no clamp (the FCNet shape).  Its input gradient (`inrfit_backward`, dcoords) is what
-reaches the pose.  Two ways to train, both on the MI355X path:
+reaches the pose.  Three ways to train, all on the MI355X path:
 
-  * `forward` + autograd + any torch optimizer over `parameters()` (the notebook's loop, pose included);
+  * `fit_minibatch(pixel_info, labels, num_epochs, number=...)`: the notebook's loop of cell 3 - random pixels per epoch, ONE Adam
+    over pose and network, the prior switched on once training has started - as one device call (awesome_amd/symmetric.py,
+    csrc/sym.h: the pose as a deformation in front of the network, differentiated and stepped by its own kernels);
+  * `forward` + autograd + any torch optimizer over `parameters()` (the same loop, several launches and host round trips per epoch);
   * `fit(coords, targets, steps)`: the fused `inrfit_fit` of the network under the current, fixed pose - and
     `fit_alternating`, which interleaves it with pose steps through autograd.
 
-Only the kernels' widths are available (n_hidden in {32, 64, 130}; the notebook used 150).  The star-shape prior of the same folder
-is awesome_amd/model/star_net.py."""
+Every width up to 1024 runs: n_hidden <= 130 on the fused kernels (zero-padded to 32 / 64 / 130), wider ones - the notebook's 150 -
+layer by layer.  The star-shape prior of the same folder is awesome_amd/model/star_net.py."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -106,8 +109,54 @@ class RotationSymmetricNet(_EncodedMLP):
             return self.forward(flat, symmetry_prior).reshape(b, h, w, 1).permute(0, 3, 1, 2)
         if x.dim() != 2 or x.shape[1] != 2:
             raise ValueError(f"expected (N, 2) or (B, 2, H, W) coordinates, got {tuple(x.shape)}")
+        if not torch.is_grad_enabled():   # nothing to differentiate: pose and network in one call (inrfit_sym_forward)
+            from .. import symmetric as SY
+            sp = self.symmetry_prior if symmetry_prior is None else bool(symmetry_prior)
+            flat, pose = self.flat_parameters()[None].contiguous(), self._pose()[None].contiguous()
+            return SY.sym_forward(self.spec, flat, pose, K.Grid.explicit(x.t()), sp)[0][:, None]
         feats = self.features(x, symmetry_prior)
         return _IcnnFunction.apply(feats.t().contiguous(), self.spec, *self._param_list(False))[:, None]
+
+    def _pose(self) -> torch.Tensor:
+        """(3,) = offset[2] | orientation, float32 (a copy)."""
+        return torch.cat([self.offset.detach().reshape(-1), self.orientation.detach().reshape(-1)]).to(torch.float32)
+
+    # -- the notebook's loop in one device call ----------------------------------------------------------------------------------
+    def fit_minibatch(self, pixel_info: torch.Tensor, labels: torch.Tensor, num_epochs: int, number: int = None, lr: float = 1e-3,
+                      loss: str = "se", class_weights=(2.0, 1.0), symmetry_from_epoch: int = 502, batch_index: torch.Tensor = None,
+                      counts=None, generator: torch.Generator = None, state: dict = None):
+        """rotation_symmetric.ipynb cell 3 as one device-resident call (awesome_amd/symmetric.py): per epoch `number` random background
+        (label < 0.5) + `number` random foreground pixels of pixel_info (N, 2) / labels (N,), loss w_bg MSE(bg) + w_fg MSE(fg) with
+        class_weights = (w_bg, w_fg), one Adam(lr) over offset, orientation, W0, W1, W2.  The epoch with 0-based number e mirrors iff
+        e >= symmetry_from_epoch (negative: never); the notebook sets the flag after the forward of epoch 501, so 502 is its first.
+        `batch_index` ([steps, batch] pixel numbers, with `counts`) replaces the draw.  `state` (a dict this call fills: opt_state,
+        pose_opt_state, epoch) continues an earlier call.  The five tensors are updated in place; returns the SymFitResult
+        (loss_hist [1, steps])."""
+        from .. import minibatch as MB
+        from .. import symmetric as SY
+        dev = self.W2.weight.device
+        pixel_info = pixel_info.to(device=dev, dtype=torch.float32)
+        labels = labels.to(device=dev, dtype=torch.float32)
+        batch_index, counts, weights = MB.module_batches(labels, pixel_info.shape[0], num_epochs, number, None, class_weights,
+                                                         batch_index, counts, generator)
+        state = {} if state is None else state
+        flat, pose = self.flat_parameters()[None].contiguous().to(dev), self._pose()[None].contiguous().to(dev)
+        res = SY.sym_fit_minibatch(self.spec, flat, pose, pixel_info.t().contiguous(), labels.reshape(1, -1).contiguous(), batch_index,
+                                   counts, lr=lr, loss=loss, symmetry_from_step=int(symmetry_from_epoch),
+                                   opt_state=state.get("opt_state"), pose_opt_state=state.get("pose_opt_state"),
+                                   step0=int(state.get("epoch", 0)), **weights)
+        state["opt_state"], state["pose_opt_state"] = res.opt_state, res.pose_opt_state
+        state["epoch"] = int(state.get("epoch", 0)) + int(batch_index.shape[0])
+        if int(res.status[0]) != 0:
+            raise ValueError("Loss is nan or inf!")
+        sd = K.unpack_params(self.spec, flat[0])
+        with torch.no_grad():   # in place: an optimizer or a reference that holds these tensors keeps them
+            self.offset.copy_(pose[0, :2].reshape(1, 2))
+            self.orientation.copy_(pose[0, 2:])
+            for lin, key in ((self.W0, "input"), (self.W1, "skip.0.ln"), (self.W2, "out.ln")):
+                lin.weight.copy_(sd[key + ".weight"])
+                lin.bias.copy_(sd[key + ".bias"])
+        return res
 
     # -- fused fits ------------------------------------------------------------------------------------------------------------
     def fit(self, coords: torch.Tensor, targets: torch.Tensor, steps: int, lr: float = 1e-3, symmetry_prior: Optional[bool] = None,

@@ -396,6 +396,51 @@ int inrfit_cdn_fit_minibatch(const InrModelDesc* model, const InrFlowDesc* flow,
                              const InrOptDesc* opt, float weight_decay_on_weight_g, int n_images, int steps, int step0,
                              float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- rotation / mirror-symmetry prior of the teaser: pose and network trained together (csrc/sym.h) --------------------------------
+ * Replaces: `myNet` of notebooks/icml_teaser_code/rotation_symmetric/rotation_symmetric.ipynb cell 2 and the loop of cell 3 (one Adam
+ * over pose and network, the `symmetry_prior` switch flipped once training has started).  Per point, with the pose (o0, o1, th):
+ *     x' = x + o,  r = |x'|,  n = x' / (r_eps + r),  u = n0 cos th - n1 sin th,  v0 = n0 sin th + n1 cos th,  v = mirror ? |v0| : v0
+ * and the network `model` (in_features = 3: a fused kernel, or the layer-by-layer ICNN form such as the notebook's h = 150) on the
+ * features (u, v, r).  pose_params [n_images][3] = offset[2] | orientation; pose_opt_state [n_images][6] = exp_avg[3] | exp_avg_sq[3]
+ * (zero it before step 0); pose_grads [n_images][3].  grid: the caller's 2-channel grid, shared or per image as everywhere.
+ * The pose takes torch's single-tensor Adam step with the learning rate of the network's step (the ICNN header's double buffer) and
+ * opt->weight_decay; a step the network's update freezes (a non-finite loss) leaves the pose and its moments untouched.  A point with
+ * r == 0 contributes nothing to the pose's gradient (torch yields NaN there).  Every sum has a fixed order: two calls give the same
+ * bits.  Callers of the notebook's net pass opt->clamp = 0, opt->freeze_skips = 1 (an unconstrained MLP); the optimizer is Adam.
+ * symmetry_from_step: the step with 0-based number step0 + k mirrors iff it is >= symmetry_from_step (negative: never, 0: always).
+ * Checks, every one before the first HIP call: INR_EINVAL (a null pointer, r_eps not in (0, inf), steps / step0 < 0, the optimizer, the
+ * loss, INR_LOSS_EXTERNAL; the minibatch fit: inrfit_fit_minibatch's), then INR_EUNSUPPORTED (in_features != 3, no kernel and no
+ * layer-by-layer form of the shape), then INR_EINVAL (workspace pointer, grid, n_images), then INR_EWORKSPACE. */
+typedef struct InrSymDesc {
+    int32_t symmetry_from_step;
+    float r_eps;   /* the notebook: 0.001 */
+} InrSymDesc;
+
+int64_t inrfit_sym_workspace_bytes(const InrModelDesc* model, const InrGridDesc* grid, int n_images);
+/* staging buffers (2 coordinate planes, the targets) + inrfit_sym_workspace_bytes for every count in 1..batch */
+int64_t inrfit_sym_minibatch_workspace_bytes(const InrModelDesc* model, int64_t batch, int n_images);
+/* logits [n_images][n_points] of pose + network; mirror != 0: with the prior */
+int inrfit_sym_forward(const InrModelDesc* model, const InrSymDesc* sym, const float* params, const float* pose_params,
+                       const InrGridDesc* grid, int n_images, int mirror, float* logits, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+/* loss_out [n_images], grads [n_images][P] (inrfit_loss_grad's) and pose_grads [n_images][3] */
+int inrfit_sym_loss_grad(const InrModelDesc* model, const InrSymDesc* sym, const float* params, const float* pose_params,
+                         const InrGridDesc* grid, const float* targets, const InrLossDesc* loss, int n_images, int mirror,
+                         float* loss_out, float* grads, float* pose_grads, void* workspace, int64_t workspace_bytes, void* stream);
+/* inrfit_fit's full-batch steps with the pose beside the network (params, pose_params, both optimizer states IN PLACE); there are no
+ * final logits (inrfit_sym_forward) */
+int inrfit_sym_fit(const InrModelDesc* model, const InrSymDesc* sym, float* params, float* pose_params, float* opt_state,
+                   float* pose_opt_state, const InrGridDesc* grid, const float* targets, const InrLossDesc* loss, const InrOptDesc* opt,
+                   int n_images, int steps, int step0, float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+/* inrfit_fit_minibatch's contract (pool_coords [2][n_pool], the shared index table, counts, the index clamp, step0, loss_hist, status):
+ * step k launches exactly what inrfit_sym_fit(steps = 1, step0 = step0 + k) launches on the gathered rows. */
+int inrfit_sym_fit_minibatch(const InrModelDesc* model, const InrSymDesc* sym, float* params, float* pose_params, float* opt_state,
+                             float* pose_opt_state, const float* pool_coords, const float* pool_targets, int64_t n_pool,
+                             const int32_t* index, const int32_t* counts, int64_t batch, const InrLossDesc* loss, const InrOptDesc* opt,
+                             int n_images, int steps, int step0, float* loss_hist, int32_t* status, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
 /* ---- joint segmentation + prior training: the composite losses on the device (row a12).
  * INR_JOINT_FBMS - FBMSJointLoss (awesome/measures/fbms_joint_loss.py:35-59).  output [batch][2][hw] = [seg, prior] probabilities (the
  * WrapperModule's output, image mode), target [batch][hw]:
