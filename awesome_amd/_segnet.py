@@ -9,8 +9,9 @@ from typing import Callable, Optional
 import torch
 from torch import Tensor
 
+from . import _call as X
 from . import _lib as L
-from .icnn import _check_dev, _stream_ptr
+from .icnn import _check_dev
 
 
 def _plain_bce(c) -> bool:
@@ -42,13 +43,6 @@ class SegResult:
     status: Optional[Tensor] = None   # [1] int32: 1 = non-finite loss or gradient (grads zeroed)
 
 
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-_ws_cache = {}
-
-
 @dataclass(frozen=True)
 class SegDriver:
     """The host side of one inrfit_<name>_{param_count, workspace_bytes, forward, step} family."""
@@ -71,16 +65,13 @@ class SegDriver:
         return int(n)
 
     def workspace(self, desc, dev) -> Tensor:
-        """One workspace per (shape, device).  Unlike joint._workspace this cache must NOT reallocate under L.POISON:
-        step(reuse_forward=True) reads what forward left in the workspace, a fresh NaN-filled one would lose it."""
-        key = (self.name, self.ws_key(desc), str(dev))
-        ws = _ws_cache.get(key)
-        if ws is None:
-            nbytes = int(self._entry("workspace_bytes")(C.byref(desc)))
-            if nbytes < 0:
+        """One workspace per (shape, device), kept under L.POISON too (X.cached_workspace: it carries forward's state to step)."""
+        def nbytes():
+            n = int(self._entry("workspace_bytes")(C.byref(desc)))
+            if n < 0:
                 raise L.InrfitError(f"inrfit_{self.name}_workspace_bytes: unsupported {self.net_name} shape")
-            ws = _ws_cache[key] = L.scratch(nbytes // 4 + 64, dtype=torch.float32, device=dev)
-        return ws
+            return n
+        return X.cached_workspace((self.name, self.ws_key(desc)), nbytes, dev, refresh_under_poison=False)
 
     def _checked(self, desc, image, features, target, dseg=None):
         image, features = self.inputs(desc, image, features)
@@ -100,10 +91,7 @@ class SegDriver:
         logits = L.scratch(n, dtype=torch.float32, device=dev)
         seg = L.scratch(n, dtype=torch.float32, device=dev)
         loss = L.scratch(1, dtype=torch.float32, device=dev) if target is not None or self.loss_without_target else None
-        ws = self.workspace(desc, dev)
-        rc = self._entry("forward")(C.byref(desc), w, b, _ptr(image), _ptr(features), _ptr(target), logits.data_ptr(), seg.data_ptr(),
-                                    _ptr(loss), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
-        L.check(rc, f"inrfit_{self.name}_forward")
+        X.call(f"inrfit_{self.name}_forward", desc, w, b, image, features, target, logits, seg, loss, ws=self.workspace(desc, dev), device=dev)
         return SegResult(logits, seg, loss)
 
     def step(self, net, desc, image, features, target, dseg=None, reuse_forward=False, grads=None) -> SegResult:
@@ -121,9 +109,6 @@ class SegDriver:
             seg = L.scratch(n, dtype=torch.float32, device=dev)
         loss = L.scratch(1, dtype=torch.float32, device=dev)
         status = L.scratch(1, dtype=torch.int32, device=dev)      # (always written)
-        ws = self.workspace(desc, dev)
-        rc = self._entry("step")(C.byref(desc), w, b, _ptr(image), _ptr(features), target.data_ptr(), _ptr(dseg),
-                                 int(bool(reuse_forward)), _ptr(logits), _ptr(seg), loss.data_ptr(), grads.data_ptr(),
-                                 status.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
-        L.check(rc, f"inrfit_{self.name}_step")
+        X.call(f"inrfit_{self.name}_step", desc, w, b, image, features, target, dseg, int(bool(reuse_forward)), logits, seg, loss, grads,
+               status, ws=self.workspace(desc, dev), device=dev)
         return SegResult(logits, seg, loss, grads, status)

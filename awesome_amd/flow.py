@@ -7,12 +7,13 @@
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
+from functools import cached_property
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
 from . import icnn as K
 
@@ -28,7 +29,11 @@ class FlowSpec:
     def desc(self) -> L.InrFlowDesc:
         return L.InrFlowDesc(self.width, self.num_coupling, L.INR_FLOW_SIMPLE if self.backbone == "default" else L.INR_FLOW_NORMAL_BLOCK)
 
-    @property
+    @cached_property
+    def _desc(self) -> L.InrFlowDesc:      # for the wrappers, once per spec (never written to)
+        return self.desc()
+
+    @cached_property
     def n_params(self) -> int:
         return 6 + 2 * self.num_coupling * (3 * self.width + 3) + 4 * self.num_coupling
 
@@ -94,67 +99,56 @@ def merge_cdn_state_dict(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_flat: Tensor, 
 
 
 def _ws(ispec: Optional[K.IcnnSpec], fspec: FlowSpec, grid: K.Grid, n_images: int) -> Tensor:
-    md = ispec.desc() if ispec is not None else None
-    fd, gd = fspec.desc(), grid.desc()
-    nbytes = L.load().inrfit_cdn_workspace_bytes(C.byref(md) if md is not None else None, C.byref(fd), C.byref(gd), n_images)
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_cdn_workspace_bytes")
-    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=grid.device)
+    return X.workspace("inrfit_cdn_workspace_bytes", ispec._desc if ispec is not None else None, fspec._desc, grid._desc, n_images,
+                       device=grid.device)
+
+
+def _params(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_params: Tensor, flow_params: Tensor) -> Tuple[Tensor, Tensor, int]:
+    """icnn_params [n_images, P] and flow_params [n_images, FP], checked against their specs."""
+    K._check_spec(ispec)
+    ip = X.rows(icnn_params, "icnn_params", None, ispec.n_params)
+    return ip, X.rows(flow_params, "flow_params", ip.shape[0], fspec.n_params), ip.shape[0]
 
 
 def flow_forward(fspec: FlowSpec, flow_params: Tensor, grid: K.Grid) -> Tensor:
     """flow_params [n_images, FP] -> deformed coordinates [n_images, 2, N]."""
-    fp = K._check_dev(flow_params, "flow_params")
+    fp = X.rows(flow_params, "flow_params", None, fspec.n_params)
+    X.on_gpu(flow_params=fp)
     n = fp.shape[0]
     out = L.scratch(n, 2, grid.n_points, dtype=torch.float32, device=fp.device)
-    ws = _ws(None, fspec, grid, n)
-    fd, gd = fspec.desc(), grid.desc()
-    rc = L.load().inrfit_flow_forward(C.byref(fd), fp.data_ptr(), C.byref(gd), n, out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                      K._stream_ptr(fp.device))
-    L.check(rc, "inrfit_flow_forward")
+    X.call("inrfit_flow_forward", fspec._desc, fp, grid._desc, n, out, ws=_ws(None, fspec, grid, n), device=fp.device)
     return out
 
 
 def flow_backward(fspec: FlowSpec, flow_params: Tensor, grid: K.Grid, dout_coords: Tensor) -> Tensor:
     """Vector-Jacobian product of flow_forward: dout_coords [n_images, 2, N] -> gradients [n_images, FP] (forward recomputed)."""
-    fp = K._check_dev(flow_params, "flow_params")
-    d = K._check_dev(dout_coords, "dout_coords")
+    fp = X.rows(flow_params, "flow_params", None, fspec.n_params)
     n = fp.shape[0]
-    assert d.shape == (n, 2, grid.n_points), (d.shape, n, grid.n_points)
+    d = X.rows(dout_coords, "dout_coords", n, (2, grid.n_points))
+    X.on_gpu(flow_params=fp, dout_coords=d)
     grads = L.scratch_like(fp)
-    ws = _ws(None, fspec, grid, n)
-    fd, gd = fspec.desc(), grid.desc()
-    rc = L.load().inrfit_flow_backward(C.byref(fd), fp.data_ptr(), C.byref(gd), d.data_ptr(), n, grads.data_ptr(), ws.data_ptr(),
-                                       ws.numel() * 4, K._stream_ptr(fp.device))
-    L.check(rc, "inrfit_flow_backward")
+    X.call("inrfit_flow_backward", fspec._desc, fp, grid._desc, d, n, grads, ws=_ws(None, fspec, grid, n), device=fp.device)
     return grads
 
 
 def cdn_forward(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_params: Tensor, flow_params: Tensor, grid: K.Grid) -> Tensor:
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n = ip.shape[0]
+    ip, fp, n = _params(ispec, fspec, icnn_params, flow_params)
+    X.on_gpu(icnn_params=ip, flow_params=fp)
     logits = L.scratch(n, grid.n_points, dtype=torch.float32, device=ip.device)
-    ws = _ws(ispec, fspec, grid, n)
-    md, fd, gd = ispec.desc(), fspec.desc(), grid.desc()
-    rc = L.load().inrfit_cdn_forward(C.byref(md), C.byref(fd), ip.data_ptr(), fp.data_ptr(), C.byref(gd), n, logits.data_ptr(),
-                                     ws.data_ptr(), ws.numel() * 4, K._stream_ptr(ip.device))
-    L.check(rc, "inrfit_cdn_forward")
+    X.call("inrfit_cdn_forward", ispec._desc, fspec._desc, ip, fp, grid._desc, n, logits, ws=_ws(ispec, fspec, grid, n),
+           device=ip.device)
     return logits
 
 
 def cdn_loss_grad(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_params: Tensor, flow_params: Tensor, grid: K.Grid, targets: Tensor,
                   loss: str = "bce", weight_mode: str = "none", ratio: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n = ip.shape[0]
-    targets = K._check_dev(targets, "targets").reshape(n, -1)
+    ip, fp, n = _params(ispec, fspec, icnn_params, flow_params)
+    targets = K._per_point(ispec, targets, "targets", n, grid)
+    X.on_gpu(icnn_params=ip, flow_params=fp, targets=targets)
     lo = L.scratch(n, dtype=torch.float32, device=ip.device)
     gi, gf = L.scratch_like(ip), L.scratch_like(fp)
-    ws = _ws(ispec, fspec, grid, n)
-    md, fd, gd, ld = ispec.desc(), fspec.desc(), grid.desc(), K._loss_desc(loss, weight_mode, ratio, 0.0, 0.0)
-    rc = L.load().inrfit_cdn_loss_grad(C.byref(md), C.byref(fd), ip.data_ptr(), fp.data_ptr(), C.byref(gd), targets.data_ptr(),
-                                       C.byref(ld), n, lo.data_ptr(), gi.data_ptr(), gf.data_ptr(), ws.data_ptr(),
-                                       ws.numel() * 4, K._stream_ptr(ip.device))
-    L.check(rc, "inrfit_cdn_loss_grad")
+    X.call("inrfit_cdn_loss_grad", ispec._desc, fspec._desc, ip, fp, grid._desc, targets, X.loss_desc(loss, weight_mode, ratio, 0.0, 0.0),
+           n, lo, gi, gf, ws=_ws(ispec, fspec, grid, n), device=ip.device)
     return lo, gi, gf
 
 
@@ -177,27 +171,14 @@ def cdn_fit(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_params: Tensor, flow_params
             c_fg: float = 0.0, c_bg: float = 0.0) -> CdnFitResult:
     """ConvexDiffeomorphismNet.pretrain's inner loop on the device (defaults: Adam lr 3e-3, BCE, wd 5e-5 on weight_g, the ICNN's
     projection after every step; c_fg / c_bg: the coefficients of weight_mode 'explicit')."""
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n, dev = ip.shape[0], ip.device
-    targets = K._check_dev(targets, "targets").reshape(n, -1)
-    if icnn_opt_state is None:
-        icnn_opt_state = K.new_opt_state(ispec, n, dev)
-    if flow_opt_state is None:
-        flow_opt_state = torch.zeros(n, 2 * fspec.n_params, dtype=torch.float32, device=dev)
-    hist = L.scratch(n, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    logits = L.scratch(n, grid.n_points, dtype=torch.float32, device=dev) if want_logits else None
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    pl = plateau or {}
-    od = L.InrOptDesc(L.INR_OPT_ADAM, float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, int(bool(clamp)), int(plateau is not None),
-                      int(pl.get("patience", 200)), float(pl.get("factor", 0.5)), float(pl.get("threshold", 1e-4)),
-                      float(pl.get("min_lr", 0.0)), float(pl.get("eps", 1e-8)), 0, 0, int(bool(gate_logits)))
-    ws = _ws(ispec, fspec, grid, n)
-    md, fd, gd, ld = ispec.desc(), fspec.desc(), grid.desc(), K._loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_cdn_fit(C.byref(md), C.byref(fd), ip.data_ptr(), fp.data_ptr(), icnn_opt_state.data_ptr(),
-                                 flow_opt_state.data_ptr(), C.byref(gd), targets.data_ptr(), C.byref(ld), C.byref(od),
-                                 float(weight_decay_on_weight_g), n, int(steps), int(step0),
-                                 hist.data_ptr() if hist is not None else None,
-                                 logits.data_ptr() if logits is not None else None, status.data_ptr(), ws.data_ptr(),
-                                 ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_cdn_fit")
-    return CdnFitResult(ip, fp, icnn_opt_state, flow_opt_state, hist[:, :steps] if hist is not None else None, logits, status)
+    ip, fp, n = _params(ispec, fspec, icnn_params, flow_params)
+    dev = ip.device
+    targets = K._per_point(ispec, targets, "targets", n, grid)
+    icnn_opt_state, flow_opt_state = K._opt_states(ispec, fspec.n_params, n, dev, icnn_opt_state, flow_opt_state)
+    X.on_gpu(icnn_params=ip, flow_params=fp, targets=targets, icnn_opt_state=icnn_opt_state, flow_opt_state=flow_opt_state)
+    hist, logits, status = X.fit_outputs(n, steps, (n, grid.n_points), record_loss, want_logits, dev)
+    od = X.opt_desc("adam", lr, betas, eps, clamp=clamp, plateau=plateau, gate_logits=gate_logits)
+    X.call("inrfit_cdn_fit", ispec._desc, fspec._desc, ip, fp, icnn_opt_state, flow_opt_state, grid._desc, targets,
+           X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), od, float(weight_decay_on_weight_g), n, int(steps), int(step0), hist, logits,
+           status, ws=_ws(ispec, fspec, grid, n), device=dev)
+    return CdnFitResult(ip, fp, icnn_opt_state, flow_opt_state, X.trim(hist, steps), logits, status)

@@ -11,10 +11,12 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from functools import cached_property
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
 
 Tensor = torch.Tensor
@@ -56,8 +58,8 @@ class IcnnSpec:
         out += [("out.ln.weight", (o, h if self.n_layers > 0 else f)), ("out.ln.bias", (o,)), ("out.skp.weight", (o, c))]
         return out
 
-    @property
-    def n_params(self) -> int:
+    @cached_property
+    def n_params(self) -> int:          # (cached: every wrapper checks its tensors' widths against it, on every call)
         n = 0
         for _, shp in self.keys_shapes():
             m = 1
@@ -76,8 +78,17 @@ class IcnnSpec:
         return self.supported() and not self.general and self.n_hidden <= 130 and self.n_layers <= 2
 
     def supported(self) -> bool:
-        d = self.desc()
-        return bool(L.load().inrfit_supported(C.byref(d)))
+        return self._supported
+
+    # what every call of every wrapper reads, once per spec: the library's answer for this shape, and the descriptor the wrappers
+    # pass by reference (never written to; desc() hands callers a fresh one)
+    @cached_property
+    def _supported(self) -> bool:
+        return bool(L.load().inrfit_supported(C.byref(self._desc)))
+
+    @cached_property
+    def _desc(self) -> L.InrModelDesc:
+        return self.desc()
 
 
 # ConvexNet (convex_net.py:10-40) uses different key names for the same L=1 network
@@ -173,22 +184,20 @@ class Grid:
     def device(self):
         return (self.xs if self.xs is not None else self.coords).device
 
+    @cached_property
+    def _desc(self) -> L.InrGridDesc:
+        """desc() for the wrappers, once per Grid: its fields are set in __init__ and it keeps its tensors alive."""
+        return self.desc()
+
     def desc(self) -> L.InrGridDesc:
         p = lambda t: (t.data_ptr() if t is not None else None)
         return L.InrGridDesc(self.mode, self.width, self.height, self.n_points, p(self.xs), p(self.ys), p(self.ts),
                              p(self.coords), self.image_stride)
 
 
-def _stream_ptr(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _check_dev(t: Tensor, name: str) -> Tensor:
-    if not t.is_cuda:
-        raise L.InrfitError(f"{name} must live on the GPU (awesome_amd has no CPU path)")
-    if t.dtype != torch.float32:
-        raise L.InrfitError(f"{name} must be float32")
-    return t.contiguous()
+_stream_ptr = X._stream_ptr
+_check_dev = X.on_device     # (dtype and device only; the wrappers check shapes with X.rows / X.flat)
+_loss_desc = X.loss_desc
 
 
 def _check_spec(spec: IcnnSpec) -> None:
@@ -204,11 +213,19 @@ def _out_shape(spec: IcnnSpec, n_images: int, n_points: int) -> Tuple[int, ...]:
 
 
 def _workspace(spec: IcnnSpec, grid: Grid, n_images: int) -> Tensor:
-    md, gd = spec.desc(), grid.desc()
-    nbytes = L.load().inrfit_workspace_bytes(C.byref(md), C.byref(gd), n_images)
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_workspace_bytes")
-    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=grid.device)
+    return X.workspace("inrfit_workspace_bytes", spec._desc, grid._desc, n_images, device=grid.device)
+
+
+def _params(spec: IcnnSpec, params: Tensor) -> Tuple[Tensor, int]:
+    """params [n_images, P] (one image: [P]) -> the checked rows and n_images."""
+    _check_spec(spec)
+    params = X.rows(params[None] if params.dim() == 1 else params, "params", None, spec.n_params)
+    return params, params.shape[0]
+
+
+def _per_point(spec: IcnnSpec, t: Tensor, name: str, n_images: int, grid: Grid) -> Tensor:
+    """targets / dlogits [n_images, N] ([n_images, O, N] for n_out > 1) -> [n_images, O * N]."""
+    return X.flat(t, name, n_images * spec.n_out * grid.n_points).reshape(n_images, -1)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -216,82 +233,51 @@ def _workspace(spec: IcnnSpec, grid: Grid, n_images: int) -> Tensor:
 # ----------------------------------------------------------------------------------------------------------------------
 def forward(spec: IcnnSpec, params: Tensor, grid: Grid) -> Tensor:
     """params [n_images, P] -> logits [n_images, N] ([n_images, O, N] for n_out = O > 1)."""
-    _check_spec(spec)
-    params = _check_dev(params, "params")
-    if params.dim() == 1:
-        params = params[None]
-    n_images = params.shape[0]
-    assert params.shape[1] == spec.n_params, (params.shape, spec.n_params)
+    params, n_images = _params(spec, params)
+    X.on_gpu(params=params)
     logits = L.scratch(*_out_shape(spec, n_images, grid.n_points), dtype=torch.float32, device=params.device)
-    md, gd = spec.desc(), grid.desc()
-    ws = _workspace(spec, grid, n_images)
-    rc = L.load().inrfit_forward(C.byref(md), params.data_ptr(), C.byref(gd), n_images, logits.data_ptr(), ws.data_ptr(),
-                                 ws.numel() * 4, _stream_ptr(params.device))
-    L.check(rc, "inrfit_forward")
+    X.call("inrfit_forward", spec._desc, params, grid._desc, n_images, logits, ws=_workspace(spec, grid, n_images),
+           device=params.device)
     return logits
-
-
-def _loss_desc(kind: str, weight_mode: str, ratio: float, c_fg: float, c_bg: float) -> L.InrLossDesc:
-    return L.InrLossDesc(L.LOSS_KINDS[kind], L.WEIGHT_MODES[weight_mode], float(ratio), float(c_fg), float(c_bg))
 
 
 def loss_grad(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, loss: str = "se", weight_mode: str = "none",
               ratio: float = 1.0, c_fg: float = 0.0, c_bg: float = 0.0) -> Tuple[Tensor, Tensor]:
     """-> (loss [n_images], grads [n_images, P]) of the data term at `params`.  targets [n_images, N] ([n_images, O, N] for n_out > 1;
     the data term is then averaged over O x N like torch's MSELoss on (N, O))."""
-    _check_spec(spec)
-    params = _check_dev(params, "params")
-    targets = _check_dev(targets, "targets")
-    if params.dim() == 1:
-        params = params[None]
-    n_images = params.shape[0]
-    targets = targets.reshape(n_images, -1)
-    assert targets.shape[1] == spec.n_out * grid.n_points
+    params, n_images = _params(spec, params)
+    targets = _per_point(spec, targets, "targets", n_images, grid)
+    X.on_gpu(params=params, targets=targets)
     ws = _workspace(spec, grid, n_images)
     loss_out = L.scratch(n_images, dtype=torch.float32, device=params.device)
     grads = L.scratch_like(params)
-    md, gd, ld = spec.desc(), grid.desc(), _loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_loss_grad(C.byref(md), params.data_ptr(), C.byref(gd), targets.data_ptr(), C.byref(ld), n_images,
-                                   loss_out.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                   _stream_ptr(params.device))
-    L.check(rc, "inrfit_loss_grad")
+    X.call("inrfit_loss_grad", spec._desc, params, grid._desc, targets, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), n_images,
+           loss_out, grads, ws=ws, device=params.device)
     return loss_out, grads
 
 
 def backward(spec: IcnnSpec, params: Tensor, grid: Grid, dlogits: Tensor, want_dcoords: bool = False):
     """Vector-Jacobian product: grads [n_images, P] = dlogits [n_images, N] . d logits / d params (forward recomputed).
     want_dcoords: also return dL/dcoords [n_images, C, N]."""
-    _check_spec(spec)
-    params = _check_dev(params, "params")
-    dlogits = _check_dev(dlogits, "dlogits")
-    if params.dim() == 1:
-        params = params[None]
-    n_images = params.shape[0]
-    dlogits = dlogits.reshape(n_images, -1)   # ([n_images, O, N] for n_out > 1)
-    assert dlogits.shape[1] == spec.n_out * grid.n_points
+    params, n_images = _params(spec, params)
+    dlogits = _per_point(spec, dlogits, "dlogits", n_images, grid)
+    X.on_gpu(params=params, dlogits=dlogits)
     ws = _workspace(spec, grid, n_images)
     grads = L.scratch_like(params)
     dco = L.scratch(n_images, spec.in_features, grid.n_points, dtype=torch.float32, device=params.device) if want_dcoords else None
-    md, gd = spec.desc(), grid.desc()
-    rc = L.load().inrfit_backward(C.byref(md), params.data_ptr(), C.byref(gd), dlogits.data_ptr(), n_images,
-                                  grads.data_ptr(), dco.data_ptr() if dco is not None else None, ws.data_ptr(),
-                                  ws.numel() * 4, _stream_ptr(params.device))
-    L.check(rc, "inrfit_backward")
+    X.call("inrfit_backward", spec._desc, params, grid._desc, dlogits, n_images, grads, dco, ws=ws, device=params.device)
     return (grads, dco) if want_dcoords else grads
 
 
 def step_only(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, iters: int, loss: str = "se",
               weight_mode: str = "none", workspace: Optional[Tensor] = None) -> Tensor:
     """Measurement hook: launch only the fused step kernel `iters` times on the current stream."""
-    _check_spec(spec)
-    params = _check_dev(params, "params")
-    targets = _check_dev(targets, "targets")
-    n_images = params.shape[0]
+    params, n_images = _params(spec, params)
+    targets = _per_point(spec, targets, "targets", n_images, grid)
+    X.on_gpu(params=params, targets=targets)
     ws = workspace if workspace is not None else _workspace(spec, grid, n_images)
-    md, gd, ld = spec.desc(), grid.desc(), _loss_desc(loss, weight_mode, 1.0, 0.0, 0.0)
-    rc = L.load().inrfit_step_only(C.byref(md), params.data_ptr(), C.byref(gd), targets.data_ptr(), C.byref(ld), n_images,
-                                   int(iters), ws.data_ptr(), ws.numel() * 4, _stream_ptr(params.device))
-    L.check(rc, "inrfit_step_only")
+    X.call("inrfit_step_only", spec._desc, params, grid._desc, targets, X.loss_desc(loss, weight_mode, 1.0, 0.0, 0.0), n_images,
+           int(iters), ws=ws, device=params.device)
     return ws
 
 
@@ -324,6 +310,18 @@ def new_opt_state(spec: IcnnSpec, n_images: int, device) -> Tensor:
     return torch.zeros(n_images, 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS, dtype=torch.float32, device=device)
 
 
+def _opt_states(ispec: IcnnSpec, flow_n_params: int, n: int, dev, icnn_opt_state: Optional[Tensor],
+               flow_opt_state: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The two optimizer states of an ICNN behind a deformation: fresh (zeroed) where None, the caller's checked against their widths
+    ([n, 2P + 8] and [n, 2 * flow_n_params])."""
+    if icnn_opt_state is None:
+        icnn_opt_state = new_opt_state(ispec, n, dev)
+    if flow_opt_state is None:
+        flow_opt_state = torch.zeros(n, 2 * flow_n_params, dtype=torch.float32, device=dev)
+    return (X.rows(icnn_opt_state, "icnn_opt_state", n, 2 * ispec.n_params + L.INR_OPT_HEADER_FLOATS),
+            X.rows(flow_opt_state, "flow_opt_state", n, 2 * flow_n_params))
+
+
 def fit(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, steps: int, lr: float = 2e-3, loss: str = "se",
         weight_mode: str = "none", ratio: float = 1.0, c_fg: float = 0.0, c_bg: float = 0.0, optimizer: str = "adam",
         betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, clamp: bool = True,
@@ -332,34 +330,21 @@ def fit(spec: IcnnSpec, params: Tensor, grid: Grid, targets: Tensor, steps: int,
     """`steps` optimisation steps of n_images independent fits on the device (params updated IN PLACE).
     gate_logits: `logits` = the output of the last training forward (what the reference's IoU gate reads) instead of the logits at
     the final parameters."""
-    _check_spec(spec)
-    params = _check_dev(params, "params")
-    targets = _check_dev(targets, "targets")
     if params.dim() != 2:
         raise ValueError("params must be [n_images, P]")
-    n_images = params.shape[0]
-    targets = targets.reshape(n_images, -1)   # ([n_images, O, N] for n_out > 1)
-    assert targets.shape[1] == spec.n_out * grid.n_points
+    params, n_images = _params(spec, params)
+    targets = _per_point(spec, targets, "targets", n_images, grid)
     dev = params.device
     if opt_state is None:
         opt_state = new_opt_state(spec, n_images, dev)
+    opt_state = X.rows(opt_state, "opt_state", n_images, 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS)
+    X.on_gpu(params=params, targets=targets, opt_state=opt_state)
     ws = _workspace(spec, grid, n_images)
-    hist = L.scratch(n_images, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    logits = L.scratch(*_out_shape(spec, n_images, grid.n_points), dtype=torch.float32, device=dev) if want_logits else None
-    status = torch.zeros(n_images, dtype=torch.int32, device=dev)
-    pl = plateau or {}
-    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                      int(bool(clamp)), int(plateau is not None), int(pl.get("patience", 200)), float(pl.get("factor", 0.5)),
-                      float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)), float(pl.get("eps", 1e-8)),
-                      int(bool(freeze_skips)), int(bool(freeze_input)), int(bool(gate_logits)))
-    md, gd, ld = spec.desc(), grid.desc(), _loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_fit(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), targets.data_ptr(),
-                             C.byref(ld), C.byref(od), n_images, int(steps), int(step0),
-                             hist.data_ptr() if hist is not None else None,
-                             logits.data_ptr() if logits is not None else None, status.data_ptr(), ws.data_ptr(),
-                             ws.numel() * 4, _stream_ptr(dev))
-    L.check(rc, "inrfit_fit")
-    return FitResult(params, opt_state, hist[:, :steps] if hist is not None else None, logits, status)
+    hist, logits, status = X.fit_outputs(n_images, steps, _out_shape(spec, n_images, grid.n_points), record_loss, want_logits, dev)
+    od = X.opt_desc(optimizer, lr, betas, eps, weight_decay, clamp, plateau, freeze_skips, freeze_input, gate_logits)
+    X.call("inrfit_fit", spec._desc, params, opt_state, grid._desc, targets, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), od,
+           n_images, int(steps), int(step0), hist, logits, status, ws=ws, device=dev)
+    return FitResult(params, opt_state, X.trim(hist, steps), logits, status)
 
 
 def miou(out: Tensor, tgt: Tensor, thr_out: float = 0.5, thr_tgt: float = 0.5, invert: bool = True) -> Tensor:
@@ -370,9 +355,7 @@ def miou(out: Tensor, tgt: Tensor, thr_out: float = 0.5, thr_tgt: float = 0.5, i
     out = out.reshape(n_images, -1)
     tgt = tgt.reshape(n_images, -1)
     res = L.scratch(n_images, dtype=torch.float32, device=out.device)
-    rc = L.load().inrfit_miou(out.data_ptr(), tgt.data_ptr(), n_images, out.shape[1], float(thr_out), float(thr_tgt),
-                              int(bool(invert)), res.data_ptr(), _stream_ptr(out.device))
-    L.check(rc, "inrfit_miou")
+    X.call("inrfit_miou", out, tgt, n_images, out.shape[1], float(thr_out), float(thr_tgt), int(bool(invert)), res, device=out.device)
     return res
 
 
@@ -403,7 +386,5 @@ def pack_masks(values: Tensor, threshold: float = 0.5, invert: bool = False) -> 
     values = values.reshape(n, -1)
     words = (values.shape[1] + 63) // 64
     bits = torch.zeros(n, words, dtype=torch.int64, device=values.device)
-    rc = L.load().inrfit_pack_masks(values.data_ptr(), n, values.shape[1], float(threshold), int(bool(invert)), bits.data_ptr(),
-                                    _stream_ptr(values.device))
-    L.check(rc, "inrfit_pack_masks")
+    X.call("inrfit_pack_masks", values, n, values.shape[1], float(threshold), int(bool(invert)), bits, device=values.device)
     return bits

@@ -24,6 +24,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
 from . import icnn as K
 
@@ -48,51 +49,38 @@ def joint_desc(kind: str = "bce", weight_mode: str = "sssdms", ratio: float = 1.
                               int(bool(class_targets)), int(noneclass is not None), float(noneclass if noneclass is not None else 0.0))
 
 
-def _opt_desc(optimizer: str, lr: float, betas, eps: float, weight_decay: float, clamp: bool) -> L.InrOptDesc:
-    return L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                        int(bool(clamp)), 0, 0, 1.0, 0.0, 0.0, 0.0, 0, 0, 0)
-
-
 def _outputs(n: int, dev) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     return (L.scratch(4, dtype=torch.float32, device=dev), L.scratch(n, dtype=torch.float32, device=dev),
             L.scratch(n, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
 
 
-_ws_cache = {}
-
-
 def _workspace(key, nbytes_fn, dev) -> Tensor:
-    """One workspace per (model shape, grid size, device): a joint epoch calls the step thousands of times.  Every call here
-    writes all of its workspace before it reads it, so under L.POISON a fresh NaN-filled one per call is the check that it does;
-    the segmentation networks' cache (_segnet.SegDriver.workspace) carries state between two calls and must not do that."""
-    k = (key, str(dev))
-    ws = _ws_cache.get(k)
-    if ws is None or L.POISON:
-        nbytes = int(nbytes_fn())
-        if nbytes < 0:
-            L.check(nbytes, "joint step workspace")
-        ws = L.scratch(nbytes // 4 + 64, dtype=torch.float32, device=dev)
-        _ws_cache[k] = ws
-    return ws
+    """One workspace per (model shape, grid size, device): a joint epoch calls the step thousands of times (X.cached_workspace)."""
+    return X.cached_workspace(key, nbytes_fn, dev, refresh_under_poison=True, what="joint step workspace")
+
+
+def _state(t: Tensor, name: str, numel: int) -> Tensor:
+    """An optimizer-state row: updated in place, so it has to be contiguous as it comes."""
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (it is updated in place)")
+    return X.flat(t, name, numel)
 
 
 def _icnn_joint(entry: str, spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
                 n_target: int, desc, extra: tuple, od: L.InrOptDesc, step: int, wide: bool = False) -> JointStepResult:
-    """inrfit_joint_step / inrfit_joint_prior_step: `extra` is what the entry point takes between its loss desc and its opt desc.
+    """inrfit_joint_step / inrfit_joint_prior_step: `extra` is what the entry point takes between its loss desc and its opt desc
+    (nothing, or the prior step's checked seg_term / None).
     `wide`: the layer-by-layer entry points and their workspace."""
-    params, seg, target = K._check_dev(params, "params"), K._check_dev(seg, "seg"), K._check_dev(target, "target")
+    K._check_spec(spec)
     dev, n = params.device, grid.n_points
-    assert params.numel() == spec.n_params and seg.numel() == n and target.numel() == n_target
-    assert opt_state.numel() == 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS and opt_state.is_contiguous()
-    md, gd = spec.desc(), grid.desc()
-    lib = L.load()
-    ws_bytes = lib.inrfit_wide_joint_step_workspace_bytes if wide else lib.inrfit_joint_step_workspace_bytes
+    params, opt_state = X.flat(params, "params", spec.n_params), _state(opt_state, "opt_state", 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS)
+    seg, target = X.flat(seg, "seg", n), X.flat(target, "target", n_target)
+    X.on_gpu(params=params, opt_state=opt_state, seg=seg, target=target, seg_term=extra[0] if extra else None)
+    md, gd = spec._desc, grid._desc
+    ws_bytes = getattr(L.load(), "inrfit_wide_joint_step_workspace_bytes" if wide else "inrfit_joint_step_workspace_bytes")
     ws = _workspace(("icnn-wide" if wide else "icnn", spec, n), lambda: ws_bytes(C.byref(md), C.byref(gd)), dev)
     loss, dseg, logits, status = _outputs(n, dev)
-    rc = getattr(lib, entry)(C.byref(md), params.data_ptr(), opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(),
-                             C.byref(desc), *extra, C.byref(od), int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(),
-                             status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, entry)
+    X.call(entry, md, params, opt_state, gd, seg, target, desc, *extra, od, int(step), loss, dseg, logits, status, ws=ws, device=dev)
     return JointStepResult(loss, dseg, logits, status)
 
 
@@ -101,8 +89,15 @@ def _flow_joint(family: str, ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow
                 flow_weight_decay: float, step: int) -> JointStepResult:
     """inrfit_pcn_joint_step / inrfit_cdn_joint_step: `fspec` is the family's flow (RnvpSpec / FlowSpec); family 'pcn_wide':
     inrfit_pcn_wide_joint_step with its own workspace call."""
+    K._check_spec(ispec)
     dev, n = icnn_params.device, grid.n_points
-    md, fd, gd = ispec.desc(), fspec.desc(), grid.desc()
+    icnn_params, flow_params = X.flat(icnn_params, "icnn_params", ispec.n_params), X.flat(flow_params, "flow_params", fspec.n_params)
+    icnn_opt_state = _state(icnn_opt_state, "icnn_opt_state", 2 * ispec.n_params + L.INR_OPT_HEADER_FLOATS)
+    flow_opt_state = _state(flow_opt_state, "flow_opt_state", 2 * fspec.n_params)
+    seg, target = X.flat(seg, "seg", n), X.flat(target, "target", n)
+    X.on_gpu(icnn_params=icnn_params, flow_params=flow_params, icnn_opt_state=icnn_opt_state, flow_opt_state=flow_opt_state, seg=seg,
+             target=target)
+    md, fd, gd = ispec._desc, fspec._desc, grid._desc
     lib = L.load()
     if family == "pcn_wide":
         ws = _workspace((family, ispec, fspec, n),
@@ -113,12 +108,8 @@ def _flow_joint(family: str, ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow
                         lambda: ws_bytes(C.byref(md), C.byref(fd), C.byref(gd), 1) + lib.inrfit_joint_loss_workspace_bytes(n) + 4 * n + 1024,
                         dev)
     loss, dseg, logits, status = _outputs(n, dev)
-    entry = f"inrfit_{family}_joint_step"
-    rc = getattr(lib, entry)(C.byref(md), C.byref(fd), icnn_params.data_ptr(), flow_params.data_ptr(), icnn_opt_state.data_ptr(),
-                             flow_opt_state.data_ptr(), C.byref(gd), seg.data_ptr(), target.data_ptr(), C.byref(desc), C.byref(od),
-                             float(flow_weight_decay), int(step), loss.data_ptr(), dseg.data_ptr(), logits.data_ptr(),
-                             status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, entry)
+    X.call(f"inrfit_{family}_joint_step", md, fd, icnn_params, flow_params, icnn_opt_state, flow_opt_state, gd, seg, target, desc, od,
+           float(flow_weight_decay), int(step), loss, dseg, logits, status, ws=ws, device=dev)
     return JointStepResult(loss, dseg, logits, status)
 
 
@@ -127,7 +118,7 @@ def joint_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid
                weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
     """ICNN prior (ConvexNet / ConvexNextNet).  `params` [P] and `opt_state` [2P + 8] are updated IN PLACE."""
     return _icnn_joint("inrfit_joint_step", spec, params, opt_state, grid, seg, target, grid.n_points, desc, (),
-                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
+                       X.opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
 
 
 def pcn_joint_step(ispec: K.IcnnSpec, rspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor, flow_opt_state: Tensor,
@@ -135,7 +126,7 @@ def pcn_joint_step(ispec: K.IcnnSpec, rspec, icnn_params: Tensor, flow_params: T
                    optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8, flow_weight_decay: float = 0.0) -> JointStepResult:
     """PathConnectedNet prior (ICNN behind the RealNVP deformation); every tensor is one row, updated in place."""
     return _flow_joint("pcn", ispec, rspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
-                       _opt_desc(optimizer, lr, betas, eps, 0.0, True), flow_weight_decay, step)
+                       X.opt_desc(optimizer, lr, betas, eps, clamp=True), flow_weight_decay, step)
 
 
 def cdn_joint_step(ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor, flow_opt_state: Tensor,
@@ -143,7 +134,7 @@ def cdn_joint_step(ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: T
                    betas=(0.9, 0.999), eps: float = 1e-8, weight_decay_on_weight_g: float = 0.0) -> JointStepResult:
     """ConvexDiffeomorphismNet prior (ICNN behind the weight-normed coupling flow); Adam only, like its pretrain loop."""
     return _flow_joint("cdn", ispec, fspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
-                       _opt_desc("adam", lr, betas, eps, 0.0, True), weight_decay_on_weight_g, step)
+                       X.opt_desc("adam", lr, betas, eps, clamp=True), weight_decay_on_weight_g, step)
 
 
 def joint_prior_desc(kind: str = "bce", weight_mode: str = "none", ratio: float = 1.0, noneclass=None, data_count: int = 0,
@@ -160,12 +151,11 @@ def joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: 
     points when 0); `seg_term` is None or a one-element float32 device tensor, the caller's segmentation share.  `params` [P] and
     `opt_state` [2P + 8] are updated IN PLACE.  loss: composite, data term, mean align term before beta, gradient scale."""
     if seg_term is not None:
-        seg_term = K._check_dev(seg_term, "seg_term")
-        assert seg_term.numel() == 1
+        seg_term = X.flat(seg_term, "seg_term", 1)
     return _icnn_joint("inrfit_joint_prior_step", spec, params, opt_state, grid, seg, target,
                        desc.data_count if desc.data_count > 0 else grid.n_points, desc,
-                       (None if seg_term is None else seg_term.data_ptr(),),
-                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
+                       (seg_term,),
+                       X.opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step)
 
 
 def wide_joint_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
@@ -173,7 +163,7 @@ def wide_joint_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K
                     weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
     """`joint_step` for an ICNN of the layer-by-layer path (inrfit_wide_joint_step)."""
     return _icnn_joint("inrfit_wide_joint_step", spec, params, opt_state, grid, seg, target, grid.n_points, desc, (),
-                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step, wide=True)
+                       X.opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step, wide=True)
 
 
 def pcn_wide_joint_step(ispec: K.IcnnSpec, rspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
@@ -182,7 +172,7 @@ def pcn_wide_joint_step(ispec: K.IcnnSpec, rspec, icnn_params: Tensor, flow_para
                         flow_weight_decay: float = 0.0) -> JointStepResult:
     """`pcn_joint_step` over an ICNN of the layer-by-layer path (inrfit_pcn_wide_joint_step)."""
     return _flow_joint("pcn_wide", ispec, rspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
-                       _opt_desc(optimizer, lr, betas, eps, 0.0, True), flow_weight_decay, step)
+                       X.opt_desc(optimizer, lr, betas, eps, clamp=True), flow_weight_decay, step)
 
 
 def wide_joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor,
@@ -190,9 +180,8 @@ def wide_joint_prior_step(spec: K.IcnnSpec, params: Tensor, opt_state: Tensor, g
                           betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, clamp: bool = True) -> JointStepResult:
     """`joint_prior_step` for an ICNN of the layer-by-layer path (inrfit_wide_joint_prior_step)."""
     if seg_term is not None:
-        seg_term = K._check_dev(seg_term, "seg_term")
-        assert seg_term.numel() == 1
+        seg_term = X.flat(seg_term, "seg_term", 1)
     return _icnn_joint("inrfit_wide_joint_prior_step", spec, params, opt_state, grid, seg, target,
                        desc.data_count if desc.data_count > 0 else grid.n_points, desc,
-                       (None if seg_term is None else seg_term.data_ptr(),),
-                       _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step, wide=True)
+                       (seg_term,),
+                       X.opt_desc(optimizer, lr, betas, eps, weight_decay, clamp), step, wide=True)

@@ -300,7 +300,7 @@ class _FusedJointLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, output: torch.Tensor, target: torch.Tensor, desc):
-        import ctypes as C
+        from .. import _call as X
         from .. import _lib as L
         out = output.detach().contiguous().to(torch.float32)
         if desc.form == L.JOINT_AWESOME_PIXEL:
@@ -310,14 +310,10 @@ class _FusedJointLoss(torch.autograd.Function):
             b, c2 = out.shape[0], out.shape[1]
             hw = out.numel() // (b * c2)
         tgt = target.detach().contiguous().to(torch.float32)
-        lib = L.load()
-        nbytes = int(lib.inrfit_joint_loss_workspace_bytes(b * hw))
-        ws = L.scratch(nbytes // 4 + 1, dtype=torch.float32, device=out.device)
+        ws = X.workspace("inrfit_joint_loss_workspace_bytes", b * hw, device=out.device)
         res = L.scratch(4, dtype=torch.float32, device=out.device)
         dout = L.scratch_like(out)
-        rc = lib.inrfit_joint_loss(out.data_ptr(), tgt.data_ptr(), b, hw, C.byref(desc), res.data_ptr(), dout.data_ptr(), ws.data_ptr(),
-                                   ws.numel() * 4, K._stream_ptr(out.device))
-        L.check(rc, "inrfit_joint_loss")
+        X.call("inrfit_joint_loss", out, tgt, b, hw, desc, res, dout, ws=ws, device=out.device)
         ctx.save_for_backward(dout)
         ctx.terms = res
         return res[0].clone()

@@ -17,6 +17,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
 from . import flow as FL
 from . import icnn as K
@@ -74,16 +75,12 @@ def dataloader_batches(n: int, batch_size: int, epochs: int, generator: Optional
 # ----------------------------------------------------------------------------------------------------------------------
 # entry points
 # ----------------------------------------------------------------------------------------------------------------------
-def _pool(spec: K.IcnnSpec, n_images: int, pool_coords: Tensor, pool_targets: Tensor) -> Tuple[Tensor, Tensor, int]:
-    pool_coords = K._check_dev(pool_coords, "pool_coords")
-    pool_targets = K._check_dev(pool_targets, "pool_targets")
-    if pool_coords.dim() != 2 or pool_coords.shape[0] != spec.in_features:
-        raise ValueError(f"pool_coords must be [C = {spec.in_features}, n_pool] (shared by all images)")
-    n_pool = int(pool_coords.shape[1])
-    pool_targets = pool_targets.reshape(n_images, -1)   # ([n_images, O, n_pool] for n_out > 1)
-    if pool_targets.shape[1] != spec.n_out * n_pool:
-        raise ValueError(f"pool_targets must be [n_images, n_pool] ([n_images, O, n_pool] for n_out > 1), got {tuple(pool_targets.shape)}")
-    return pool_coords, pool_targets, n_pool
+def _pool(spec: K.IcnnSpec, n_images: int, pool_coords: Tensor, pool_targets: Tensor, channels: Optional[int] = None) -> Tuple[Tensor, Tensor, int]:
+    """pool_coords [C, n_pool] (shared by all images; C = spec.in_features unless `channels`) and pool_targets [n_images, n_pool]
+    ([n_images, O, n_pool] for n_out > 1), checked -> (pool_coords, pool_targets [n_images, O * n_pool], n_pool)."""
+    n_pool = int(pool_coords.shape[-1]) if pool_coords.dim() else 0
+    pool_coords = X.rows(pool_coords, "pool_coords", channels or spec.in_features, n_pool)
+    return pool_coords, X.flat(pool_targets, "pool_targets", n_images * spec.n_out * n_pool).reshape(n_images, -1), n_pool
 
 
 def _table(index: Tensor, counts, device) -> Tuple[Tensor, Optional[C.Array], int, int]:
@@ -101,21 +98,8 @@ def _table(index: Tensor, counts, device) -> Tuple[Tensor, Optional[C.Array], in
 
 
 def _workspace(spec: K.IcnnSpec, fspec: Optional[FL.FlowSpec], batch: int, n_images: int, device) -> Tensor:
-    md = spec.desc()
-    fd = fspec.desc() if fspec is not None else None
-    nbytes = L.load().inrfit_minibatch_workspace_bytes(C.byref(md), C.byref(fd) if fd is not None else None, batch, n_images)
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_minibatch_workspace_bytes")
-    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=device)
-
-
-def _opt_desc(optimizer: str, lr: float, betas, eps: float, weight_decay: float, clamp: bool, plateau: Optional[dict],
-              freeze_skips: bool, freeze_input: bool) -> L.InrOptDesc:
-    pl = plateau or {}
-    return L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                        int(bool(clamp)), int(plateau is not None), int(pl.get("patience", 200)), float(pl.get("factor", 0.5)),
-                        float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)), float(pl.get("eps", 1e-8)),
-                        int(bool(freeze_skips)), int(bool(freeze_input)), 0)
+    return X.workspace("inrfit_minibatch_workspace_bytes", spec._desc, fspec._desc if fspec is not None else None, batch, n_images,
+                       device=device)
 
 
 def fit_minibatch(spec: K.IcnnSpec, params: Tensor, pool_coords: Tensor, pool_targets: Tensor, index: Tensor,
@@ -129,25 +113,20 @@ def fit_minibatch(spec: K.IcnnSpec, params: Tensor, pool_coords: Tensor, pool_ta
     [n_images, n_pool] ([n_images, O, n_pool] for n_out > 1) are their own.  The keyword arguments are `icnn.fit`'s; there are no
     final logits (inference over all pixels is `icnn.forward`)."""
     K._check_spec(spec)
-    params = K._check_dev(params, "params")
-    if params.dim() != 2 or params.shape[1] != spec.n_params:
-        raise ValueError("params must be [n_images, P]")
+    params = X.rows(params, "params", None, spec.n_params)
     n_images, dev = params.shape[0], params.device
     pool_coords, pool_targets, n_pool = _pool(spec, n_images, pool_coords, pool_targets)
-    index, carr, steps, batch = _table(index, counts, dev)
     if opt_state is None:
         opt_state = K.new_opt_state(spec, n_images, dev)
+    opt_state = X.rows(opt_state, "opt_state", n_images, 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS)
+    X.on_gpu(params=params, pool_coords=pool_coords, pool_targets=pool_targets, opt_state=opt_state)
+    index, carr, steps, batch = _table(index, counts, dev)
     ws = _workspace(spec, None, batch, n_images, dev)
-    hist = L.scratch(n_images, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    status = torch.zeros(n_images, dtype=torch.int32, device=dev)
-    od = _opt_desc(optimizer, lr, betas, eps, weight_decay, clamp, plateau, freeze_skips, freeze_input)
-    md, ld = spec.desc(), K._loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_fit_minibatch(C.byref(md), params.data_ptr(), opt_state.data_ptr(), pool_coords.data_ptr(),
-                                       pool_targets.data_ptr(), n_pool, index.data_ptr(), carr, batch, C.byref(ld), C.byref(od),
-                                       n_images, steps, int(step0), hist.data_ptr() if hist is not None else None,
-                                       status.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_fit_minibatch")
-    return K.FitResult(params, opt_state, hist[:, :steps] if hist is not None else None, None, status)
+    hist, _, status = X.fit_outputs(n_images, steps, None, record_loss, False, dev)
+    od = X.opt_desc(optimizer, lr, betas, eps, weight_decay, clamp, plateau, freeze_skips, freeze_input)
+    X.call("inrfit_fit_minibatch", spec._desc, params, opt_state, pool_coords, pool_targets, n_pool, index, carr, batch,
+           X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), od, n_images, steps, int(step0), hist, status, ws=ws, device=dev)
+    return K.FitResult(params, opt_state, X.trim(hist, steps), None, status)
 
 
 def cdn_fit_minibatch(ispec: K.IcnnSpec, fspec: FL.FlowSpec, icnn_params: Tensor, flow_params: Tensor, pool_coords: Tensor,
@@ -158,26 +137,20 @@ def cdn_fit_minibatch(ispec: K.IcnnSpec, fspec: FL.FlowSpec, icnn_params: Tensor
                       flow_opt_state: Optional[Tensor] = None, step0: int = 0, record_loss: bool = True) -> FL.CdnFitResult:
     """`fit_minibatch` for ICNN(flow(Ax + b)): `flow.cdn_fit`'s step (Adam over everything, weight decay on the weight_g group) on
     the pixels index[k, :counts[k]] of the pool at step k.  No final logits (`flow.cdn_forward`)."""
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n, dev = ip.shape[0], ip.device
+    ip, fp, n = FL._params(ispec, fspec, icnn_params, flow_params)
+    dev = ip.device
     pool_coords, pool_targets, n_pool = _pool(ispec, n, pool_coords, pool_targets)
+    icnn_opt_state, flow_opt_state = K._opt_states(ispec, fspec.n_params, n, dev, icnn_opt_state, flow_opt_state)
+    X.on_gpu(icnn_params=ip, flow_params=fp, pool_coords=pool_coords, pool_targets=pool_targets, icnn_opt_state=icnn_opt_state,
+             flow_opt_state=flow_opt_state)
     index, carr, steps, batch = _table(index, counts, dev)
-    if icnn_opt_state is None:
-        icnn_opt_state = K.new_opt_state(ispec, n, dev)
-    if flow_opt_state is None:
-        flow_opt_state = torch.zeros(n, 2 * fspec.n_params, dtype=torch.float32, device=dev)
     ws = _workspace(ispec, fspec, batch, n, dev)
-    hist = L.scratch(n, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    od = _opt_desc("adam", lr, betas, eps, 0.0, clamp, plateau, False, False)
-    md, fd, ld = ispec.desc(), fspec.desc(), K._loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_cdn_fit_minibatch(C.byref(md), C.byref(fd), ip.data_ptr(), fp.data_ptr(), icnn_opt_state.data_ptr(),
-                                           flow_opt_state.data_ptr(), pool_coords.data_ptr(), pool_targets.data_ptr(), n_pool,
-                                           index.data_ptr(), carr, batch, C.byref(ld), C.byref(od), float(weight_decay_on_weight_g),
-                                           n, steps, int(step0), hist.data_ptr() if hist is not None else None, status.data_ptr(),
-                                           ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_cdn_fit_minibatch")
-    return FL.CdnFitResult(ip, fp, icnn_opt_state, flow_opt_state, hist[:, :steps] if hist is not None else None, None, status)
+    hist, _, status = X.fit_outputs(n, steps, None, record_loss, False, dev)
+    od = X.opt_desc("adam", lr, betas, eps, clamp=clamp, plateau=plateau)
+    X.call("inrfit_cdn_fit_minibatch", ispec._desc, fspec._desc, ip, fp, icnn_opt_state, flow_opt_state, pool_coords, pool_targets,
+           n_pool, index, carr, batch, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), od, float(weight_decay_on_weight_g), n, steps,
+           int(step0), hist, status, ws=ws, device=dev)
+    return FL.CdnFitResult(ip, fp, icnn_opt_state, flow_opt_state, X.trim(hist, steps), None, status)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -17,10 +17,12 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
+from functools import cached_property
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
 from . import icnn as K
 
@@ -68,11 +70,15 @@ class RnvpSpec:
             d.masks[f] = int(m)
         return d
 
+    @cached_property
+    def _desc(self) -> L.InrRnvpDesc:      # for the wrappers, once per spec (never written to)
+        return self.desc()
+
     @property
     def net_params(self) -> int:
         return 2 * self.hidden_units * self.channels + self.hidden_units + self.channels
 
-    @property
+    @cached_property
     def n_params(self) -> int:
         return 2 * self.channels + self.n_flows * (2 * self.net_params + 2 * self.channels)
 
@@ -137,36 +143,37 @@ def init_rnvp_params(spec: RnvpSpec) -> Tensor:
 
 
 def _ws(ispec: Optional[K.IcnnSpec], rspec: RnvpSpec, grid: K.Grid, n_images: int) -> Tensor:
-    md = ispec.desc() if ispec is not None else None
-    rd, gd = rspec.desc(), grid.desc()
-    nbytes = L.load().inrfit_pcn_workspace_bytes(C.byref(md) if md is not None else None, C.byref(rd), C.byref(gd), n_images)
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_pcn_workspace_bytes")
-    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=grid.device)
+    return X.workspace("inrfit_pcn_workspace_bytes", ispec._desc if ispec is not None else None, rspec._desc, grid._desc, n_images,
+                       device=grid.device)
+
+
+def _flow_params(rspec: RnvpSpec, flow_params: Tensor, n: Optional[int] = None) -> Tensor:
+    return X.rows(flow_params, "flow_params", n, rspec.n_params)
+
+
+def _params(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, flow_params: Tensor, n: Optional[int] = None) -> Tuple[Tensor, Tensor, int]:
+    """icnn_params [n_images, P] and flow_params [n_images, RP], checked against their specs."""
+    K._check_spec(ispec)
+    ip = X.rows(icnn_params, "icnn_params", n, ispec.n_params)
+    return ip, _flow_params(rspec, flow_params, ip.shape[0]), ip.shape[0]
 
 
 def actnorm_init(rspec: RnvpSpec, flow_params: Tensor, grid: K.Grid) -> Tensor:
     """Data-dependent ActNorm initialisation, in place on flow_params [n_images, RP]."""
-    fp = K._check_dev(flow_params, "flow_params")
+    fp = _flow_params(rspec, flow_params)
+    X.on_gpu(flow_params=fp)
     n = fp.shape[0]
-    ws = _ws(None, rspec, grid, n)
-    rd, gd = rspec.desc(), grid.desc()
-    rc = L.load().inrfit_rnvp_actnorm_init(C.byref(rd), fp.data_ptr(), C.byref(gd), n, ws.data_ptr(), ws.numel() * 4,
-                                           K._stream_ptr(fp.device))
-    L.check(rc, "inrfit_rnvp_actnorm_init")
+    X.call("inrfit_rnvp_actnorm_init", rspec._desc, fp, grid._desc, n, ws=_ws(None, rspec, grid, n), device=fp.device)
     return fp
 
 
 def rnvp_forward(rspec: RnvpSpec, flow_params: Tensor, grid: K.Grid) -> Tensor:
     """flow_params [n_images, RP] -> deformed coordinates [n_images, C, N]."""
-    fp = K._check_dev(flow_params, "flow_params")
+    fp = _flow_params(rspec, flow_params)
+    X.on_gpu(flow_params=fp)
     n = fp.shape[0]
     out = L.scratch(n, rspec.channels, grid.n_points, dtype=torch.float32, device=fp.device)
-    ws = _ws(None, rspec, grid, n)
-    rd, gd = rspec.desc(), grid.desc()
-    rc = L.load().inrfit_rnvp_forward(C.byref(rd), fp.data_ptr(), C.byref(gd), n, out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                      K._stream_ptr(fp.device))
-    L.check(rc, "inrfit_rnvp_forward")
+    X.call("inrfit_rnvp_forward", rspec._desc, fp, grid._desc, n, out, ws=_ws(None, rspec, grid, n), device=fp.device)
     return out
 
 
@@ -174,33 +181,26 @@ def rnvp_backward(rspec: RnvpSpec, flow_params: Tensor, grid: K.Grid, dout: Tens
     """The vector-Jacobian product of rnvp_forward: dout [n_images, C, N] (d loss / d deformed coordinates) -> flow gradients
     [n_images, RP] in the flat layout (linear.weight / linear.bias included); with want_dcoords also d loss / d input coordinates
     [n_images, C, N].  Returns flow_grads or (flow_grads, dcoords)."""
-    fp = K._check_dev(flow_params, "flow_params")
+    fp = _flow_params(rspec, flow_params)
     n = fp.shape[0]
-    dout = K._check_dev(dout, "dout").reshape(n, rspec.channels, grid.n_points)
+    dout = X.flat(dout, "dout", n * rspec.channels * grid.n_points)
+    X.on_gpu(flow_params=fp, dout=dout)
     gf = L.scratch_like(fp)
     din = L.scratch(n, rspec.channels, grid.n_points, dtype=torch.float32, device=fp.device) if want_dcoords else None
-    ws = _ws(None, rspec, grid, n)
-    rd, gd = rspec.desc(), grid.desc()
-    rc = L.load().inrfit_rnvp_backward(C.byref(rd), fp.data_ptr(), C.byref(gd), dout.data_ptr(), n, gf.data_ptr(),
-                                       din.data_ptr() if din is not None else None, ws.data_ptr(), ws.numel() * 4,
-                                       K._stream_ptr(fp.device))
-    L.check(rc, "inrfit_rnvp_backward")
+    X.call("inrfit_rnvp_backward", rspec._desc, fp, grid._desc, dout, n, gf, din, ws=_ws(None, rspec, grid, n), device=fp.device)
     return (gf, din) if want_dcoords else gf
 
 
 def rnvp_inverse(rspec: RnvpSpec, flow_params: Tensor, coords: Tensor) -> Tensor:
     """PathConnectedNet.inverse (path_connected_net.py:107-122): coords (C, N) shared or (n_images, C, N) -> [n_images, C, N]."""
-    fp = K._check_dev(flow_params, "flow_params")
-    coords = K._check_dev(coords, "coords")
-    n = fp.shape[0]
+    fp = _flow_params(rspec, flow_params)
+    n, N = fp.shape[0], (coords.shape[-1] if coords.dim() else 0)
+    coords = X.rows(coords, "coords", n, (rspec.channels, N)) if coords.dim() == 3 else X.rows(coords, "coords", rspec.channels, N)
+    X.on_gpu(flow_params=fp, coords=coords)
     stride = 0 if coords.dim() == 2 else coords.shape[1] * coords.shape[2]
-    N = coords.shape[-1]
     out = L.scratch(n, rspec.channels, N, dtype=torch.float32, device=fp.device)
-    ws = _ws(None, rspec, K.Grid.explicit(coords), n)
-    rd = rspec.desc()
-    rc = L.load().inrfit_rnvp_inverse(C.byref(rd), fp.data_ptr(), coords.data_ptr(), stride, N, n, out.data_ptr(), ws.data_ptr(),
-                                      ws.numel() * 4, K._stream_ptr(fp.device))
-    L.check(rc, "inrfit_rnvp_inverse")
+    X.call("inrfit_rnvp_inverse", rspec._desc, fp, coords, stride, N, n, out, ws=_ws(None, rspec, K.Grid.explicit(coords), n),
+           device=fp.device)
     return out
 
 
@@ -209,47 +209,40 @@ def fit_identity(rspec: RnvpSpec, flow_params: Tensor, grid: K.Grid, steps: int 
                  step0: int = 0) -> Tuple[Tensor, Tensor]:
     """PathConnectedNet.learn_flow_identity (path_connected_net.py:155-250; defaults of the prefit kwargs :771-774): the flow_net
     alone is trained towards the identity on the grid, in place on flow_params [n_images, RP].  Returns (loss_hist, opt_state)."""
-    fp = K._check_dev(flow_params, "flow_params")
+    fp = _flow_params(rspec, flow_params)
     n, dev = fp.shape[0], fp.device
-    if flow_opt_state is None:
-        flow_opt_state = torch.zeros(n, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+    flow_opt_state = _flow_opt_state(rspec, n, dev, flow_opt_state)
+    X.on_gpu(flow_params=fp, flow_opt_state=flow_opt_state)
     hist = L.scratch(n, max(steps, 1), dtype=torch.float32, device=dev)
-    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 0, 0,
-                      0, 0.0, 0.0, 0.0, 0.0)
-    ws = _ws(None, rspec, grid, n)
-    rd, gd = rspec.desc(), grid.desc()
-    rc = L.load().inrfit_rnvp_fit_identity(C.byref(rd), fp.data_ptr(), flow_opt_state.data_ptr(), C.byref(gd), C.byref(od), n,
-                                           int(steps), int(step0), hist.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                           K._stream_ptr(dev))
-    L.check(rc, "inrfit_rnvp_fit_identity")
+    X.call("inrfit_rnvp_fit_identity", rspec._desc, fp, flow_opt_state, grid._desc, X.opt_desc(optimizer, lr, betas, eps, weight_decay),
+           n, int(steps), int(step0), hist, ws=_ws(None, rspec, grid, n), device=dev)
     return hist[:, :steps], flow_opt_state
 
 
+def _flow_opt_state(rspec: RnvpSpec, n: int, dev, flow_opt_state: Optional[Tensor]) -> Tensor:
+    if flow_opt_state is None:
+        flow_opt_state = torch.zeros(n, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+    return X.rows(flow_opt_state, "flow_opt_state", n, 2 * rspec.n_params)
+
+
 def pcn_forward(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, flow_params: Tensor, grid: K.Grid) -> Tensor:
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n = ip.shape[0]
+    ip, fp, n = _params(ispec, rspec, icnn_params, flow_params)
+    X.on_gpu(icnn_params=ip, flow_params=fp)
     logits = L.scratch(n, grid.n_points, dtype=torch.float32, device=ip.device)
-    ws = _ws(ispec, rspec, grid, n)
-    md, rd, gd = ispec.desc(), rspec.desc(), grid.desc()
-    rc = L.load().inrfit_pcn_forward(C.byref(md), C.byref(rd), ip.data_ptr(), fp.data_ptr(), C.byref(gd), n, logits.data_ptr(),
-                                     ws.data_ptr(), ws.numel() * 4, K._stream_ptr(ip.device))
-    L.check(rc, "inrfit_pcn_forward")
+    X.call("inrfit_pcn_forward", ispec._desc, rspec._desc, ip, fp, grid._desc, n, logits, ws=_ws(ispec, rspec, grid, n),
+           device=ip.device)
     return logits
 
 
 def pcn_loss_grad(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, flow_params: Tensor, grid: K.Grid, targets: Tensor,
                   loss: str = "se", weight_mode: str = "none", ratio: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n = ip.shape[0]
-    targets = K._check_dev(targets, "targets").reshape(n, -1)
+    ip, fp, n = _params(ispec, rspec, icnn_params, flow_params)
+    targets = K._per_point(ispec, targets, "targets", n, grid)
+    X.on_gpu(icnn_params=ip, flow_params=fp, targets=targets)
     lo = L.scratch(n, dtype=torch.float32, device=ip.device)
     gi, gf = L.scratch_like(ip), L.scratch_like(fp)
-    ws = _ws(ispec, rspec, grid, n)
-    md, rd, gd, ld = ispec.desc(), rspec.desc(), grid.desc(), K._loss_desc(loss, weight_mode, ratio, 0.0, 0.0)
-    rc = L.load().inrfit_pcn_loss_grad(C.byref(md), C.byref(rd), ip.data_ptr(), fp.data_ptr(), C.byref(gd), targets.data_ptr(),
-                                       C.byref(ld), n, lo.data_ptr(), gi.data_ptr(), gf.data_ptr(), ws.data_ptr(),
-                                       ws.numel() * 4, K._stream_ptr(ip.device))
-    L.check(rc, "inrfit_pcn_loss_grad")
+    X.call("inrfit_pcn_loss_grad", ispec._desc, rspec._desc, ip, fp, grid._desc, targets, X.loss_desc(loss, weight_mode, ratio, 0.0, 0.0),
+           n, lo, gi, gf, ws=_ws(ispec, rspec, grid, n), device=ip.device)
     return lo, gi, gf
 
 
@@ -271,30 +264,17 @@ def pcn_fit(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, flow_params
             step0: int = 0, record_loss: bool = True, want_logits: bool = True, gate_logits: bool = False) -> PcnFitResult:
     """_prior_based_pretrain's inner loop for PathConnectedNet on the device (defaults of path_connected_net.py:756-760,
     922-933: Adamax lr 1e-3, flow weight decay 1e-5, UnariesWeightedLoss(SE); pass plateau={} for ReduceLROnPlateau(200, 0.5))."""
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    n, dev = ip.shape[0], ip.device
-    targets = K._check_dev(targets, "targets").reshape(n, -1)
-    if icnn_opt_state is None:
-        icnn_opt_state = K.new_opt_state(ispec, n, dev)
-    if flow_opt_state is None:
-        flow_opt_state = torch.zeros(n, 2 * rspec.n_params, dtype=torch.float32, device=dev)
-    hist = L.scratch(n, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    logits = L.scratch(n, grid.n_points, dtype=torch.float32, device=dev) if want_logits else None
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    pl = plateau or {}
-    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 1,
-                      int(plateau is not None), int(pl.get("patience", 200)), float(pl.get("factor", 0.5)),
-                      float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)), float(pl.get("eps", 1e-8)), 0, 0, int(bool(gate_logits)))
-    ws = _ws(ispec, rspec, grid, n)
-    md, rd, gd, ld = ispec.desc(), rspec.desc(), grid.desc(), K._loss_desc(loss, weight_mode, ratio, 0.0, 0.0)
-    rc = L.load().inrfit_pcn_fit(C.byref(md), C.byref(rd), ip.data_ptr(), fp.data_ptr(), icnn_opt_state.data_ptr(),
-                                 flow_opt_state.data_ptr(), C.byref(gd), targets.data_ptr(), C.byref(ld), C.byref(od),
-                                 float(flow_weight_decay), n, int(steps), int(step0),
-                                 hist.data_ptr() if hist is not None else None,
-                                 logits.data_ptr() if logits is not None else None, status.data_ptr(), ws.data_ptr(),
-                                 ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_pcn_fit")
-    return PcnFitResult(ip, fp, icnn_opt_state, flow_opt_state, hist[:, :steps] if hist is not None else None, logits, status)
+    ip, fp, n = _params(ispec, rspec, icnn_params, flow_params)
+    dev = ip.device
+    targets = K._per_point(ispec, targets, "targets", n, grid)
+    icnn_opt_state, flow_opt_state = K._opt_states(ispec, rspec.n_params, n, dev, icnn_opt_state, flow_opt_state)
+    X.on_gpu(icnn_params=ip, flow_params=fp, targets=targets, icnn_opt_state=icnn_opt_state, flow_opt_state=flow_opt_state)
+    hist, logits, status = X.fit_outputs(n, steps, (n, grid.n_points), record_loss, want_logits, dev)
+    od = X.opt_desc(optimizer, lr, betas, eps, clamp=True, plateau=plateau, gate_logits=gate_logits)
+    X.call("inrfit_pcn_fit", ispec._desc, rspec._desc, ip, fp, icnn_opt_state, flow_opt_state, grid._desc, targets,
+           X.loss_desc(loss, weight_mode, ratio, 0.0, 0.0), od, float(flow_weight_decay), n, int(steps), int(step0), hist, logits, status,
+           ws=_ws(ispec, rspec, grid, n), device=dev)
+    return PcnFitResult(ip, fp, icnn_opt_state, flow_opt_state, X.trim(hist, steps), logits, status)
 
 
 # ---- sequence pretraining: all mini-batch epochs in one device call (include/inrfit.h, "sequence pretraining") --------------------
@@ -323,13 +303,18 @@ def _orders_host(orders, num_epochs: int, T: int):
 
 
 def _seq_ws(ispec: Optional[K.IcnnSpec], rspec: RnvpSpec, HW: int, T: int, batch_size: int, device) -> Tensor:
-    md = ispec.desc() if ispec is not None else None
-    rd = rspec.desc()
-    nbytes = L.load().inrfit_pcn_sequence_workspace_bytes(C.byref(md) if md is not None else None, C.byref(rd), int(HW), int(T),
-                                                         int(batch_size))
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_pcn_sequence_workspace_bytes")
-    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=device)
+    return X.workspace("inrfit_pcn_sequence_workspace_bytes", ispec._desc if ispec is not None else None, rspec._desc, int(HW), int(T),
+                       int(batch_size), device=device)
+
+
+def _frames(rspec: RnvpSpec, frame_coords: Tensor, orders) -> Tuple[Tensor, int, int, int, C.Array]:
+    """frame_coords (T, C, HW) checked -> (it, T, HW, num_epochs, the host order table)."""
+    if frame_coords.dim() != 3:
+        raise ValueError(f"frame_coords: expected (T, C, HW), got shape {tuple(frame_coords.shape)}")
+    fc = X.rows(frame_coords, "frame_coords", None, (rspec.channels, frame_coords.shape[2]))
+    T, HW = int(fc.shape[0]), int(fc.shape[2])
+    num_epochs = int(torch.as_tensor(orders).reshape(-1, T).shape[0])
+    return fc, T, HW, num_epochs, _orders_host(orders, num_epochs, T)
 
 
 @dataclass
@@ -350,33 +335,22 @@ def pcn_fit_sequence(ispec: K.IcnnSpec, rspec: RnvpSpec, icnn_params: Tensor, fl
     """The mini-batch epochs of _non_prior_based_pretrain (path_connected_net.py:634-713) in ONE `inrfit_pcn_fit_sequence` call: per
     batch of `orders[e]` what pcn_fit(steps=1) runs, per epoch the mean batch loss and ReduceLROnPlateau, nothing read back in
     between.  icnn_params [1, P], flow_params [1, RP] (in place); frame_coords (T, C, HW), frame_targets (T, HW)."""
-    ip, fp = K._check_dev(icnn_params, "icnn_params"), K._check_dev(flow_params, "flow_params")
-    fc, ft = K._check_dev(frame_coords, "frame_coords"), K._check_dev(frame_targets, "frame_targets")
+    ip, fp, _ = _params(ispec, rspec, icnn_params, flow_params, 1)
     dev = ip.device
-    T, HW = int(fc.shape[0]), int(fc.shape[2])
-    num_epochs = int(torch.as_tensor(orders).reshape(-1, T).shape[0])
-    order = _orders_host(orders, num_epochs, T)
-    if icnn_opt_state is None:
-        icnn_opt_state = K.new_opt_state(ispec, 1, dev)
-    if flow_opt_state is None:
-        flow_opt_state = torch.zeros(1, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+    fc, T, HW, num_epochs, order = _frames(rspec, frame_coords, orders)
+    ft = X.flat(frame_targets, "frame_targets", T * HW)
+    icnn_opt_state, flow_opt_state = K._opt_states(ispec, rspec.n_params, 1, dev, icnn_opt_state, flow_opt_state)
+    X.on_gpu(icnn_params=ip, flow_params=fp, frame_coords=fc, frame_targets=ft, icnn_opt_state=icnn_opt_state, flow_opt_state=flow_opt_state)
     epoch_loss = L.scratch(max(num_epochs, 1), dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
+    od = X.opt_desc(optimizer, lr, betas, eps, clamp=True, plateau=plateau)
+    # the scheduler's numbers as the Python loop carries them (doubles, where the desc holds floats)
     pl = plateau or {}
-    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 1,
-                      int(plateau is not None), int(pl.get("patience", 200)), float(pl.get("factor", 0.5)),
-                      float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)), float(pl.get("eps", 1e-8)), 0, 0, 0)
-    # the scheduler's numbers as the Python loop carries them (doubles)
     schedule = (C.c_double * 5)(float(lr), float(pl.get("factor", 0.5)), float(pl.get("threshold", 1e-4)), float(pl.get("min_lr", 0.0)),
                                 float(pl.get("eps", 1e-8)))
-    ws = _seq_ws(ispec, rspec, HW, T, batch_size, dev)
-    md, rd, ld = ispec.desc(), rspec.desc(), K._loss_desc(loss, weight_mode, ratio, 0.0, 0.0)
-    rc = L.load().inrfit_pcn_fit_sequence(C.byref(md), C.byref(rd), ip.data_ptr(), fp.data_ptr(), icnn_opt_state.data_ptr(),
-                                          flow_opt_state.data_ptr(), fc.data_ptr(), ft.data_ptr(), order, T, HW, int(batch_size),
-                                          num_epochs, C.byref(ld), C.byref(od), schedule, float(flow_weight_decay), 0,
-                                          epoch_loss.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                          K._stream_ptr(dev))
-    L.check(rc, "inrfit_pcn_fit_sequence")
+    X.call("inrfit_pcn_fit_sequence", ispec._desc, rspec._desc, ip, fp, icnn_opt_state, flow_opt_state, fc, ft, order, T, HW,
+           int(batch_size), num_epochs, X.loss_desc(loss, weight_mode, ratio, 0.0, 0.0), od, schedule, float(flow_weight_decay), 0,
+           epoch_loss, status, ws=_seq_ws(ispec, rspec, HW, T, batch_size, dev), device=dev)
     return PcnSequenceResult(ip, fp, icnn_opt_state, flow_opt_state, epoch_loss[:num_epochs], status)
 
 
@@ -385,20 +359,12 @@ def fit_identity_sequence(rspec: RnvpSpec, flow_params: Tensor, frame_coords: Te
                           flow_opt_state: Optional[Tensor] = None, step0: int = 0) -> Tuple[Tensor, Tensor]:
     """The mini-batched learn_flow_identity (path_connected_net.py:200-236) in ONE `inrfit_rnvp_fit_identity_sequence` call, in place
     on flow_params [1, RP]; frame_coords (T, C, HW).  Returns (loss_hist [num_epochs]: every epoch's LAST batch loss, opt_state)."""
-    fp, fc = K._check_dev(flow_params, "flow_params"), K._check_dev(frame_coords, "frame_coords")
+    fp = _flow_params(rspec, flow_params, 1)
     dev = fp.device
-    T, HW = int(fc.shape[0]), int(fc.shape[2])
-    num_epochs = int(torch.as_tensor(orders).reshape(-1, T).shape[0])
-    order = _orders_host(orders, num_epochs, T)
-    if flow_opt_state is None:
-        flow_opt_state = torch.zeros(1, 2 * rspec.n_params, dtype=torch.float32, device=dev)
+    fc, T, HW, num_epochs, order = _frames(rspec, frame_coords, orders)
+    flow_opt_state = _flow_opt_state(rspec, 1, dev, flow_opt_state)
+    X.on_gpu(flow_params=fp, frame_coords=fc, flow_opt_state=flow_opt_state)
     hist = L.scratch(max(num_epochs, 1), dtype=torch.float32, device=dev)
-    od = L.InrOptDesc(L.OPT_KINDS[optimizer], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 0, 0,
-                      0, 0.0, 0.0, 0.0, 0.0)
-    ws = _seq_ws(None, rspec, HW, T, batch_size, dev)
-    rd = rspec.desc()
-    rc = L.load().inrfit_rnvp_fit_identity_sequence(C.byref(rd), fp.data_ptr(), flow_opt_state.data_ptr(), fc.data_ptr(), order, T,
-                                                    HW, int(batch_size), num_epochs, C.byref(od), int(step0), hist.data_ptr(),
-                                                    ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_rnvp_fit_identity_sequence")
+    X.call("inrfit_rnvp_fit_identity_sequence", rspec._desc, fp, flow_opt_state, fc, order, T, HW, int(batch_size), num_epochs,
+           X.opt_desc(optimizer, lr, betas, eps, weight_decay), int(step0), hist, ws=_seq_ws(None, rspec, HW, T, batch_size, dev), device=dev)
     return hist[:num_epochs], flow_opt_state

@@ -4,14 +4,13 @@ kernels in csrc/star.h).  Mirrors notebooks/icml_teaser_code/star_shaped/star.ip
 Parameters travel as ONE flat vector in the order of the notebook class's named_parameters() (PARAM_ORDER)."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
-from . import icnn as K
 
 Tensor = torch.Tensor
 
@@ -62,57 +61,41 @@ def unflatten(spec: StarSpec, flat: Tensor) -> Dict[str, Tensor]:
 
 
 def _workspace(spec: StarSpec, n_points: int, dev) -> Tensor:
-    lib = L.load()
-    d = spec.desc()
-    nbytes = int(lib.inrfit_star_workspace_bytes(C.byref(d), int(n_points)))
-    if nbytes < 0:
-        L.check(nbytes, "inrfit_star_workspace_bytes")
-    return L.scratch(nbytes // 4 + 64, dtype=torch.float32, device=dev)
+    return X.workspace("inrfit_star_workspace_bytes", spec.desc(), int(n_points), device=dev, slack=64)
 
 
-def _check(params: Tensor, spec: StarSpec, coords: Tensor):
+def _check(params: Tensor, spec: StarSpec, coords: Tensor, labels: Optional[Tensor] = None):
     if not params.is_contiguous():
         raise ValueError("params must be one contiguous flat vector (it is updated in place)")
-    params = K._check_dev(params, "params")
-    coords = K._check_dev(coords, "coords")
-    if params.numel() != spec.n_params:
-        raise ValueError(f"params: expected {spec.n_params} floats, got {params.numel()}")
-    if coords.dim() != 2 or coords.shape[1] != 2:
-        raise ValueError(f"coords: expected (n_pixels, 2), got {tuple(coords.shape)}")
-    return params, coords
+    params = X.flat(params, "params", spec.n_params)
+    coords = X.rows(coords, "coords", None, 2)                  # (n_pixels, 2)
+    if labels is not None:
+        labels = X.flat(labels, "labels", coords.shape[0])      # one per pixel
+    return params, coords, labels
 
 
 def star_forward(spec: StarSpec, params: Tensor, coords: Tensor) -> Tensor:
     """logits [n] of every row of coords [n, 2] (cell 4 / 6 of the notebook: inference on all pixels)."""
-    params, coords = _check(params, spec, coords)
+    params, coords, _ = _check(params, spec, coords)
+    X.on_gpu(params=params, coords=coords)
     n, dev = coords.shape[0], params.device
     out = L.scratch(n, dtype=torch.float32, device=dev)
-    ws = _workspace(spec, n, dev)
-    d = spec.desc()
-    rc = L.load().inrfit_star_forward(C.byref(d), params.data_ptr(), coords.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                      K._stream_ptr(dev))
-    L.check(rc, "inrfit_star_forward")
+    X.call("inrfit_star_forward", spec.desc(), params, coords, n, out, ws=_workspace(spec, n, dev), device=dev)
     return out
 
 
 def star_loss_grad(spec: StarSpec, params: Tensor, coords: Tensor, labels: Tensor, index: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """(loss [1], grads [P]) of MSE(sigmoid(net(coords[index])), labels[index]); index None = every pixel."""
-    params, coords = _check(params, spec, coords)
-    labels = K._check_dev(labels, "labels")
+    params, coords, labels = _check(params, spec, coords, labels)
+    X.on_gpu(params=params, coords=coords, labels=labels)
     dev, npx = params.device, coords.shape[0]
-    if labels.numel() != npx:
-        raise ValueError("labels: one per pixel")
     if index is not None:
         index = index.to(device=dev, dtype=torch.int32).contiguous()
     batch = int(index.numel()) if index is not None else npx
     loss = L.scratch(1, dtype=torch.float32, device=dev)
     grads = L.scratch(spec.n_params, dtype=torch.float32, device=dev)
-    ws = _workspace(spec, batch, dev)
-    d = spec.desc()
-    rc = L.load().inrfit_star_loss_grad(C.byref(d), params.data_ptr(), coords.data_ptr(), labels.data_ptr(), npx,
-                                        index.data_ptr() if index is not None else None, batch, loss.data_ptr(), grads.data_ptr(),
-                                        ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_star_loss_grad")
+    X.call("inrfit_star_loss_grad", spec.desc(), params, coords, labels, npx, index, batch, loss, grads, ws=_workspace(spec, batch, dev),
+           device=dev)
     return loss, grads
 
 
@@ -129,29 +112,24 @@ def star_fit(spec: StarSpec, params: Tensor, coords: Tensor, labels: Tensor, bat
     """The loop of star.ipynb cell 3 on the device: epoch e = step0 + k takes the minibatch batch_index[k] ([steps, batch] pixel numbers),
     Adam(lr) on every parameter IN PLACE, then W2_r.weight <- relu(W2_r.weight).  `offset` takes its first step at epoch
     offset_first_step (the notebook: requires_grad after the forward of epoch 1000 -> 1001; < 0: never)."""
-    params, coords = _check(params, spec, coords)
-    labels = K._check_dev(labels, "labels")
+    params, coords, labels = _check(params, spec, coords, labels)
     dev, npx = params.device, coords.shape[0]
-    if labels.numel() != npx:
-        raise ValueError("labels: one per pixel")
     if batch_index.dim() != 2:
         raise ValueError("batch_index: expected (steps, batch)")
-    batch_index = batch_index.to(device=dev, dtype=torch.int32).contiguous()
     steps, batch = int(batch_index.shape[0]), int(batch_index.shape[1])
     if batch < 1 or batch > MAX_BATCH:
         raise ValueError(f"batch must be in [1, {MAX_BATCH}]")
     if opt_state is None:
         opt_state = torch.zeros(2 * spec.n_params, dtype=torch.float32, device=dev)
-    assert opt_state.numel() == 2 * spec.n_params and opt_state.is_contiguous() and opt_state.device == dev
+    if not opt_state.is_contiguous() or opt_state.device != dev:
+        raise ValueError("opt_state must be contiguous (it is updated in place) and live on the parameters' device")
+    opt_state = X.flat(opt_state, "opt_state", 2 * spec.n_params)
+    X.on_gpu(params=params, coords=coords, labels=labels, opt_state=opt_state)
+    batch_index = batch_index.to(device=dev, dtype=torch.int32).contiguous()
     hist = L.scratch(max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    ws = _workspace(spec, batch, dev)
-    d = spec.desc()
-    od = L.InrOptDesc(L.OPT_KINDS["adam"], float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 0, 0, 0, 1.0, 0.0, 0.0, 0.0, 0, 0, 0)
-    rc = L.load().inrfit_star_fit(C.byref(d), params.data_ptr(), opt_state.data_ptr(), coords.data_ptr(), labels.data_ptr(), npx,
-                                  batch_index.data_ptr(), batch, C.byref(od), steps, int(step0), int(offset_first_step),
-                                  hist.data_ptr() if hist is not None else None, ws.data_ptr(), ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_star_fit")
-    return StarFitResult(params, opt_state, hist[:steps] if hist is not None else None)
+    X.call("inrfit_star_fit", spec.desc(), params, opt_state, coords, labels, npx, batch_index, batch, X.opt_desc("adam", lr, betas, eps),
+           steps, int(step0), int(offset_first_step), hist, ws=_workspace(spec, batch, dev), device=dev)
+    return StarFitResult(params, opt_state, X.trim(hist, steps))
 
 
 def notebook_minibatches(labels: Tensor, steps: int, number: int = 500, generator: Optional[torch.Generator] = None,

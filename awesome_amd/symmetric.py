@@ -9,12 +9,12 @@ image, `pose [n_images, 3]` = offset[2] | orientation, with `pose_opt_state [n_i
 `sym_fit(steps=1, step0=step0 + k)` launches on the gathered rows, so a finite run ends bit for bit where the per-step loop ends."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import torch
 
+from . import _call as X
 from . import _lib as L
 from . import icnn as K
 from . import minibatch as MB
@@ -37,12 +37,8 @@ def _check(spec: K.IcnnSpec, params: Tensor, pose: Tensor) -> Tuple[Tensor, Tens
     K._check_spec(spec)
     if spec.in_features != 3 or spec.n_out != 1:
         raise ValueError("the network behind the pose reads the 3 features (u, v, r) and has one output")
-    params, pose = K._check_dev(params, "params"), K._check_dev(pose, "pose")
-    if params.dim() != 2 or params.shape[1] != spec.n_params:
-        raise ValueError("params must be [n_images, P]")
-    if tuple(pose.shape) != (params.shape[0], 3):
-        raise ValueError("pose must be [n_images, 3] (offset[2] | orientation)")
-    return params, pose, int(params.shape[0])
+    params = X.rows(params, "params", None, spec.n_params)
+    return params, X.rows(pose, "pose", params.shape[0], 3), int(params.shape[0])   # pose: offset[2] | orientation
 
 
 def _grid(grid: K.Grid) -> K.Grid:
@@ -52,11 +48,7 @@ def _grid(grid: K.Grid) -> K.Grid:
 
 
 def _ws(spec: K.IcnnSpec, grid: K.Grid, n_images: int) -> Tensor:
-    md, gd = spec.desc(), grid.desc()
-    nbytes = L.load().inrfit_sym_workspace_bytes(C.byref(md), C.byref(gd), n_images)
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_sym_workspace_bytes")
-    return L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=grid.device)
+    return X.workspace("inrfit_sym_workspace_bytes", spec._desc, grid._desc, n_images, device=grid.device)
 
 
 def _sym_desc(symmetry_from_step: int, r_eps: float) -> L.InrSymDesc:
@@ -71,12 +63,10 @@ def sym_forward(spec: K.IcnnSpec, params: Tensor, pose: Tensor, grid: K.Grid, sy
     """logits [n_images, N] of pose + network on the 2-channel grid, with or without the mirror."""
     params, pose, n = _check(spec, params, pose)
     grid = _grid(grid)
+    X.on_gpu(params=params, pose=pose)
     logits = L.scratch(n, grid.n_points, dtype=torch.float32, device=params.device)
-    ws = _ws(spec, grid, n)
-    md, sd, gd = spec.desc(), _sym_desc(-1, r_eps), grid.desc()
-    rc = L.load().inrfit_sym_forward(C.byref(md), C.byref(sd), params.data_ptr(), pose.data_ptr(), C.byref(gd), n, int(bool(symmetry_prior)),
-                                     logits.data_ptr(), ws.data_ptr(), ws.numel() * 4, K._stream_ptr(params.device))
-    L.check(rc, "inrfit_sym_forward")
+    X.call("inrfit_sym_forward", spec._desc, _sym_desc(-1, r_eps), params, pose, grid._desc, n, int(bool(symmetry_prior)), logits,
+           ws=_ws(spec, grid, n), device=params.device)
     return logits
 
 
@@ -86,15 +76,13 @@ def sym_loss_grad(spec: K.IcnnSpec, params: Tensor, pose: Tensor, grid: K.Grid, 
     """-> (loss [n_images], network gradients [n_images, P], pose gradients [n_images, 3])."""
     params, pose, n = _check(spec, params, pose)
     grid = _grid(grid)
-    targets = K._check_dev(targets, "targets").reshape(n, -1)
+    targets = K._per_point(spec, targets, "targets", n, grid)
+    X.on_gpu(params=params, pose=pose, targets=targets)
     lo = L.scratch(n, dtype=torch.float32, device=params.device)
     g, gp = L.scratch_like(params), L.scratch_like(pose)
-    ws = _ws(spec, grid, n)
-    md, sd, gd, ld = spec.desc(), _sym_desc(-1, r_eps), grid.desc(), K._loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_sym_loss_grad(C.byref(md), C.byref(sd), params.data_ptr(), pose.data_ptr(), C.byref(gd), targets.data_ptr(),
-                                       C.byref(ld), n, int(bool(symmetry_prior)), lo.data_ptr(), g.data_ptr(), gp.data_ptr(), ws.data_ptr(),
-                                       ws.numel() * 4, K._stream_ptr(params.device))
-    L.check(rc, "inrfit_sym_loss_grad")
+    X.call("inrfit_sym_loss_grad", spec._desc, _sym_desc(-1, r_eps), params, pose, grid._desc, targets,
+           X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), n, int(bool(symmetry_prior)), lo, g, gp, ws=_ws(spec, grid, n),
+           device=params.device)
     return lo, g, gp
 
 
@@ -103,7 +91,13 @@ def _states(spec, n, dev, opt_state, pose_opt_state):
         opt_state = K.new_opt_state(spec, n, dev)
     if pose_opt_state is None:
         pose_opt_state = new_pose_opt_state(n, dev)
-    return opt_state, K._check_dev(pose_opt_state, "pose_opt_state")
+    return (X.rows(opt_state, "opt_state", n, 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS),
+            X.rows(pose_opt_state, "pose_opt_state", n, 6))
+
+
+def _opt_desc(lr, betas, eps, weight_decay, plateau) -> L.InrOptDesc:
+    """ONE Adam over pose and an unconstrained MLP: no projection, the skip weights stay where they are."""
+    return X.opt_desc("adam", lr, betas, eps, weight_decay, clamp=False, plateau=plateau, freeze_skips=True)
 
 
 def sym_fit(spec: K.IcnnSpec, params: Tensor, pose: Tensor, grid: K.Grid, targets: Tensor, steps: int, lr: float = 1e-3,
@@ -116,19 +110,14 @@ def sym_fit(spec: K.IcnnSpec, params: Tensor, pose: Tensor, grid: K.Grid, target
     params, pose, n = _check(spec, params, pose)
     grid = _grid(grid)
     dev = params.device
-    targets = K._check_dev(targets, "targets").reshape(n, -1)
+    targets = K._per_point(spec, targets, "targets", n, grid)
     opt_state, pose_opt_state = _states(spec, n, dev, opt_state, pose_opt_state)
-    hist = L.scratch(n, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    od = MB._opt_desc("adam", lr, betas, eps, weight_decay, False, plateau, True, False)
-    ws = _ws(spec, grid, n)
-    md, sd, gd, ld = spec.desc(), _sym_desc(symmetry_from_step, r_eps), grid.desc(), K._loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_sym_fit(C.byref(md), C.byref(sd), params.data_ptr(), pose.data_ptr(), opt_state.data_ptr(),
-                                 pose_opt_state.data_ptr(), C.byref(gd), targets.data_ptr(), C.byref(ld), C.byref(od), n, int(steps),
-                                 int(step0), hist.data_ptr() if hist is not None else None, status.data_ptr(), ws.data_ptr(),
-                                 ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_sym_fit")
-    return SymFitResult(params, pose, opt_state, pose_opt_state, hist[:, :steps] if hist is not None else None, status)
+    X.on_gpu(params=params, pose=pose, targets=targets, opt_state=opt_state, pose_opt_state=pose_opt_state)
+    hist, _, status = X.fit_outputs(n, steps, None, record_loss, False, dev)
+    X.call("inrfit_sym_fit", spec._desc, _sym_desc(symmetry_from_step, r_eps), params, pose, opt_state, pose_opt_state, grid._desc,
+           targets, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), _opt_desc(lr, betas, eps, weight_decay, plateau), n, int(steps),
+           int(step0), hist, status, ws=_ws(spec, grid, n), device=dev)
+    return SymFitResult(params, pose, opt_state, pose_opt_state, X.trim(hist, steps), status)
 
 
 def sym_fit_minibatch(spec: K.IcnnSpec, params: Tensor, pose: Tensor, pool_coords: Tensor, pool_targets: Tensor, index: Tensor,
@@ -142,29 +131,13 @@ def sym_fit_minibatch(spec: K.IcnnSpec, params: Tensor, pose: Tensor, pool_coord
     contract).  No final logits (`sym_forward`)."""
     params, pose, n = _check(spec, params, pose)
     dev = params.device
-    pool_coords = K._check_dev(pool_coords, "pool_coords")
-    pool_targets = K._check_dev(pool_targets, "pool_targets")
-    if pool_coords.dim() != 2 or pool_coords.shape[0] != 2:
-        raise ValueError("pool_coords must be [2, n_pool] (shared by all images)")
-    n_pool = int(pool_coords.shape[1])
-    pool_targets = pool_targets.reshape(n, -1)
-    if pool_targets.shape[1] != n_pool:
-        raise ValueError(f"pool_targets must be [n_images, n_pool], got {tuple(pool_targets.shape)}")
-    index, carr, steps, batch = MB._table(index, counts, dev)
+    pool_coords, pool_targets, n_pool = MB._pool(spec, n, pool_coords, pool_targets, channels=2)
     opt_state, pose_opt_state = _states(spec, n, dev, opt_state, pose_opt_state)
-    md = spec.desc()
-    nbytes = L.load().inrfit_sym_minibatch_workspace_bytes(C.byref(md), batch, n)
-    if nbytes < 0:
-        L.check(int(nbytes), "inrfit_sym_minibatch_workspace_bytes")
-    ws = L.scratch(int(nbytes) // 4 + 1, dtype=torch.float32, device=dev)
-    hist = L.scratch(n, max(steps, 1), dtype=torch.float32, device=dev) if record_loss else None
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    od = MB._opt_desc("adam", lr, betas, eps, weight_decay, False, plateau, True, False)
-    sd, ld = _sym_desc(symmetry_from_step, r_eps), K._loss_desc(loss, weight_mode, ratio, c_fg, c_bg)
-    rc = L.load().inrfit_sym_fit_minibatch(C.byref(md), C.byref(sd), params.data_ptr(), pose.data_ptr(), opt_state.data_ptr(),
-                                           pose_opt_state.data_ptr(), pool_coords.data_ptr(), pool_targets.data_ptr(), n_pool,
-                                           index.data_ptr(), carr, batch, C.byref(ld), C.byref(od), n, steps, int(step0),
-                                           hist.data_ptr() if hist is not None else None, status.data_ptr(), ws.data_ptr(),
-                                           ws.numel() * 4, K._stream_ptr(dev))
-    L.check(rc, "inrfit_sym_fit_minibatch")
-    return SymFitResult(params, pose, opt_state, pose_opt_state, hist[:, :steps] if hist is not None else None, status)
+    X.on_gpu(params=params, pose=pose, pool_coords=pool_coords, pool_targets=pool_targets, opt_state=opt_state, pose_opt_state=pose_opt_state)
+    index, carr, steps, batch = MB._table(index, counts, dev)
+    ws = X.workspace("inrfit_sym_minibatch_workspace_bytes", spec._desc, batch, n, device=dev)
+    hist, _, status = X.fit_outputs(n, steps, None, record_loss, False, dev)
+    X.call("inrfit_sym_fit_minibatch", spec._desc, _sym_desc(symmetry_from_step, r_eps), params, pose, opt_state, pose_opt_state,
+           pool_coords, pool_targets, n_pool, index, carr, batch, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg),
+           _opt_desc(lr, betas, eps, weight_decay, plateau), n, steps, int(step0), hist, status, ws=ws, device=dev)
+    return SymFitResult(params, pose, opt_state, pose_opt_state, X.trim(hist, steps), status)

@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
+from . import _call as X
 from . import _lib as L
 from .icnn import _check_dev, _stream_ptr
 
@@ -75,10 +76,7 @@ def _workspace(net, desc, dev) -> Tensor:
     cache = net.__dict__.setdefault(_CACHE, {})
     key = (desc.height, desc.width, desc.strip_points, str(dev))
     if cache.get("ws_key") != key:
-        nbytes = int(L.load().inrfit_unet_workspace_bytes(C.byref(desc)))
-        if nbytes < 0:
-            L.check(nbytes, "inrfit_unet_workspace_bytes")
-        cache["ws"], cache["ws_key"] = L.scratch(nbytes // 4, dtype=torch.float32, device=dev), key
+        cache["ws"], cache["ws_key"] = X.workspace("inrfit_unet_workspace_bytes", desc, device=dev, slack=0), key
     return cache["ws"]
 
 
@@ -94,15 +92,12 @@ def unet_forward(net, image: Tensor, features: Optional[Tensor], strip_points: i
         raise L.InrfitError(f"the UNet takes {net.in_chn} input channels, got {c}")
     dev = x.device
     desc = make_desc(net, H, W, strip_points)
-    lib = L.load()
     with torch.cuda.device(dev):
         packed = packed_weights(net, dev)
         ws = _workspace(net, desc, dev)
         out = L.scratch(B, int(net.out_chn), H, W, dtype=torch.float32, device=dev)
         for b in range(B):
-            rc = lib.inrfit_unet_forward(C.byref(desc), packed.data_ptr(), x[b].data_ptr(), out[b].data_ptr(), ws.data_ptr(),
-                                         ws.numel() * 4, _stream_ptr(dev))
-            L.check(rc, "inrfit_unet_forward")
+            X.call("inrfit_unet_forward", desc, packed, x[b], out[b], ws=ws, device=dev)
     return out
 
 
@@ -126,10 +121,7 @@ def _train_workspace(net, desc, dev) -> Tensor:
     cache = net.__dict__.setdefault(_CACHE, {})
     key = (desc.height, desc.width, desc.strip_points, str(dev))
     if cache.get("train_key") != key or cache.get("train_busy"):
-        nbytes = int(L.load().inrfit_unet_train_workspace_bytes(C.byref(desc)))
-        if nbytes < 0:
-            L.check(nbytes, "inrfit_unet_train_workspace_bytes")
-        cache["train_ws"], cache["train_key"] = L.scratch(nbytes // 4, dtype=torch.float32, device=dev), key
+        cache["train_ws"], cache["train_key"] = X.workspace("inrfit_unet_train_workspace_bytes", desc, device=dev, slack=0), key
     cache["train_busy"] = True
     return cache["train_ws"]
 
@@ -151,7 +143,6 @@ class UNetTrainFunction(torch.autograd.Function):
         dev = x.device
         _, c, H, W = x.shape
         desc = make_desc(net, H, W, strip_points)
-        lib = L.load()
         momentum = train_momentum(net)
         if momentum is None:
             raise L.InrfitError("the UNet's BatchNorms must share one eps and one float momentum and carry affine weights and running statistics")
@@ -162,9 +153,7 @@ class UNetTrainFunction(torch.autograd.Function):
             tables = _train_tables(net, params)
             means, variances = _table([bn.running_mean for bn in bns]), _table([bn.running_var for bn in bns])
             logits = L.scratch(1, int(net.out_chn), H, W, dtype=torch.float32, device=dev)
-            rc = lib.inrfit_unet_train_forward(C.byref(desc), *[t[0] for t in tables], means[0], variances[0], momentum, x.data_ptr(),
-                                               logits.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
-            L.check(rc, "inrfit_unet_train_forward")
+            X.call("inrfit_unet_train_forward", desc, *[t[0] for t in tables], means[0], variances[0], momentum, x, logits, ws=ws, device=dev)
             for bn in bns:
                 bn.num_batches_tracked.add_(1)
         net.__dict__[_CACHE].pop("sig", None)      # the running statistics changed under the evaluation pass's packed weights
@@ -188,9 +177,7 @@ class UNetTrainFunction(torch.autograd.Function):
             n = int(lib.inrfit_unet_param_count(C.byref(desc)))
             grads = L.scratch(n, dtype=torch.float32, device=dev)
             tables = _train_tables(net, params)
-            rc = lib.inrfit_unet_train_backward(C.byref(desc), *[t[0] for t in tables], x.data_ptr(), dlogits.data_ptr(), grads.data_ptr(),
-                                                ws.data_ptr(), ws.numel() * 4, _stream_ptr(dev))
-            L.check(rc, "inrfit_unet_train_backward")
+            X.call("inrfit_unet_train_backward", desc, *[t[0] for t in tables], x, dlogits, grads, ws=ws, device=dev)
         cache = net.__dict__.get(_CACHE, {})
         if cache.get("train_ws") is ws:
             cache["train_busy"] = False
