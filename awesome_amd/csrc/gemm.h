@@ -401,23 +401,32 @@ inline int gemm_vec_width(const float* p, int ld) {
     return 1;
 }
 
-// row-major C[M x N] = op(A) op(B); `splits` > 1 cuts K into that many z-slices of k_per_split (multiple of 16) writing
-// C + z * c_split_stride.  Returns INR_OK / INR_ELAUNCH.
-inline int gemm_launch(hipStream_t s, bool tA, bool tB, GemmArgs g) {
-    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return INR_EINVAL;
-    if (g.k_per_split <= 0) g.k_per_split = (g.K + GM_BK - 1) / GM_BK * GM_BK;
-    const int splits = (g.K + g.k_per_split - 1) / g.k_per_split;
+// which instantiation a launch takes: fills g.vecA / g.vecB, clears g.buf where 32-bit byte offsets do not reach, and returns MODE
+// (0 general, 1 V4, 2 V4 through buffer descriptors).  Host arithmetic on sizes and pointer values only (g.k_per_split is set).
+inline int gemm_pick_mode(bool tA, bool tB, GemmArgs& g) {
     g.vecA = gemm_vec_width(g.A, g.lda);
     g.vecB = gemm_vec_width(g.B, g.ldb);
-    const dim3 grid((g.N + GM_BN - 1) / GM_BN, (g.M + GM_BM - 1) / GM_BM, splits);
     // 16-byte loads throughout: aligned operands whose contiguous extent is a multiple of 4 floats or may be read up to the next one
     // (a split contraction ends inside the rows of an operand contiguous along k: always readable)
     const int contigA = tA ? g.M : g.K, contigB = tB ? g.K : g.N;
     if (g.buf && ((long long)(tA ? g.K : g.M) * g.lda * 4 >= (1ll << 31) || (long long)(tB ? g.N : g.K) * g.ldb * 4 >= (1ll << 31))) g.buf = 0;   // (32-bit byte offsets)
     const bool v4 = g.vecA == 4 && g.vecB == 4 && ((contigA & 3) == 0 || g.padA) && ((contigB & 3) == 0 || g.padB) && (g.k_per_split & 3) == 0;
+    return v4 && g.buf ? 2 : (v4 ? 1 : 0);
+}
+
+// row-major C[M x N] = op(A) op(B); `splits` > 1 cuts K into that many z-slices of k_per_split (multiple of 16) writing
+// C + z * c_split_stride.  Returns INR_OK / INR_ELAUNCH; INR_EINVAL for a non-positive extent, an epilogue on another operand form than
+// its own, or a split contraction whose slices are no multiple of GM_BK (a slice's last k-step would read into the next slice: the
+// kernel bounds k by the slice's end only where it selects, and the buffer mode does not select).
+inline int gemm_launch(hipStream_t s, bool tA, bool tB, GemmArgs g) {
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return INR_EINVAL;
+    if (g.k_per_split <= 0) g.k_per_split = (g.K + GM_BK - 1) / GM_BK * GM_BK;
+    const int splits = (g.K + g.k_per_split - 1) / g.k_per_split;
+    if (splits > 1 && g.k_per_split % GM_BK != 0) return INR_EINVAL;
+    const dim3 grid((g.N + GM_BN - 1) / GM_BN, (g.M + GM_BM - 1) / GM_BM, splits);
     // epilogues other than the plain store exist for the products that use them: HIDDEN on A . B^T (a layer's forward), MASK on A . B (its
     // backward); each kernel holds the code of ONE epilogue
-    const int mode = v4 && g.buf ? 2 : (v4 ? 1 : 0);
+    const int mode = gemm_pick_mode(tA, tB, g);
     if (g.epi == GEMM_EPI_HIDDEN && !(!tA && tB)) return INR_EINVAL;
     if (g.epi == GEMM_EPI_MASK && !(!tA && !tB)) return INR_EINVAL;
 #define GEMM_GO3(TA_, TB_, EPI_)                                                                          \
