@@ -240,6 +240,15 @@ EXPORTS = {
     "inrfit_star_fit": (C.c_int, [C.POINTER(InrStarDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_int64, C.POINTER(InrOptDesc), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.c_void_p]),
+    "inrfit_star_dense_tile_points": (C.c_int32, []),
+    "inrfit_star_opt_state_floats": (C.c_int64, [C.POINTER(InrStarDesc)]),
+    "inrfit_star_dense_workspace_bytes": (C.c_int64, [C.POINTER(InrStarDesc), C.c_int64, C.c_int32]),
+    "inrfit_star_fit_dense": (C.c_int, [C.POINTER(InrStarDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_star_loss_grad_dense": (C.c_int, [C.POINTER(InrStarDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.POINTER(InrLossDesc), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.c_void_p]),
     "inrfit_debug_tanh_exp": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "inrfit_miou": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_void_p,
                               C.c_void_p]),

@@ -135,6 +135,41 @@ def _layer_by_layer_joint(ispec) -> bool:
     return ispec.supported() and not ispec.fused() and not ispec.general and ispec.act0 == "relu"
 
 
+def _fused_prior_family(prior, kind: str, fused_layer_by_layer: bool):
+    """Which fused joint step serves `prior` under optimizer `kind`: (family, ispec, dspec, wide), or None = the autograd step.
+    Host logic only (no device), so the routing of a model class can be checked anywhere."""
+    from .model.star_net import StarShapedNet
+    if isinstance(prior, StarShapedNet):
+        # its `spec` describes the ICNN calls of the autograd bridge, NOT its parameter vector (awesome_amd/star.py PARAM_ORDER): the
+        # fused ICNN step would run over another layout.  No fused joint step for the star prior: autograd through its forward.
+        return None
+    if hasattr(prior, "_specs"):
+        try:
+            ispec, dspec = prior._specs()
+        except NotImplementedError:   # no fused form of this composite at all ('resnet' flow backbone): autograd step
+            return None
+        family = "pcn" if type(dspec).__name__ == "RnvpSpec" else "cdn"
+        wide = not ispec.fused()
+        # its ICNN runs layer by layer: the composite's autograd bridges - unless asked for (fused_layer_by_layer) and the
+        # composite is a PathConnectedNet (inrfit_pcn_wide_joint_step; ConvexDiffeomorphismNet has no such step)
+        if wide and not (fused_layer_by_layer and family == "pcn" and _layer_by_layer_joint(ispec)):
+            return None
+        if kind != "adam" and family == "cdn":
+            return None
+    elif hasattr(prior, "spec"):
+        ispec, dspec, family = prior.spec, None, "icnn"
+        wide = not ispec.fused()
+        # n_hidden > 130 or L > 2: inrfit_joint_step has no kernel (INR_EUNSUPPORTED); autograd step (ADVICE r03) - unless asked
+        # for (fused_layer_by_layer: inrfit_wide_joint_step / inrfit_wide_joint_prior_step)
+        if wide and not (fused_layer_by_layer and _layer_by_layer_joint(ispec)):
+            return None
+        if getattr(prior, "fit_options", None):   # FCNet / encode nets: frozen ranges, no clamp - not part of the joint configs
+            return None
+    else:
+        return None
+    return family, ispec, dspec, wide
+
+
 def _prior_grid(prior_args, pixel: bool):
     """The prior's coordinates (WrapperModule.get_prior_args) as the kernels' explicit grid, (2, n) float32."""
     from . import icnn as K
@@ -361,30 +396,10 @@ class JointTrainer:
             return None
         if not pids <= {id(p) for p in groups[0]["params"]}:
             return None
-        if hasattr(prior, "_specs"):
-            try:
-                ispec, dspec = prior._specs()
-            except NotImplementedError:   # no fused form of this composite at all ('resnet' flow backbone): autograd step
-                return None
-            family = "pcn" if type(dspec).__name__ == "RnvpSpec" else "cdn"
-            wide = not ispec.fused()
-            # its ICNN runs layer by layer: the composite's autograd bridges - unless asked for (fused_layer_by_layer) and the
-            # composite is a PathConnectedNet (inrfit_pcn_wide_joint_step; ConvexDiffeomorphismNet has no such step)
-            if wide and not (self.fused_layer_by_layer and family == "pcn" and _layer_by_layer_joint(ispec)):
-                return None
-            if kind != "adam" and family == "cdn":
-                return None
-        elif hasattr(prior, "spec"):
-            ispec, dspec, family = prior.spec, None, "icnn"
-            wide = not ispec.fused()
-            # n_hidden > 130 or L > 2: inrfit_joint_step has no kernel (INR_EUNSUPPORTED); autograd step - unless asked
-            # for (fused_layer_by_layer: inrfit_wide_joint_step / inrfit_wide_joint_prior_step)
-            if wide and not (self.fused_layer_by_layer and _layer_by_layer_joint(ispec)):
-                return None
-            if getattr(prior, "fit_options", None):   # FCNet / encode nets: frozen ranges, no clamp - not part of the joint configs
-                return None
-        else:
+        fam = _fused_prior_family(prior, kind, self.fused_layer_by_layer)
+        if fam is None:
             return None
+        family, ispec, dspec, wide = fam
         if not hasattr(self.criterion, "joint_desc") or self.criterion.joint_desc() is None:
             if not self._convexity_applies(family):
                 return None

@@ -3546,6 +3546,116 @@ int inrfit_star_fit(const InrStarDesc* star, float* params, float* opt_state, co
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
+// ---- the dense full-batch form (csrc/star.h: tiles of STAR_DENSE_TILE points, accumulated in tile order) ------------------------------
+int32_t inrfit_star_dense_tile_points(void) { return STAR_DENSE_TILE; }
+
+int64_t inrfit_star_opt_state_floats(const InrStarDesc* star) {
+    if (!star || star->n_hidden < 1 || star->n_hidden > STAR_MAX_HIDDEN) return INR_EUNSUPPORTED;
+    return 2 * (int64_t)make_star_map(star->n_hidden).P + INR_OPT_HEADER_FLOATS;
+}
+
+int64_t inrfit_star_dense_workspace_bytes(const InrStarDesc* star, int64_t n_pixels, int32_t n_images) {
+    if (!star || star->n_hidden < 1 || star->n_hidden > STAR_MAX_HIDDEN) return INR_EUNSUPPORTED;
+    if (n_pixels <= 0 || n_images <= 0) return INR_EINVAL;
+    return carve_star_dense(star->n_hidden, n_pixels, n_images, nullptr).bytes;
+}
+
+// everything the two dense entry points share in front of their first HIP call
+static int check_star_dense(const InrStarDesc* star, const float* params, const float* coords, int64_t coords_image_stride,
+                            const float* targets, const InrLossDesc* loss, int64_t n_pixels, int32_t n_images, void* workspace,
+                            int64_t workspace_bytes, StarMap* m, StarDenseWs* w) {
+    if (!star || star->n_hidden < 1 || star->n_hidden > STAR_MAX_HIDDEN) return INR_EUNSUPPORTED;
+    if (!params || !coords || !targets || !loss || !workspace || n_pixels <= 0 || n_images <= 0) return INR_EINVAL;
+    if (coords_image_stride != 0 && coords_image_stride < 2 * n_pixels) return INR_EINVAL;
+    if (loss->kind != INR_LOSS_SE && loss->kind != INR_LOSS_BCE) return INR_EINVAL;
+    if (loss->weight_mode < INR_WEIGHT_NONE || loss->weight_mode > INR_WEIGHT_EXPLICIT) return INR_EINVAL;
+    *m = make_star_map(star->n_hidden);
+    *w = carve_star_dense(star->n_hidden, n_pixels, n_images, workspace);
+    if (workspace_bytes < w->bytes) return INR_EWORKSPACE;
+    return INR_OK;
+}
+
+int inrfit_star_loss_grad_dense(const InrStarDesc* star, const float* params, const float* coords, int64_t coords_image_stride,
+                                const float* targets, const InrLossDesc* loss, int64_t n_pixels, int32_t n_images, float* loss_out,
+                                float* grads, void* workspace, int64_t workspace_bytes, void* stream) {
+    StarMap m;
+    StarDenseWs w;
+    if (!loss_out || !grads) return INR_EINVAL;
+    int rc = check_star_dense(star, params, coords, coords_image_stride, targets, loss, n_pixels, n_images, workspace, workspace_bytes, &m, &w);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)n_pixels, *loss, w.coef, 1.f);
+    StarDenseUpdArgs u{};
+    u.gW1 = w.gW1;
+    u.col = w.col;
+    u.scal = w.scal;
+    u.m = m;
+    u.mode = 1;
+    for (int img = 0; img < n_images; ++img) {
+        const float* prm = params + (size_t)img * m.P;
+        if ((rc = star_dense_pass(m, w, prm, coords + (size_t)img * coords_image_stride, targets + (size_t)img * n_pixels, w.coef + 2 * img,
+                                  loss->kind, n_pixels, nullptr, true, s)))
+            return rc;
+        u.grads_out = grads + (size_t)img * m.P;
+        u.loss_out = loss_out + img;
+        hipLaunchKernelGGL(star_dense_update_kernel, dim3((m.P + 1 + 255) / 256), dim3(256), 0, s, u);
+    }
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
+int inrfit_star_fit_dense(const InrStarDesc* star, float* params, float* opt_state, const float* coords, int64_t coords_image_stride,
+                          const float* targets, const InrLossDesc* loss, const InrOptDesc* opt, int64_t n_pixels, int32_t n_images,
+                          int32_t steps, int32_t step0, int32_t offset_first_step, float* loss_hist, float* final_logits, int32_t* status,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+    StarMap m;
+    StarDenseWs w;
+    if (!opt_state || !opt || !status || steps < 0 || step0 < 0) return INR_EINVAL;
+    if (opt->kind != INR_OPT_ADAM && opt->kind != INR_OPT_ADAMAX) return INR_EINVAL;
+    if (opt->weight_decay != 0.f || opt->clamp || opt->freeze_skips || opt->freeze_input) return INR_EINVAL;   // not part of this prior
+    int rc = check_star_dense(star, params, coords, coords_image_stride, targets, loss, n_pixels, n_images, workspace, workspace_bytes, &m, &w);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(status, 0, sizeof(int32_t) * n_images, s) != hipSuccess) return INR_ELAUNCH;
+    hipLaunchKernelGGL(opt_init_kernel, dim3(n_images), dim3(32), 0, s, opt_state, m.P, *opt, (int)step0);
+    hipLaunchKernelGGL(loss_coef_kernel, dim3(n_images), dim3(256), 0, s, targets, (long long)n_pixels, *loss, w.coef, 1.f);
+    StarDenseUpdArgs u{};
+    u.gW1 = w.gW1;
+    u.col = w.col;
+    u.scal = w.scal;
+    u.m = m;
+    u.od = *opt;
+    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
+    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
+    u.mode = 0;
+    for (int img = 0; img < n_images; ++img) {
+        float* prm = params + (size_t)img * m.P;
+        const float* xy = coords + (size_t)img * coords_image_stride;
+        const float* tg = targets + (size_t)img * n_pixels;
+        float* lg = final_logits ? final_logits + (size_t)img * n_pixels : nullptr;
+        u.prm = prm;
+        u.opt = opt_state + (size_t)img * (2 * (size_t)m.P + INR_OPT_HEADER_FLOATS);
+        u.status = status + img;
+        for (int it = 0; it < steps; ++it) {
+            const int ep = step0 + it;
+            const bool gate = lg && opt->logits_at_last_forward && it == steps - 1;
+            if ((rc = star_dense_pass(m, w, prm, xy, tg, w.coef + 2 * img, loss->kind, n_pixels, gate ? lg : nullptr, true, s))) return rc;
+            const int t_off = offset_first_step >= 0 && ep >= offset_first_step ? ep - offset_first_step + 1 : 0;
+            u.t = ep + 1;
+            bias_corrections(opt, u.t, &u.bc1, &u.bc2_sqrt);
+            u.offset_on = t_off > 0;
+            u.bc1_off = 1.0;
+            u.bc2_sqrt_off = 1.f;
+            if (t_off > 0) bias_corrections(opt, t_off, &u.bc1_off, &u.bc2_sqrt_off);
+            u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps + it : nullptr;
+            hipLaunchKernelGGL(star_dense_update_kernel, dim3((m.P + 1 + 255) / 256), dim3(256), 0, s, u);
+        }
+        if (lg && (!opt->logits_at_last_forward || steps == 0)) {   // the logits at the final parameters: one more forward
+            if ((rc = star_dense_pass(m, w, prm, xy, nullptr, nullptr, loss->kind, n_pixels, lg, false, s))) return rc;
+        }
+    }
+    return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
+}
+
 __global__ __launch_bounds__(256) void debug_tanh_exp_kernel(const float* __restrict__ x, long long n, float* __restrict__ th,
                                                               float* __restrict__ ex) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

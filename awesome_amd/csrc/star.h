@@ -96,11 +96,15 @@ __global__ __launch_bounds__(256) void star_l1_kernel(const float* __restrict__ 
 
 // read-out, sigmoid, squared error and dL/dout: one wave per point, four points per block.
 // labels == null: forward only (logits out).  partial: [blocks][2] = (sum of squared errors, sum of ds) of the block's points.
+// DENSE (the full-batch fits below): the criterion is the ICNN fits' data term (wide_data_term: SE / BCE on the sigmoid with the class
+// coefficient coef[0] (target < 0.5) / coef[1], 'mean' normalisation included), labels / logits are this tile's rows, no index.
+template <bool DENSE>
 __global__ __launch_bounds__(256) void star_out_kernel(const float* __restrict__ prm, const StarMap m, const float* __restrict__ feat,
                                                        const float* __restrict__ A0, const float* __restrict__ A1,
                                                        const float* __restrict__ labels, const int32_t* __restrict__ idx,
                                                        const long long n_pixels, const long long N, float* __restrict__ logits, float* __restrict__ ds, float* __restrict__ drd,
-                                                       float* __restrict__ partial) {
+                                                       float* __restrict__ partial, const float* __restrict__ coef = nullptr,
+                                                       const int loss_kind = INR_LOSS_SE) {
     __shared__ float sh[4][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long long p = (long long)blockIdx.x * 4 + wv;
@@ -118,7 +122,14 @@ __global__ __launch_bounds__(256) void star_out_kernel(const float* __restrict__
         const float out = __fsub_rn(__fmul_rn(r, s), 1.f);
         if (lane == 0) {
             if (logits) logits[p] = out;
-            if (labels) {
+            if (DENSE && labels) {
+                float l = 0.f, dout = 0.f;
+                wide_data_term<false>(labels, coef, loss_kind, WideJoint{}, p, out, l, dout);
+                ds[p] = dout * r;
+                drd[p] = dout * s;
+                se = l;
+                sds = dout * r;
+            } else if (labels) {
                 const float pr = 1.f / (1.f + expf(-out));
                 const float er = pr - labels[star_pixel(idx, p, n_pixels)];
                 const float dout = 2.f * er / (float)N * pr * (1.f - pr);
@@ -155,15 +166,18 @@ __global__ __launch_bounds__(256) void star_bwd0_kernel(const float* __restrict_
     D0[e] = A0[e] > 0.f ? fmaf(ds[p], prm[m.p_w2() + j], D0[e]) : 0.f;
 }
 
-// Column sums over the points of one chunk: grid (ceil(h / 32), STAR_CHUNKS), thread = (unit jj of 32, point group pg of 8).
+// Column sums over the points of one chunk: grid (ceil(h / 32), CHUNKS), thread = (unit jj of 32, point group pg of 8).
 // colp[chunk][q][h]; fixed order: a thread walks its points in order, the 8 groups are added in order.
+// CHUNKS: STAR_CHUNKS for a minibatch; the dense fits cut a tile into STAR_DENSE_CHUNKS (a thread's walk is a chain of dependent
+// loads: at 16 chunks of a 16384-point tile it is 128 steps long on 80 blocks; measured, a 256 x 256 step: 1081 -> 1056 us).
+template <int CHUNKS>
 __global__ __launch_bounds__(256) void star_col_kernel(const StarMap m, const float* __restrict__ feat, const float* __restrict__ ds,
                                                        const float* __restrict__ A0, const float* __restrict__ A1,
                                                        const float* __restrict__ D0, const float* __restrict__ D1, const long long N,
                                                        float* __restrict__ colp) {
     __shared__ float sh[8][STAR_COLQ][32];
     const int jj = threadIdx.x & 31, pg = threadIdx.x >> 5, j = blockIdx.x * 32 + jj, c = blockIdx.y;
-    const long long cl = (N + STAR_CHUNKS - 1) / STAR_CHUNKS, p0 = c * cl, p1 = p0 + cl < N ? p0 + cl : N;
+    const long long cl = (N + CHUNKS - 1) / CHUNKS, p0 = c * cl, p1 = p0 + cl < N ? p0 + cl : N;
     float a[STAR_COLQ];
 #pragma unroll
     for (int q = 0; q < STAR_COLQ; ++q) a[q] = 0.f;
@@ -195,6 +209,8 @@ __global__ __launch_bounds__(256) void star_col_kernel(const StarMap m, const fl
 
 // Gradient of the centre: per point dx^ = D0 W0, dr = dout s + D1 . W1_r, chained through x^ = x' / (0.01 + r), r = |x'|
 // (a pixel exactly at -offset has r = 0 and a NaN gradient, in torch as here).  One wave per point; offp[blocks][2].
+// DENSE: on a full grid the centre can sit on a pixel; that pixel contributes nothing to the centre's gradient (include/inrfit.h).
+template <bool DENSE>
 __global__ __launch_bounds__(256) void star_point_kernel(const float* __restrict__ prm, const StarMap m, const float* __restrict__ feat,
                                                          const float* __restrict__ drd, const float* __restrict__ D0,
                                                          const float* __restrict__ D1, const long long N, float* __restrict__ offp) {
@@ -219,6 +235,7 @@ __global__ __launch_bounds__(256) void star_point_kernel(const float* __restrict
         const float dr = drd[p] + drh + dden;
         g0 = du0 * q + dr * x0 / r;                            // r = sqrt(x'0^2 + x'1^2): dr / dx' = x' / r
         g1 = du1 * q + dr * x1 / r;
+        if (DENSE && r == 0.f) g0 = g1 = 0.f;
     }
     if (lane == 0) { sh[wv][0] = g0; sh[wv][1] = g1; }
     __syncthreads();
@@ -350,7 +367,7 @@ inline int star_forward_pass(const StarMap& m, const StarWs& w, const float* prm
     int rc = gemm_rm(s, false, true, (int)N, h, h, w.A0, h, prm + m.p_w1(), h, w.A1, h);      // P1 = x_old W1^T
     if (rc) return rc;
     hipLaunchKernelGGL(star_l1_kernel, star_elem_grid(N, h), dim3(256), 0, s, prm, m, (const float*)w.feat, N, w.A1);
-    hipLaunchKernelGGL(star_out_kernel, dim3(w.nb4), dim3(256), 0, s, prm, m, (const float*)w.feat, (const float*)w.A0, (const float*)w.A1,
+    hipLaunchKernelGGL(star_out_kernel<false>, dim3(w.nb4), dim3(256), 0, s, prm, m, (const float*)w.feat, (const float*)w.A0, (const float*)w.A1,
                        labels, idx, n_pixels, N, logits, w.ds, w.drd, labels ? w.partial : nullptr);
     return INR_OK;
 }
@@ -364,12 +381,215 @@ inline int star_backward_pass(const StarMap& m, const StarWs& w, const float* pr
     if (rc) return rc;
     hipLaunchKernelGGL(star_bwd0_kernel, star_elem_grid(N, h), dim3(256), 0, s, prm, m, (const float*)w.ds, (const float*)w.A0, N, w.D0);
     if ((rc = gemm_rm_splitk(s, true, false, h, h, (int)N, w.D1, h, w.A0, h, w.gW1, w.gpart))) return rc;   // dW1 = D1^T x_old, slices added in order
-    hipLaunchKernelGGL(star_col_kernel, dim3((h + 31) / 32, STAR_CHUNKS), dim3(256), 0, s, m, (const float*)w.feat, (const float*)w.ds,
+    hipLaunchKernelGGL(star_col_kernel<STAR_CHUNKS>, dim3((h + 31) / 32, STAR_CHUNKS), dim3(256), 0, s, m, (const float*)w.feat, (const float*)w.ds,
                        (const float*)w.A0, (const float*)w.A1, (const float*)w.D0, (const float*)w.D1, N, w.colp);
-    hipLaunchKernelGGL(star_point_kernel, dim3(w.nb4), dim3(256), 0, s, prm, m, (const float*)w.feat, (const float*)w.drd,
+    hipLaunchKernelGGL(star_point_kernel<false>, dim3(w.nb4), dim3(256), 0, s, prm, m, (const float*)w.feat, (const float*)w.drd,
                        (const float*)w.D0, (const float*)w.D1, N, w.offp);
     hipLaunchKernelGGL(star_scalar_kernel, dim3(1), dim3(256), 0, s, (const float*)w.partial, (const float*)w.offp, w.nb4, N, w.scal,
                        loss_hist, hist_idx);
+    return INR_OK;
+}
+
+// ---- dense full-batch fits (inrfit_star_fit_dense / inrfit_star_loss_grad_dense) ------------------------------------------------------
+// Every step sees ALL pixels of the image.  The grid is walked in tiles of STAR_DENSE_TILE points: the kernels above run on one tile
+// at a time ([T][h] activations, whatever the image's size), and star_dense_acc_kernel adds the tile's gradient pieces - the h x h
+// product (its split-K slices already added in slice order), the seven column sums (their STAR_DENSE_CHUNKS chunks added in chunk order), the
+// loss, db2 and the centre's two components - onto the image's accumulators, tile after tile in stream order.  The tile size is a
+// constant, not a property of the device: it fixes the order of every sum, so two runs give the same bits.
+// Twelve launches per tile and one update launch per step; nothing synchronises with the host.
+constexpr int STAR_DENSE_TILE = 16384;
+constexpr int STAR_DENSE_CHUNKS = 128;   // point chunks of a tile's column sums (128 points each in a full tile)
+
+// acc layout per call (images run one after another): gW1 [h][h] | col [STAR_COLQ][h] | scal [4] = loss, db2, doffset[2]
+// grid: the elementwise blocks + ONE last block for the four scalars.  first: tile 0 stores, the others add.
+__global__ __launch_bounds__(256) void star_dense_acc_kernel(const StarMap m, const float* __restrict__ gW1t, const float* __restrict__ colp,
+                                                             const float* __restrict__ partial, const float* __restrict__ offp,
+                                                             const int nb, const int first, float* __restrict__ gW1,
+                                                             float* __restrict__ col, float* __restrict__ scal) {
+    const int h = m.h;
+    if (blockIdx.x == gridDim.x - 1) {
+        __shared__ float sm[4];
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int b = threadIdx.x; b < nb; b += 256) {
+            v[0] += partial[2 * b];
+            v[1] += partial[2 * b + 1];
+            v[2] += offp[2 * b];
+            v[3] += offp[2 * b + 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = block_sum256(v[k], sm);
+            if (threadIdx.x == 0) scal[k] = first ? t : scal[k] + t;
+        }
+        return;
+    }
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < h * h) {
+        gW1[e] = first ? gW1t[e] : gW1[e] + gW1t[e];
+    } else if (e < h * h + STAR_COLQ * h) {
+        const int qj = e - h * h;   // = q * h + j
+        float g = 0.f;
+#pragma unroll
+        for (int c = 0; c < STAR_DENSE_CHUNKS; ++c) g += colp[(size_t)c * STAR_COLQ * h + qj];
+        col[qj] = first ? g : col[qj] + g;
+    }
+}
+
+struct StarDenseUpdArgs {
+    float* prm;          // [P] in place
+    float* opt;          // [2 P + INR_OPT_HEADER_FLOATS]: exp_avg | exp_avg_sq or exp_inf | header (include/inrfit.h)
+    const float* gW1;    // the accumulators of star_dense_acc_kernel
+    const float* col;
+    const float* scal;
+    float* grads_out;    // mode 1: [P]
+    float* loss_out;     // mode 1: [1]
+    float* loss_hist;    // mode 0: this step's slot, or null
+    int32_t* status;     // mode 0: this image's word
+    StarMap m;
+    InrOptDesc od;
+    float one_minus_b1, one_minus_b2;
+    double bc1, bc1_off;             // 1 - beta1^t for the network / for the centre (its own step count)
+    float bc2_sqrt, bc2_sqrt_off;
+    int offset_on;                   // the centre takes this step
+    int t;                           // 1-based optimizer step index (selects the header's double-buffer slots)
+    int mode;                        // 0 = optimizer step + projection + plateau, 1 = gradients and loss only
+};
+
+// Thread i < P: one parameter (torch's single-tensor Adam / Adamax in its operation order, then W2_r.weight <- relu(W2_r.weight));
+// thread P: the loss, the "frozen by a non-finite loss" flag and ReduceLROnPlateau in the header - the discipline of icnn_update_kernel:
+// this step's learning rate and the flag left by the previous step sit in slot [t & 1], the next step's are written to the other one,
+// and every thread derives "frozen" from the flag and from THIS step's loss, so which parameters move does not depend on block timing.
+__global__ __launch_bounds__(256) void star_dense_update_kernel(const StarDenseUpdArgs u) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const StarMap& m = u.m;
+    if (i > m.P) return;
+    const int h = m.h;
+    const float loss = u.scal[0];
+    float g = 0.f;
+    int colq = -1, j = 0;
+    if (i < m.p_w0()) g = u.scal[2 + i];
+    else if (i < m.p_b0()) { j = (i - m.p_w0()) >> 1; colq = 5 + ((i - m.p_w0()) & 1); }
+    else if (i < m.p_w1()) { j = i - m.p_b0(); colq = 4; }
+    else if (i < m.p_b1()) g = u.gW1[i - m.p_w1()];
+    else if (i < m.p_w2()) { j = i - m.p_b1(); colq = 0; }
+    else if (i < m.p_b2()) { j = i - m.p_w2(); colq = 2; }
+    else if (i < m.p_w1r()) g = u.scal[1];
+    else if (i < m.p_b1r()) { j = i - m.p_w1r(); colq = 1; }
+    else if (i < m.p_w2r()) { j = i - m.p_b1r(); colq = 0; }
+    else if (i < m.p_b2r()) { j = i - m.p_w2r(); colq = 3; }
+    else if (i < m.P) g = u.scal[1];
+    if (colq >= 0) g = u.col[colq * h + j];
+    if (u.mode != 0) {
+        if (i < m.P) u.grads_out[i] = g;
+        else u.loss_out[0] = loss;
+        return;
+    }
+    float* __restrict__ hdr = u.opt + 2 * (size_t)m.P;
+    const bool bad_before = hdr[6 + (u.t & 1)] != 0.f;   // written by the PREVIOUS step's launch (double buffer like the lr: no race)
+    const float lr_now = hdr[u.t & 1];
+    const bool frozen = bad_before || !isfinite(loss);
+    if (i == m.P) {
+        if (u.loss_hist) u.loss_hist[0] = loss;
+        float lr = lr_now;
+        hdr[6 + ((u.t + 1) & 1)] = frozen ? 1.f : 0.f;
+        if (frozen) {
+            u.status[0] = INR_STATUS_NONFINITE;
+        } else if (u.od.plateau) {   // torch semantics, mode 'min', relative threshold
+            float best = hdr[3];
+            int num_bad = (int)hdr[4];
+            if (loss < best * (1.f - u.od.plateau_threshold)) {
+                best = loss;
+                num_bad = 0;
+            } else {
+                num_bad += 1;
+            }
+            if (num_bad > u.od.plateau_patience) {
+                const float nlr = fmaxf(lr * u.od.plateau_factor, u.od.plateau_min_lr);
+                if (lr - nlr > u.od.plateau_eps) lr = nlr;
+                num_bad = 0;
+            }
+            hdr[3] = best;
+            hdr[4] = (float)num_bad;
+        }
+        hdr[(u.t + 1) & 1] = lr;   // learning rate of the NEXT step (the scheduler steps after the optimizer)
+        hdr[2] = lr;
+        hdr[5] = loss;
+        return;
+    }
+    if (frozen) return;
+    const bool is_off = i < m.p_w0();
+    if (is_off && !u.offset_on) return;     // requires_grad = False: torch's optimizers skip a parameter without a gradient
+    float p = u.prm[i], mm = u.opt[i], v = u.opt[m.P + i];
+    const float step_size = (float)((double)lr_now / (is_off ? u.bc1_off : u.bc1));
+    mm = __fadd_rn(mm, __fmul_rn(u.one_minus_b1, __fsub_rn(g, mm)));
+    if (u.od.kind == INR_OPT_ADAM) {
+        v = __fadd_rn(__fmul_rn(v, u.od.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, g), g));
+        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), is_off ? u.bc2_sqrt_off : u.bc2_sqrt), u.od.eps);
+        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, mm), denom));
+    } else {   // Adamax: exp_inf = max(beta2 exp_inf, |grad| + eps); p -= lr / bc1 * m / exp_inf
+        v = fmaxf(__fmul_rn(v, u.od.beta2), __fadd_rn(fabsf(g), u.od.eps));
+        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, mm), v));
+    }
+    if (i >= m.p_w2r() && i < m.p_b2r()) p = fmaxf(p, 0.f);
+    u.prm[i] = p;
+    u.opt[i] = mm;
+    u.opt[m.P + i] = v;
+}
+
+struct StarDenseWs {
+    StarWs t;                        // one tile's buffers
+    float *colp;                     // [STAR_DENSE_CHUNKS][STAR_COLQ][h] column sums of the tile's chunks
+    float *gW1, *col, *scal, *coef;  // the image's accumulators; coef [n_images][2]
+    long long bytes;
+};
+inline StarDenseWs carve_star_dense(int h, long long n_pixels, int n_images, void* base) {
+    StarDenseWs w{};
+    w.t = carve_star(h, n_pixels < STAR_DENSE_TILE ? n_pixels : STAR_DENSE_TILE, base);
+    char* b = (char*)base;
+    long long off = w.t.bytes;
+    auto take = [&](long long bytes) {
+        float* p = (float*)(b + off);
+        off += (bytes + 255) / 256 * 256;
+        return p;
+    };
+    w.colp = take((long long)STAR_DENSE_CHUNKS * STAR_COLQ * h * 4);
+    w.gW1 = take((long long)h * h * 4);
+    w.col = take((long long)STAR_COLQ * h * 4);
+    w.scal = take(256);
+    w.coef = take((long long)n_images * 2 * 4);
+    w.bytes = off;
+    return w;
+}
+
+// One pass over all N pixels of an image, tile by tile.  labels != null: the criterion; backward: every gradient onto the accumulators
+// (complete after the last tile); logits != null: the forward's output [N].
+inline int star_dense_pass(const StarMap& m, const StarDenseWs& w, const float* prm, const float* coords, const float* labels,
+                           const float* coef, int loss_kind, long long N, float* logits, bool backward, hipStream_t s) {
+    const int h = m.h;
+    const StarWs& t = w.t;
+    for (long long p0 = 0; p0 < N; p0 += STAR_DENSE_TILE) {
+        const long long n = N - p0 < STAR_DENSE_TILE ? N - p0 : STAR_DENSE_TILE;
+        const int nb4 = (int)((n + 3) / 4);
+        hipLaunchKernelGGL(star_l0_kernel, star_elem_grid(n, h), dim3(256), 0, s, prm, m, coords + 2 * p0, (const int32_t*)nullptr, n, n,
+                           t.feat, t.A0);
+        int rc = gemm_rm(s, false, true, (int)n, h, h, t.A0, h, prm + m.p_w1(), h, t.A1, h);      // P1 = x_old W1^T
+        if (rc) return rc;
+        hipLaunchKernelGGL(star_l1_kernel, star_elem_grid(n, h), dim3(256), 0, s, prm, m, (const float*)t.feat, n, t.A1);
+        hipLaunchKernelGGL(star_out_kernel<true>, dim3(nb4), dim3(256), 0, s, prm, m, (const float*)t.feat, (const float*)t.A0,
+                           (const float*)t.A1, labels ? labels + p0 : nullptr, (const int32_t*)nullptr, n, n,
+                           logits ? logits + p0 : nullptr, t.ds, t.drd, labels ? t.partial : nullptr, coef, loss_kind);
+        if (!backward) continue;
+        hipLaunchKernelGGL(star_bwd1_kernel, star_elem_grid(n, h), dim3(256), 0, s, prm, m, (const float*)t.ds, (const float*)t.A1, n, t.D1);
+        if ((rc = gemm_rm(s, false, false, (int)n, h, h, t.D1, h, prm + m.p_w1(), h, t.D0, h))) return rc;     // D1 W1
+        hipLaunchKernelGGL(star_bwd0_kernel, star_elem_grid(n, h), dim3(256), 0, s, prm, m, (const float*)t.ds, (const float*)t.A0, n, t.D0);
+        if ((rc = gemm_rm_splitk(s, true, false, h, h, (int)n, t.D1, h, t.A0, h, t.gW1, t.gpart))) return rc;  // dW1 of the tile
+        hipLaunchKernelGGL(star_col_kernel<STAR_DENSE_CHUNKS>, dim3((h + 31) / 32, STAR_DENSE_CHUNKS), dim3(256), 0, s, m, (const float*)t.feat,
+                           (const float*)t.ds, (const float*)t.A0, (const float*)t.A1, (const float*)t.D0, (const float*)t.D1, n, w.colp);
+        hipLaunchKernelGGL(star_point_kernel<true>, dim3(nb4), dim3(256), 0, s, prm, m, (const float*)t.feat, (const float*)t.drd,
+                           (const float*)t.D0, (const float*)t.D1, n, t.offp);
+        hipLaunchKernelGGL(star_dense_acc_kernel, dim3((h * h + STAR_COLQ * h + 255) / 256 + 1), dim3(256), 0, s, m, (const float*)t.gW1,
+                           (const float*)w.colp, (const float*)t.partial, (const float*)t.offp, nb4, p0 == 0 ? 1 : 0, w.gW1, w.col, w.scal);
+    }
     return INR_OK;
 }
 

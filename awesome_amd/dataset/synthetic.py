@@ -73,6 +73,32 @@ def disc_unaries(h: int, w: int, cy: float, cx: float, r: float) -> torch.Tensor
     return torch.from_numpy(1.0 - disc.astype(np.float32))
 
 
+def star_shape(seed: int = 0):
+    """The seeded parameters of the `star` kind in grid coordinates ([0, 1]^2): (cx, cy, r0, a, k, phase) of the region
+    |x - c| <= r0 + a cos(k (theta - phase)) - star-shaped about c by construction, and not convex: a (k^2 + 1) > r0."""
+    rng = np.random.RandomState(40_000 + seed)
+    cx, cy = rng.uniform(0.42, 0.58, 2)
+    r0 = rng.uniform(0.22, 0.28)
+    a = rng.uniform(0.28, 0.36) * r0
+    k = int(rng.randint(3, 6))
+    phase = rng.uniform(0.0, 2.0 * np.pi)
+    return float(cx), float(cy), float(r0), float(a), k, float(phase)
+
+
+def star_mask(size: int = 64, seed: int = 0) -> np.ndarray:
+    """bool (size, size), True = object, on the linspace(0, 1) grid of the prior datasets (x along the columns, y along the rows)."""
+    cx, cy, r0, a, k, phase = star_shape(seed)
+    lin = np.linspace(0.0, 1.0, size)
+    yy, xx = np.meshgrid(lin, lin, indexing="ij")
+    rad, theta = np.hypot(xx - cx, yy - cy), np.arctan2(yy - cy, xx - cx)
+    return rad <= r0 + a * np.cos(k * (theta - phase))
+
+
+def star_unaries(size: int = 64, seed: int = 0) -> torch.Tensor:
+    """(size, size) float32 unaries of the seeded non-convex star, fg (object) = 0, bg = 1."""
+    return torch.from_numpy(1.0 - star_mask(size, seed).astype(np.float32))
+
+
 from .prior_dataset import PriorDataset, prior  # noqa: E402
 
 
@@ -229,8 +255,8 @@ class SyntheticPixelDataset(SyntheticPriorDataset):
 
 class SyntheticUnariesDataset:
     """Minimal stand-in for the reference's prior datasets on the hot path: item i is `(grid_desc, unaries_i)` where
-    unaries follow the reference convention (fg = 0).  `kind`: 'disc' (C1), 'blob' (C2/C3, seed = index + seed0) or
-    'noisy_blob' (C5: soft unaries from noisy synthetic logits)."""
+    unaries follow the reference convention (fg = 0).  `kind`: 'disc' (C1), 'blob' (C2/C3, seed = index + seed0),
+    'noisy_blob' (C5: soft unaries from noisy synthetic logits) or 'star' (C8: a seeded non-convex star, star_shape)."""
 
     def __init__(self, n_images: int = 1, size: int = 256, kind: str = "blob", seed0: int = 0, **kwargs):
         self.n_images, self.size, self.kind, self.seed0 = int(n_images), int(size), kind, int(seed0)
@@ -246,6 +272,8 @@ class SyntheticUnariesDataset:
             return convex_blob_unaries(self.size, self.seed0 + i)
         if self.kind == "noisy_blob":
             return noisy_blob_unaries(self.size, self.seed0 + i)
+        if self.kind == "star":
+            return star_unaries(self.size, self.seed0 + i)
         raise ValueError(f"unknown kind {self.kind}")
 
     def ground_truth(self, i: int) -> torch.Tensor:

@@ -23,7 +23,10 @@ the notebook's loop (random 1000-pixel minibatches, a torch optimizer) runs unch
 The loop itself also exists on the device (`fit` -> `inrfit_star_fit`, csrc/star.h: the network evaluated layer by layer on the
 minibatch with its own read-out, MSE on the sigmoid, every gradient incl. the centre's, torch's Adam and the projection - no autograd,
 no torch optimizer, no host synchronisation), and `forward_fused` is the inference of cells 4 / 6 (`inrfit_star_forward`).  Any width
-up to 1024 (the notebook's 150 included); the autograd surface takes what `inrfit_supported` takes."""
+up to 1024 (the notebook's 150 included); the autograd surface takes what `inrfit_supported` takes.
+
+`pretrain(...)` (PriorFitMixin) fits the prior to every image of a prior dataset like the other prior families do: dense, full-batch,
+many images per device call (`inrfit_star_fit_dense`), with the criterion, optimizer and plateau options of the ICNN fits."""
 from __future__ import annotations
 
 import torch
@@ -32,9 +35,20 @@ import torch.nn as nn
 from .. import icnn as K
 from .. import star as S
 from .convex_net import _IcnnFunction
+from .pretrainable_module import PriorFitMixin
 
 
-class StarShapedNet(nn.Module):
+def foreground_mean(grid: torch.Tensor, unaries: torch.Tensor) -> torch.Tensor:
+    """(2,) mean of the grid's own coordinates over the foreground pixels (unaries < 0.5).  grid: (2, N) or (.., 2, H, W); unaries: N
+    values in any shape.  Without foreground: the mean over all pixels."""
+    co = grid.reshape(-1, 2, unaries.numel())[0] if grid.dim() > 2 else grid
+    fg = (unaries.reshape(-1) < 0.5).to(co.dtype)
+    if float(fg.sum()) == 0.0:
+        fg = torch.ones_like(fg)
+    return (co * fg[None]).sum(1) / fg.sum()
+
+
+class StarShapedNet(nn.Module, PriorFitMixin):
     def __init__(self, n_hidden: int = 130, **kwargs):
         super().__init__()
         self.spec = K.IcnnSpec(n_hidden, 3, 1)
@@ -45,6 +59,8 @@ class StarShapedNet(nn.Module):
         self.W2 = nn.Linear(n_hidden, 1)
         self.W1_r = nn.Linear(1, n_hidden)
         self.W2_r = nn.Linear(n_hidden, 1)
+        # PriorBank binds its rows through list(model.parameters()): that order IS the flat vector's (include/inrfit.h)
+        assert tuple(k for k, _ in self.named_parameters()) == S.PARAM_ORDER
 
     def enforce_star_shape(self) -> None:
         """The projection the notebook applies after every optimizer step: W2_r.weight <- relu(W2_r.weight)."""
@@ -52,6 +68,72 @@ class StarShapedNet(nn.Module):
             self.W2_r.weight.clamp_(min=0.0)
 
     enforce_convexity = enforce_star_shape   # the prior-module contract name (WrapperModule calls it after each step)
+
+    def reset_parameters(self) -> bool:
+        """Each nn.Linear's own reset in creation order (a seeded call redraws what a seeded construction draws), the centre to 0."""
+        for lin in (self.W0, self.W1, self.W2, self.W1_r, self.W2_r):
+            lin.reset_parameters()
+        with torch.no_grad():
+            self.offset.zero_()
+        return True
+
+    # ---- PriorFitMixin engine: `pretrain(...)` on inrfit_star_fit_dense -----------------------------------------------------------
+    def _pretrain_defaults(self):
+        """The notebook's optimizer (Adam 1e-2, no scheduler; the centre freed after a tenth of the epochs, as after 1000 of its
+        10 000) around the reference's gate / retry / reuse_state keys.  `optimizer: adamax` and `use_plateau: true` (patience 200,
+        factor 0.5) select what the other priors' pretrain uses.  `offset_free_epoch`: the centre's first step is the NEXT epoch's
+        (as in `fit`; -1: free from the first step, None: never; "auto": num_epochs // 10 of the fit at hand).  A warm start
+        (reuse_state) continues a fit whose centre is free already.
+        `init_center`: "center_of_mass" = a cold start puts the centre on the mean coordinate of the foreground, None keeps the
+        state's offset."""
+        return dict(num_epochs=2000, lr=1e-2, optimizer="adam", use_plateau=False, offset_free_epoch="auto",
+                    init_center="center_of_mass", reuse_state=True, reuse_state_epochs=200, proper_prior_fit_threshold=0.5,
+                    proper_prior_fit_retrys=1)
+
+    def _engine_pack(self, sd):
+        return S.flatten_state_dict(self.star_spec, sd, "cpu")
+
+    def _engine_unpack(self, flat):
+        return S.unflatten(self.star_spec, flat)
+
+    @staticmethod
+    def _image_coords(grid) -> torch.Tensor:
+        """K.Grid.explicit's channel-planar (2, N) / (n, 2, N) -> the star entry points' rows (N, 2) / (n, N, 2)."""
+        return grid.coords.transpose(-1, -2).contiguous()
+
+    def _engine_fit(self, grid, unaries, flat, epochs, cold, opts, states=None):
+        from ..measures import criterion_to_desc
+        crit = opts.get("criterion")
+        kind, wmode, ratio = criterion_to_desc(crit, "targets") if crit is not None else ("se", "none", 1.0)
+        rows = self._image_coords(grid)
+        if cold and opts.get("init_center", "center_of_mass") == "center_of_mass":
+            for i in range(flat.shape[0]):
+                co = grid.coords if grid.coords.dim() == 2 else grid.coords[i]
+                flat[i, 0:2] = -foreground_mean(co, unaries[i])
+        free = opts.get("offset_free_epoch", "auto")
+        if not cold:
+            first = 0                       # a warm start continues a fit whose centre is already free
+        elif free is None:
+            first = -1
+        else:
+            first = (int(epochs) // 10 if free == "auto" else int(free)) + 1
+        res = S.star_fit_dense(self.star_spec, flat, rows, unaries, epochs, lr=float(opts.get("lr", 1e-2)), loss=kind, weight_mode=wmode,
+                               ratio=ratio, optimizer=opts.get("optimizer", "adam"),
+                               plateau=dict(patience=200, factor=0.5) if opts.get("use_plateau", False) else None,
+                               offset_first_step=first, record_loss=False, want_logits=True, gate_logits=True)
+        return res.params, res.logits, res.status
+
+    def _engine_chain_context(self, ctx, image):
+        """The reuse_state chain carries the foreground's mean coordinate of the last properly fitted frame along."""
+        return foreground_mean(image.grid, image.unaries).cpu()
+
+    def _engine_warm_start(self, flat, ctx, image, opts):
+        """The centre moves with the foreground: offset <- offset_prev - (mean_now - mean_prev)."""
+        if ctx is not None:
+            now = foreground_mean(image.grid, image.unaries).cpu()
+            flat = flat.clone()
+            flat[0:2] -= (now - ctx).to(flat.device, flat.dtype)
+        return flat, ctx
 
     # ---- the device-resident surface (awesome_amd/star.py) -----------------------------------------------------------------------
     @property

@@ -1,5 +1,6 @@
-"""Host side of the star-shape prior's device-resident entry points (include/inrfit.h: inrfit_star_forward / _loss_grad / _fit;
-kernels in csrc/star.h).  Mirrors notebooks/icml_teaser_code/star_shaped/star.ipynb: `myNet` (cell 2) and its training loop (cell 3).
+"""Host side of the star-shape prior's device-resident entry points (include/inrfit.h: inrfit_star_forward / _loss_grad / _fit, and
+the dense full-batch, many-image form inrfit_star_fit_dense / _loss_grad_dense; kernels in csrc/star.h).  Mirrors
+notebooks/icml_teaser_code/star_shaped/star.ipynb: `myNet` (cell 2) and its training loop (cell 3).
 
 Parameters travel as ONE flat vector in the order of the notebook class's named_parameters() (PARAM_ORDER)."""
 from __future__ import annotations
@@ -130,6 +131,88 @@ def star_fit(spec: StarSpec, params: Tensor, coords: Tensor, labels: Tensor, bat
     X.call("inrfit_star_fit", spec.desc(), params, opt_state, coords, labels, npx, batch_index, batch, X.opt_desc("adam", lr, betas, eps),
            steps, int(step0), int(offset_first_step), hist, ws=_workspace(spec, batch, dev), device=dev)
     return StarFitResult(params, opt_state, X.trim(hist, steps))
+
+
+# ---- the dense full-batch form (inrfit_star_fit_dense / _loss_grad_dense) -------------------------------------------------------------
+def dense_tile_points() -> int:
+    """Points per tile of the dense entry points: a constant of the library (it fixes the order of the sums)."""
+    return int(L.load().inrfit_star_dense_tile_points())
+
+
+def opt_state_floats(spec: StarSpec) -> int:
+    return 2 * spec.n_params + L.INR_OPT_HEADER_FLOATS
+
+
+def new_dense_opt_state(spec: StarSpec, n_images: int, device) -> Tensor:
+    """Zeroed: a cold fit (moments 0; step0 == 0 fills the header)."""
+    return torch.zeros(n_images, opt_state_floats(spec), dtype=torch.float32, device=device)
+
+
+def _check_dense(spec: StarSpec, params: Tensor, coords: Tensor, targets: Tensor):
+    """params [n, P]; coords [N, 2] (one grid for all images) or [n, N, 2]; targets [n, N] -> (..., n, N, coords' image stride)."""
+    if params.dim() != 2:
+        raise ValueError("params must be [n_images, P]")
+    if not params.is_contiguous():
+        raise ValueError("params must be contiguous (they are updated in place)")
+    n = int(params.shape[0])
+    params = X.rows(params, "params", n, spec.n_params)
+    if coords.dim() == 3:
+        coords = X.rows(coords, "coords", n, (int(coords.shape[1]), 2))
+        npx = int(coords.shape[1])
+        stride = 2 * npx
+    else:
+        coords = X.rows(coords, "coords", None, 2)
+        npx, stride = int(coords.shape[0]), 0
+    targets = X.rows(targets, "targets", n, npx)
+    return params, coords, targets, n, npx, stride
+
+
+@dataclass
+class StarDenseFitResult:
+    params: Tensor               # [n, P], same storage as the input
+    opt_state: Tensor            # [n, 2P + header]
+    loss_hist: Optional[Tensor]  # [n, steps]: the loss before each step
+    logits: Optional[Tensor]     # [n, N]
+    status: Tensor               # [n] int32, INR_STATUS_*
+
+
+def star_fit_dense(spec: StarSpec, params: Tensor, coords: Tensor, targets: Tensor, steps: int, lr: float = 1e-2, loss: str = "se",
+                   weight_mode: str = "none", ratio: float = 1.0, c_fg: float = 0.0, c_bg: float = 0.0, optimizer: str = "adam",
+                   betas=(0.9, 0.999), eps: float = 1e-8, plateau: Optional[dict] = None, opt_state: Optional[Tensor] = None,
+                   step0: int = 0, offset_first_step: int = 0, record_loss: bool = True, want_logits: bool = True,
+                   gate_logits: bool = False, weight_decay: float = 0.0) -> StarDenseFitResult:
+    """`steps` full-batch steps of n independent star-shape fits on the device (params IN PLACE): criterion(sigmoid(net), targets)
+    as the ICNN fits read it, Adam / Adamax, W2_r.weight <- relu, ReduceLROnPlateau (`plateau`: None = off).  The centre takes its
+    first step at step `offset_first_step` (< 0: never).  gate_logits: `logits` = the output of the last training forward (what the
+    IoU gate reads) instead of the logits at the final parameters.  Continue a fit by handing `opt_state` back with `step0`."""
+    params, coords, targets, n, npx, stride = _check_dense(spec, params, coords, targets)
+    dev = params.device
+    if opt_state is None:
+        opt_state = new_dense_opt_state(spec, n, dev)
+    if not opt_state.is_contiguous():
+        raise ValueError("opt_state must be contiguous (it is updated in place)")
+    opt_state = X.rows(opt_state, "opt_state", n, opt_state_floats(spec))
+    X.on_gpu(params=params, coords=coords, targets=targets, opt_state=opt_state)
+    ws = X.workspace("inrfit_star_dense_workspace_bytes", spec.desc(), npx, n, device=dev, slack=64)
+    hist, logits, status = X.fit_outputs(n, steps, (n, npx), record_loss, want_logits, dev)
+    od = X.opt_desc(optimizer, lr, betas, eps, weight_decay, plateau=plateau, gate_logits=gate_logits)
+    X.call("inrfit_star_fit_dense", spec.desc(), params, opt_state, coords, stride, targets, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg),
+           od, npx, n, int(steps), int(step0), int(offset_first_step), hist, logits, status, ws=ws, device=dev)
+    return StarDenseFitResult(params, opt_state, X.trim(hist, steps), logits, status)
+
+
+def star_loss_grad_dense(spec: StarSpec, params: Tensor, coords: Tensor, targets: Tensor, loss: str = "se", weight_mode: str = "none",
+                         ratio: float = 1.0, c_fg: float = 0.0, c_bg: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """(loss [n], grads [n, P]) of the dense criterion at `params`, every pixel, any number of them."""
+    params, coords, targets, n, npx, stride = _check_dense(spec, params, coords, targets)
+    X.on_gpu(params=params, coords=coords, targets=targets)
+    dev = params.device
+    ws = X.workspace("inrfit_star_dense_workspace_bytes", spec.desc(), npx, n, device=dev, slack=64)
+    loss_out = L.scratch(n, dtype=torch.float32, device=dev)
+    grads = L.scratch(n, spec.n_params, dtype=torch.float32, device=dev)
+    X.call("inrfit_star_loss_grad_dense", spec.desc(), params, coords, stride, targets, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg),
+           npx, n, loss_out, grads, ws=ws, device=dev)
+    return loss_out, grads
 
 
 def notebook_minibatches(labels: Tensor, steps: int, number: int = 500, generator: Optional[torch.Generator] = None,

@@ -654,6 +654,42 @@ int inrfit_star_fit(const InrStarDesc* star, float* params, float* opt_state, co
                     int64_t n_pixels, const int32_t* batch_index, int64_t batch, const InrOptDesc* opt, int32_t steps, int32_t step0,
                     int32_t offset_first_step, float* loss_hist, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the star-shape prior as a dense, full-batch, many-image fit (what `pretrain` runs for every other prior family) -----------------
+ * Every step sees ALL n_pixels pixels of an image: forward, the criterion of the ICNN fits on sigmoid(out) against the unaries
+ * (InrLossDesc: SE / BCE, BCE's log clamped at -100 with a NaN kept a NaN; weight modes none / equal / ratio / sssdms / explicit with
+ * target < 0.5 as foreground, the class counts taken once before the loop), backward, INR_OPT_ADAM or INR_OPT_ADAMAX in torch's
+ * single-tensor operation order on params IN PLACE, W2_r.weight <- max(W2_r.weight, 0), ReduceLROnPlateau (InrOptDesc.plateau*).
+ * The images run one after another inside the call; nothing synchronises with the host.
+ *   params [n_images][P]; opt_state [n_images][inrfit_star_opt_state_floats] = exp_avg [P] | exp_avg_sq or exp_inf [P] | header
+ *   [INR_OPT_HEADER_FLOATS], the header as documented for the ICNN fits above (step0 == 0 takes lr from InrOptDesc and resets the
+ *   plateau state, step0 > 0 continues from the header; zero-initialise for a cold fit);
+ *   coords [n_pixels][2] row-major, image i at coords + i * coords_image_stride floats (0 = one grid for all images, else >= 2 n_pixels);
+ *   targets [n_images][n_pixels]; loss_hist [n_images][steps] or NULL: the loss BEFORE each step; final_logits [n_images][n_pixels] or
+ *   NULL: the output of the last training forward (opt->logits_at_last_forward = 1, what the IoU gate reads) or the logits at the
+ *   final parameters (0; one more forward); status [n_images].
+ * The centre takes its first step at epoch `offset_first_step` with its own step count, as in inrfit_star_fit (< 0: never).
+ * A non-finite loss freezes that image alone: its parameters and moments stay as they were before that step, status =
+ * INR_STATUS_NONFINITE.  opt->weight_decay != 0, clamp, freeze_skips, freeze_input: INR_EINVAL (not part of this prior).
+ * Point tiles: the grid is walked in tiles of inrfit_star_dense_tile_points() points - a constant of the library, NOT derived from the
+ * device, because it fixes the order of the sums - so the workspace holds [T][h] activations whatever n_pixels is, and no 65536 limit
+ * applies.  Every gradient is accumulated over the tiles in tile order (the h x h product's split-K slices in slice order inside a tile,
+ * the seven column sums, the centre's and the read-out bias's scalars): two runs give the same bits.
+ * Centre on a pixel: a pixel exactly at -offset has r = 0, where x'/r is 0/0 - torch (and the minibatch entry points above) give the
+ * centre a NaN gradient.  On a dense grid that is a live case, so here such a pixel contributes NOTHING to the centre's gradient; every
+ * other gradient of that pixel is finite as it is (out = -1 there). */
+int32_t inrfit_star_dense_tile_points(void);
+int64_t inrfit_star_opt_state_floats(const InrStarDesc* star);
+int64_t inrfit_star_dense_workspace_bytes(const InrStarDesc* star, int64_t n_pixels, int32_t n_images);
+int inrfit_star_fit_dense(const InrStarDesc* star, float* params, float* opt_state, const float* coords, int64_t coords_image_stride,
+                          const float* targets, const InrLossDesc* loss, const InrOptDesc* opt, int64_t n_pixels, int32_t n_images,
+                          int32_t steps, int32_t step0, int32_t offset_first_step, float* loss_hist, float* final_logits, int32_t* status,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+/* loss_out [n_images], grads [n_images][P] of the same criterion at `params`, with the same tiling and the same r = 0 convention; no
+ * optimizer.  (The gradient surface beyond one tile, and beyond inrfit_star_loss_grad's 65536 points.) */
+int inrfit_star_loss_grad_dense(const InrStarDesc* star, const float* params, const float* coords, int64_t coords_image_stride,
+                                const float* targets, const InrLossDesc* loss, int64_t n_pixels, int32_t n_images, float* loss_out,
+                                float* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the convexity benchmark's segmentation network (awesome/model/cnn_net.py CNNNet, csrc/cnnseg.h) --------------------------------
  * Conv3x3 in_channels -> width, LeakyReLU(0.01), depth x [Conv3x3 width -> width, ReLU], Conv3x3 width -> 1, all with padding 1, batch 1,
  * fp32; the input is the channel concatenation of `image` [image_channels][H][W] and `features` [in_channels - image_channels][H][W].
