@@ -18,6 +18,7 @@
 //                           weight_g only, awesome/util/torch.py:19-35), and the new effective weights for the next step
 #pragma once
 #include "icnn_step.h"
+#include "optim.h"
 #include <stdlib.h>
 
 namespace {
@@ -632,14 +633,14 @@ struct FlowUpdArgs {
     float* grads_out;     // [n_images][FP]               (mode 1)
     const float* slab1;   // [n_images][blocks1][S1]
     const float* slab2;   // [n_images][chunks][K*2][3][Wp]
-    const float* lr_hdr;  // ICNN opt-state header of image 0 stride...: lr of this step is hdr[t & 1]; null -> opt.lr
+    const float* lr_hdr;  // ICNN opt-state header of image 0 (hdr_stride floats per image): this step's lr; null -> opt_desc.lr
     long long hdr_stride;
     InrOptDesc opt_desc;
     FlowMap m;
     int blocks1, S1, chunks, Wp;
     int t;
-    double bc1;
-    float bc2_sqrt, one_minus_b1, one_minus_b2, wd_g;
+    OptConsts c;
+    float wd_g;
     int mode;             // 0 = Adam step + effective weights, 1 = gradients only, 2 = effective weights only (prep)
     const int32_t* status;   // per image (mode 0): frozen by a non-finite loss -> no step, like the ICNN and RealNVP updates
     const float* gscale;     // [n_images] factor on every reduced gradient (the joint step's detached clip factor), or null
@@ -659,51 +660,14 @@ __device__ __forceinline__ float block_sum256(float v, float* sm, const int tid)
 }
 __device__ __forceinline__ float block_sum256(float v, float* sm) { return block_sum256(v, sm, threadIdx.x); }
 
-// The loss of one image = the sum of its workgroups' loss partials, in the order icnn_update_kernel uses: 16 groups (group g takes the
-// workgroups g, g + 16, ...), then the groups in order.  One definition for every kernel that needs the "non-finite loss" decision.
-// `sl` = the partial of workgroup 0, `stride` = floats from one workgroup's partial to the next: 1 for the step kernels' dense copy
-// (StepArgs::loss_part: 256 partials are 8 lines), the slab stride for a loss column read in place (the one-slab views of wide.h).
-constexpr int LOSS_GROUPS = 16;
-__device__ __forceinline__ float loss_column_group_sum(const float* __restrict__ sl, const int wgs, const size_t stride, const int grp) {
-    float lp = 0.f;
-    int w = grp;
-    for (; w + 15 * LOSS_GROUPS < wgs; w += 16 * LOSS_GROUPS) {   // 256 slabs: one trip, 16 loads in flight
-        float q[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) q[k] = sl[(size_t)(w + k * LOSS_GROUPS) * stride];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lp += q[k];
-    }
-    for (; w < wgs; w += LOSS_GROUPS) lp += sl[(size_t)w * stride];
-    return lp;
-}
-
-// "this image takes no optimizer step" exactly as the ICNN update of the same launch decides it: frozen by an earlier step (the flag
-// the PREVIOUS launch wrote, hdr[6 + (t & 1)]) or a non-finite loss now.  Called by the first 256 threads of a block.
-__device__ __forceinline__ bool frozen_in_launch(const float* __restrict__ loss_part, const int wgs, const long long stride,
-                                                 const float* __restrict__ hdr0, const long long hdr_stride, const int t, const int img,
-                                                 const int tid) {
-    __shared__ float redl[LOSS_GROUPS];
-    if (tid < LOSS_GROUPS) redl[tid] = loss_column_group_sum(loss_part + (size_t)img * wgs * stride, wgs, (size_t)stride, tid);
-    __syncthreads();
-    float loss_now = 0.f;
-#pragma unroll
-    for (int k = 0; k < LOSS_GROUPS; ++k) loss_now += redl[k];
-    const bool bad_before = hdr0 != nullptr && hdr0[(size_t)img * hdr_stride + 6 + (t & 1)] != 0.f;
-    return bad_before || !isfinite(loss_now);
-}
-
+// Adam only (optim.h: the hosts of this update answer anything else with an error)
 __device__ __forceinline__ float adam_apply(const FlowUpdArgs& u, float gmul, float p, float g, float lr, float wd, float* m_, float* v_) {
     g = g * gmul;   // the joint step's detached clip factor (x 1.0 is exact: the plain fits are bit-identical)
-    if (wd != 0.f) g = __fadd_rn(g, __fmul_rn(wd, p));
     float m = *m_, v = *v_;
-    m = __fadd_rn(m, __fmul_rn(u.one_minus_b1, __fsub_rn(g, m)));
-    v = __fadd_rn(__fmul_rn(v, u.opt_desc.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, g), g));
-    const float step_size = (float)((double)lr / u.bc1);
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), u.bc2_sqrt), u.opt_desc.eps);
+    p = adam_step(u.c, opt_step_size(lr, u.c.bc1), wd, g, p, m, v);
     *m_ = m;
     *v_ = v;
-    return __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, m), denom));
+    return p;
 }
 
 // block nb of image img: coupling net nb (nb < 2K) or the scales + linear (nb == 2K); the first 256 threads of the block
@@ -714,14 +678,9 @@ __device__ __forceinline__ void flow_update_body(const FlowUpdArgs& u, const int
     const float gmul = u.gscale != nullptr ? u.gscale[img] : 1.f;
     const FlowMap& m = u.m;
     // an image the ICNN update of this step has frozen (non-finite loss) takes no optimizer step: its effective weights are rebuilt
-    // from the unchanged parameters.  ONE source of truth with the ICNN update: the "frozen" flag it has written for step t
-    // into the header's double buffer (hdr[6 + ((t + 1) & 1)], one launch earlier on this stream; `status` may be NULL) - or, when
-    // that update runs in THIS launch (cdn_update_kernel), the same decision from the same numbers (frozen_in_launch).
-    const bool frozen = !isfinite(gmul) ||    // the joint step's composite loss was not finite (joint_step_finish_kernel)
-                        ((u.mode == 0 && u.loss_part != nullptr)
-                             ? frozen_in_launch(u.loss_part, u.loss_wgs, u.loss_stride, u.lr_hdr, u.hdr_stride, u.t, img, tid)
-                             : ((u.lr_hdr != nullptr && u.lr_hdr[(size_t)img * u.hdr_stride + 6 + ((u.t + 1) & 1)] != 0.f) ||
-                                (u.status != nullptr && u.status[img] != INR_STATUS_OK)));
+    // from the unchanged parameters
+    const bool frozen = deformation_frozen(gmul, u.mode == 0 ? u.loss_part : nullptr, u.loss_wgs, u.loss_stride, u.lr_hdr, u.hdr_stride,
+                                           u.status, u.t, img, tid);
     const int mode = (u.mode == 0 && frozen) ? 2 : u.mode;
     const int W = m.W, K = m.K;
     float* __restrict__ fp = u.FP + (size_t)img * m.FP;
@@ -729,7 +688,7 @@ __device__ __forceinline__ void flow_update_body(const FlowUpdArgs& u, const int
     float* __restrict__ om = u.opt ? u.opt + (size_t)img * 2 * m.FP : nullptr;
     float* __restrict__ ov = om ? om + m.FP : nullptr;
     float* __restrict__ go = u.grads_out ? u.grads_out + (size_t)img * m.FP : nullptr;
-    const float lr = u.lr_hdr ? u.lr_hdr[(size_t)img * u.hdr_stride + (u.t & 1)] : u.opt_desc.lr;
+    const float lr = opt_hdr_lr(u.lr_hdr, u.hdr_stride, img, u.t, u.opt_desc.lr);
     if (nb < 2 * K) {
         const int pb = m.p_nb + nb * m.nb_stride;    // v1[W] g1 b1[W] v2[W] g2 b2
         const int eb = m.e_nb + (nb >> 1) * m.e_cp_stride + (nb & 1);  // this net's slots in the coupling's records

@@ -24,6 +24,7 @@
 //   * fp32 everywhere (exact-f32 MFMA == fmaf chain), fixed-order reductions, no atomics: results are reproducible.
 #include "icnn_step.h"
 #include "icnn_step2.h"
+#include "optim.h"
 #include "flow.h"
 #include "rnvp.h"
 #include "joint_loss.h"
@@ -61,9 +62,7 @@ struct UpdArgs {
     int Pu, hu;                 // the CALLER's model: parameter count and n_hidden (hu == img.H: same shape; hu < img.H: the model runs
                                 // zero-padded on the next compiled width, user_param_index below)
     int t;                // 1-based optimizer step index
-    double bc1;           // 1 - beta1^t
-    float bc2_sqrt;       // sqrt(1 - beta2^t)
-    float one_minus_b1, one_minus_b2;
+    OptConsts c;          // ... and its constants
     int hist_idx, hist_stride;
     int mode;             // 0 = optimizer step, 1 = write reduced grads + loss only
     int clamp_lo[UPD_RANGES], clamp_hi[UPD_RANGES];    // flat ranges projected onto >= 0 (ln.weight of every hidden layer, out.ln.weight)
@@ -200,8 +199,8 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
     float p_old = 0.f, m_old = 0.f, v_old = 0.f, lr_now = 0.f;
     bool bad_before = false;
     if (u.mode == 0 && jl < ppb) {   // (in every thread that may own a parameter: the index is not known yet)
-        bad_before = hdr[6 + (u.t & 1)] != 0.f;   // written by the PREVIOUS step's launch (double buffer like the lr: no race)
-        lr_now = hdr[u.t & 1];
+        bad_before = hdr[opt_hdr_frozen_before(u.t)] != 0.f;   // written by the PREVIOUS step's launch (double buffer like the lr: no race)
+        lr_now = hdr[opt_hdr_lr_of(u.t)];
     }
     __builtin_amdgcn_sched_barrier(0);
     const int j = jl < ppb ? slab_param_of_col(u.img, col0 + jl) : -1;   // flat parameter index (kernel shape), P = loss, -1 = none
@@ -251,7 +250,7 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
         }
     }
     float step_size = 0.f;
-    if (ju >= 0) step_size = (float)((double)lr_now / u.bc1);   // bc1 = 1 - beta1^t, computed on the host in double like torch does
+    if (ju >= 0) step_size = opt_step_size(lr_now, u.c.bc1);
     UPD_STAMP(1);
     __syncthreads();
     if (j < 0) return;
@@ -275,54 +274,14 @@ __device__ __forceinline__ void icnn_update_body(const UpdArgs& u, const int bx,
     for (int k = 0; k < UPD_GROUPS; ++k) loss_now += redl[k];
     const bool frozen = bad_before || !isfinite(loss_now) || (u.gscale != nullptr && !isfinite(u.gscale[img]));
     if (j == u.P) {
-        // loss bookkeeping + ReduceLROnPlateau (torch semantics, mode 'min', relative threshold)
-        const float loss = gsum;
-        if (u.loss_hist) u.loss_hist[(size_t)img * u.hist_stride + u.hist_idx] = loss;
-        float lr = lr_now;
-        hdr[6 + ((u.t + 1) & 1)] = frozen ? 1.f : 0.f;
-        if (frozen) {
-            if (u.status) u.status[img] = INR_STATUS_NONFINITE;
-        } else if (u.opt.plateau) {
-            float best = hdr[3];
-            int num_bad = (int)hdr[4];
-            if (loss < best * (1.f - u.opt.plateau_threshold)) {
-                best = loss;
-                num_bad = 0;
-            } else {
-                num_bad += 1;
-            }
-            if (num_bad > u.opt.plateau_patience) {
-                const float nlr = fmaxf(lr * u.opt.plateau_factor, u.opt.plateau_min_lr);
-                if (lr - nlr > u.opt.plateau_eps) lr = nlr;
-                num_bad = 0;
-            }
-            hdr[3] = best;
-            hdr[4] = (float)num_bad;
-        }
-        hdr[(u.t + 1) & 1] = lr;  // learning rate of the NEXT step (the scheduler steps after the optimizer)
-        hdr[2] = lr;
-        hdr[5] = loss;
+        opt_header_step(hdr, u.opt, u.t, gsum, frozen, lr_now, u.loss_hist ? u.loss_hist + (size_t)img * u.hist_stride + u.hist_idx : nullptr,
+                        u.status ? u.status + img : nullptr);
         return;
     }
     if (frozen || !isfinite(gsum) || ju < 0 || never_updated) return;
 
-    float p = p_old, m = m_old, v = v_old;
-    float grad = gsum;
-    if (u.opt.weight_decay != 0.f) grad = __fadd_rn(grad, __fmul_rn(u.opt.weight_decay, p));
-    const float w1 = u.one_minus_b1;
-    // exp_avg.lerp_(grad, 1 - beta1)
-    m = __fadd_rn(m, __fmul_rn(w1, __fsub_rn(grad, m)));
-    if (u.opt.kind == INR_OPT_ADAM) {
-        const float bc2_sqrt = u.bc2_sqrt;
-        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-        v = __fadd_rn(__fmul_rn(v, u.opt.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, grad), grad));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), u.opt.eps);
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, m), denom));
-    } else {
-        // Adamax: exp_inf = max(beta2*exp_inf, |grad| + eps); p -= lr/bc1 * m / exp_inf
-        v = fmaxf(__fmul_rn(v, u.opt.beta2), __fadd_rn(fabsf(grad), u.opt.eps));
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, m), v));
-    }
+    float m = m_old, v = v_old;
+    float p = opt_step(u.opt.kind, u.c, step_size, u.opt.weight_decay, gsum, p_old, m, v);
     if (clamped) p = fmaxf(p, 0.f);
     u.params[(size_t)img * u.Pu + ju] = p;
     if (n_slots > 0) {
@@ -460,14 +419,14 @@ __global__ __launch_bounds__(256) void opt_init_kernel(float* opt_state, int P, 
         float lr;
         if (step0 == 0) {
             lr = opt.lr;
-            hdr[3] = INFINITY;
-            hdr[4] = 0.f;
+            hdr[OPT_HDR_BEST] = INFINITY;
+            hdr[OPT_HDR_NUM_BAD] = 0.f;
         } else {
-            lr = hdr[2];
+            lr = hdr[OPT_HDR_LR];
         }
-        hdr[2] = lr;
-        hdr[(step0 + 1) & 1] = lr;
-        hdr[6] = hdr[7] = 0.f;   // "frozen by a non-finite loss" double buffer: a property of one call, like `status`
+        hdr[OPT_HDR_LR] = lr;
+        hdr[opt_hdr_lr_of(step0 + 1)] = lr;   // the first step of this call is t = step0 + 1
+        opt_hdr_clear_frozen(hdr);
     }
 }
 
@@ -1113,8 +1072,6 @@ static UpdArgs make_upd_args(const KernelEntry* e, const Workspace& w, float* pa
     u.wgs = w.wgs;
     u.n_images = n_images;
     u.hist_stride = steps;
-    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
-    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
     u.mode = 0;
     for (int k = 0; k < UPD_RANGES; ++k) u.clamp_lo[k] = u.clamp_hi[k] = 0;
     for (int k = 0; k < e->img.L; ++k) {
@@ -1134,16 +1091,10 @@ static UpdArgs make_upd_args(const KernelEntry* e, const Workspace& w, float* pa
     return u;
 }
 
-// Adam's bias corrections of step t: 1 - beta1^t and sqrt(1 - beta2^t), computed on the host in double like torch does
-static void bias_corrections(const InrOptDesc* opt, int t, double* bc1, float* bc2_sqrt) {
-    *bc1 = 1.0 - pow((double)opt->beta1, (double)t);
-    *bc2_sqrt = (float)sqrt(1.0 - pow((double)opt->beta2, (double)t));
-}
-
 // what changes from one optimizer step of a loop to the next (t is 1-based)
 static void set_step_consts(UpdArgs& u, const InrOptDesc* opt, int t, int hist_idx = 0) {
     u.t = t;
-    bias_corrections(opt, t, &u.bc1, &u.bc2_sqrt);
+    u.c = opt_consts(opt, t);
     u.hist_idx = hist_idx;
 }
 
@@ -1253,8 +1204,6 @@ static UpdArgs wide_upd_args(const WideMap& m, const float* grads, const InrOptD
     u.wgs = 1;
     u.n_images = 1;
     u.hist_stride = steps;
-    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
-    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
     u.slabs = grads;
     u.loss_part = grads + m.P;   // the one-slab view's loss column, in place
     u.loss_stride = u.PS;
@@ -1403,11 +1352,7 @@ FlowUpdArgs make_flow_upd_args(const CdnWs& w, int mode, float* FP, float* opt, 
     u.chunks = w.chunks;
     u.Wp = w.Wp;
     u.t = t;
-    if (od && t > 0) {
-        bias_corrections(od, t, &u.bc1, &u.bc2_sqrt);
-        u.one_minus_b1 = (float)(1.0 - (double)od->beta1);
-        u.one_minus_b2 = (float)(1.0 - (double)od->beta2);
-    }
+    u.c = opt_consts(od, t);
     u.wd_g = wd_g;
     u.mode = mode;
     return u;
@@ -1827,11 +1772,7 @@ RnvpUpdArgs make_rnvp_upd_args(const PcnWs& w, int n_images, int mode, float* rp
     u.S1 = w.S1;
     u.chunks = w.chunks;
     u.t = t;
-    if (od && t > 0) {
-        bias_corrections(od, t, &u.bc1, &u.bc2_sqrt);
-        u.one_minus_b1 = (float)(1.0 - (double)od->beta1);
-        u.one_minus_b2 = (float)(1.0 - (double)od->beta2);
-    }
+    u.c = opt_consts(od, t);
     u.wd_flow = wd_flow;
     u.mode = mode;
     return u;
@@ -2096,9 +2037,9 @@ namespace {
 // penalty on, where the step kernel's align mode adds the second data term).
 __global__ void joint_prep_kernel(float* hdr, float lr, int t, float* coef, float c, int write_coef) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        hdr[t & 1] = lr;
-        hdr[2] = lr;
-        hdr[6] = hdr[7] = 0.f;
+        hdr[opt_hdr_lr_of(t)] = lr;
+        hdr[OPT_HDR_LR] = lr;
+        opt_hdr_clear_frozen(hdr);
         if (write_coef) coef[0] = coef[1] = c;
     }
 }
@@ -2910,11 +2851,7 @@ struct PoseDeform : SymWs {
         u.blocks = blocks;
         u.t = bu.t;
         u.mode = 0;
-        bias_corrections(&bu.opt, bu.t, &u.bc1, &u.bc2_sqrt);
-        u.one_minus_b1 = (float)(1.0 - (double)bu.opt.beta1);
-        u.one_minus_b2 = (float)(1.0 - (double)bu.opt.beta2);
-        u.beta2 = bu.opt.beta2;
-        u.eps = bu.opt.eps;
+        u.c = opt_consts(&bu.opt, bu.t);
         u.wd = bu.opt.weight_decay;
         hipLaunchKernelGGL(sym_update_kernel, dim3(n_images), dim3(64), 0, s, u);
     }
@@ -3479,18 +3416,9 @@ int inrfit_star_forward(const InrStarDesc* star, const float* params, const floa
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
 }
 
-static void star_upd_consts(StarUpdArgs& u, const InrOptDesc* opt, int t, int t_off) {
-    u.lr = opt->lr;
-    u.beta1 = opt->beta1;
-    u.beta2 = opt->beta2;
-    u.eps = opt->eps;
-    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
-    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
-    bias_corrections(opt, t, &u.bc1, &u.bc2_sqrt);
-    u.offset_on = t_off > 0;
-    u.bc1_off = 1.0;
-    u.bc2_sqrt_off = 1.f;
-    if (t_off > 0) bias_corrections(opt, t_off, &u.bc1_off, &u.bc2_sqrt_off);
+// the centre's own step count at epoch ep (0: it takes no step yet)
+static int star_offset_step(int ep, int offset_first_step) {
+    return offset_first_step >= 0 && ep >= offset_first_step ? ep - offset_first_step + 1 : 0;
 }
 
 int inrfit_star_loss_grad(const InrStarDesc* star, const float* params, const float* coords, const float* labels, int64_t n_pixels,
@@ -3534,13 +3462,17 @@ int inrfit_star_fit(const InrStarDesc* star, float* params, float* opt_state, co
     u.colp = w.colp;
     u.scal = w.scal;
     u.m = m;
+    u.lr = opt->lr;
     u.mode = 0;
     for (int it = 0; it < steps; ++it) {
         const int ep = step0 + it;
         const int32_t* idx = batch_index + (size_t)it * batch;
         if ((rc = star_forward_pass(m, w, params, coords, idx, n_pixels, batch, labels, nullptr, s))) return rc;
         if ((rc = star_backward_pass(m, w, params, batch, loss_hist, it, s))) return rc;
-        star_upd_consts(u, opt, ep + 1, offset_first_step >= 0 && ep >= offset_first_step ? ep - offset_first_step + 1 : 0);
+        const int t_off = star_offset_step(ep, offset_first_step);
+        u.net = opt_consts(opt, ep + 1);
+        u.off = opt_consts(opt, t_off);
+        u.offset_on = t_off > 0;
         hipLaunchKernelGGL(star_update_kernel, dim3((m.P + 255) / 256), dim3(256), 0, s, u);
     }
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;
@@ -3624,8 +3556,6 @@ int inrfit_star_fit_dense(const InrStarDesc* star, float* params, float* opt_sta
     u.scal = w.scal;
     u.m = m;
     u.od = *opt;
-    u.one_minus_b1 = (float)(1.0 - (double)opt->beta1);
-    u.one_minus_b2 = (float)(1.0 - (double)opt->beta2);
     u.mode = 0;
     for (int img = 0; img < n_images; ++img) {
         float* prm = params + (size_t)img * m.P;
@@ -3639,13 +3569,11 @@ int inrfit_star_fit_dense(const InrStarDesc* star, float* params, float* opt_sta
             const int ep = step0 + it;
             const bool gate = lg && opt->logits_at_last_forward && it == steps - 1;
             if ((rc = star_dense_pass(m, w, prm, xy, tg, w.coef + 2 * img, loss->kind, n_pixels, gate ? lg : nullptr, true, s))) return rc;
-            const int t_off = offset_first_step >= 0 && ep >= offset_first_step ? ep - offset_first_step + 1 : 0;
+            const int t_off = star_offset_step(ep, offset_first_step);
             u.t = ep + 1;
-            bias_corrections(opt, u.t, &u.bc1, &u.bc2_sqrt);
+            u.net = opt_consts(opt, u.t);
+            u.off = opt_consts(opt, t_off);
             u.offset_on = t_off > 0;
-            u.bc1_off = 1.0;
-            u.bc2_sqrt_off = 1.f;
-            if (t_off > 0) bias_corrections(opt, t_off, &u.bc1_off, &u.bc2_sqrt_off);
             u.loss_hist = loss_hist ? loss_hist + (size_t)img * steps + it : nullptr;
             hipLaunchKernelGGL(star_dense_update_kernel, dim3((m.P + 1 + 255) / 256), dim3(256), 0, s, u);
         }

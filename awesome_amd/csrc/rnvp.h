@@ -924,15 +924,14 @@ struct RnvpUpdArgs {
     float* grads_out;     // [n_images][RP] (mode 1)
     const float* slab1;
     const float* slab2;
-    const float* lr_hdr;  // ICNN opt-state header: lr of this step is hdr[t & 1]; null -> opt_desc.lr
+    const float* lr_hdr;  // ICNN opt-state header: this step's lr; null -> opt_desc.lr
     long long hdr_stride;
     const int32_t* status;   // per image: a non-finite loss freezes the image (like the ICNN update)
     InrOptDesc opt_desc;
     RnvpMap m;
     int blocks1, S1, chunks;
     int t;
-    double bc1;
-    float bc2_sqrt, one_minus_b1, one_minus_b2;
+    OptConsts c;
     float wd_flow;        // weight decay of the flow_net group (path_connected_net.py:925); the linear has none
     int mode;             // 0 = optimizer step, 1 = gradients only
     // learn_flow_identity: the 1x1 linear is not part of the model; the loss comes as per-block partial sums
@@ -953,18 +952,8 @@ struct RnvpUpdArgs {
 
 __device__ __forceinline__ float opt_apply(const RnvpUpdArgs& u, float gmul, float p, float g, float lr, float wd, float* m_, float* v_) {
     g = g * gmul;   // the joint step's detached clip factor (x 1.0 is exact: the plain fits are bit-identical)
-    if (wd != 0.f) g = __fadd_rn(g, __fmul_rn(wd, p));
     float m = *m_, v = *v_;
-    m = __fadd_rn(m, __fmul_rn(u.one_minus_b1, __fsub_rn(g, m)));
-    const float clr = (float)((double)lr / u.bc1);
-    if (u.opt_desc.kind == INR_OPT_ADAM) {
-        v = __fadd_rn(__fmul_rn(v, u.opt_desc.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, g), g));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), u.bc2_sqrt), u.opt_desc.eps);
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-clr, m), denom));
-    } else {
-        v = fmaxf(__fmul_rn(v, u.opt_desc.beta2), __fadd_rn(fabsf(g), u.opt_desc.eps));
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-clr, m), v));
-    }
+    p = opt_step(u.opt_desc.kind, u.c, opt_step_size(lr, u.c.bc1), wd, g, p, m, v);
     *m_ = m;
     *v_ = v;
     return p;
@@ -978,18 +967,12 @@ __device__ __forceinline__ void rnvp_update_body(const RnvpUpdArgs& u, const int
     const float gmul = u.gscale != nullptr ? u.gscale[img] : 1.f;
     const RnvpMap& m = u.m;
     const int F = m.F, HID = m.HID;
-    // one source of truth with the ICNN update: the flag it has written for step t (hdr[6 + ((t + 1) & 1)]; `status` may be NULL) -
-    // or, when that update runs in THIS launch (pcn_update_kernel), the same decision from the same numbers (frozen_in_launch)
-    const bool frozen = !isfinite(gmul) ||    // the joint step's composite loss was not finite (joint_step_finish_kernel)
-                        (u.loss_part != nullptr
-                             ? frozen_in_launch(u.loss_part, u.loss_wgs, u.loss_stride, u.lr_hdr, u.hdr_stride, u.t, img, tid)
-                             : ((u.lr_hdr != nullptr && u.lr_hdr[(size_t)img * u.hdr_stride + 6 + ((u.t + 1) & 1)] != 0.f) ||
-                                (u.status != nullptr && u.status[img] != INR_STATUS_OK)));
+    const bool frozen = deformation_frozen(gmul, u.loss_part, u.loss_wgs, u.loss_stride, u.lr_hdr, u.hdr_stride, u.status, u.t, img, tid);
     float* __restrict__ rp = u.RP + (size_t)img * m.RP;
     float* __restrict__ om = u.opt ? u.opt + (size_t)img * 2 * m.RP : nullptr;
     float* __restrict__ ov = om ? om + m.RP : nullptr;
     float* __restrict__ go = u.grads_out ? u.grads_out + (size_t)img * m.RP : nullptr;
-    const float lr = u.lr_hdr ? u.lr_hdr[(size_t)img * u.hdr_stride + (u.t & 1)] : u.opt_desc.lr;
+    const float lr = opt_hdr_lr(u.lr_hdr, u.hdr_stride, img, u.t, u.opt_desc.lr);
     // per-point-scalar gradients of this block: fixed-order sums over the point blocks
     const int k0 = f < F ? f * 4 * C : F * 4 * C, nk = f < F ? 4 * C : 2 * C;
     {   // all nk sums at once: every thread walks its share of the point blocks for all scalars (their nk slots are adjacent

@@ -90,7 +90,7 @@ __global__ void seq_begin_kernel(SeqPlateau* st, double lr0) {
 
 // One thread, fixed order, no atomics.  The epoch loss is summed as the host loop sums it - acc = acc + loss_b / n_batches in fp32,
 // where torch divides a device scalar by a Python number as a product with the fp32 reciprocal - and the scheduler's decision is
-// taken in double on (double)acc.  next_slot: header slot the NEXT optimizer step reads its learning rate from (hdr[t & 1]); the
+// taken in double on (double)acc.  next_slot: header slot the NEXT optimizer step reads its learning rate from (opt_hdr_lr_of); the
 // RealNVP half of the update reads the same slot.
 __global__ void seq_epoch_end_kernel(const float* __restrict__ batch_loss, int n_batches, float* __restrict__ epoch_loss,
                                      float* __restrict__ hdr, int next_slot, SeqPlateau* __restrict__ st, const int32_t* __restrict__ status,
@@ -120,9 +120,9 @@ __global__ void seq_epoch_end_kernel(const float* __restrict__ batch_loss, int n
     st->best = best;
     st->num_bad = num_bad;
     hdr[next_slot] = (float)lr;
-    hdr[2] = (float)lr;
-    hdr[3] = (float)best;
-    hdr[4] = (float)num_bad;
+    hdr[OPT_HDR_LR] = (float)lr;
+    hdr[OPT_HDR_BEST] = (float)best;
+    hdr[OPT_HDR_NUM_BAD] = (float)num_bad;
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
@@ -271,7 +271,7 @@ int inrfit_pcn_fit_sequence(const InrModelDesc* model, const InrRnvpDesc* rnvp, 
             c.f.update(c.b, true, s);
             prev = &c;
         }
-        hipLaunchKernelGGL(seq_epoch_end_kernel, dim3(1), dim3(64), 0, s, (const float*)l.batch_loss, nb, epoch_loss + e, hdr, (k + 1) & 1,
+        hipLaunchKernelGGL(seq_epoch_end_kernel, dim3(1), dim3(64), 0, s, (const float*)l.batch_loss, nb, epoch_loss + e, hdr, opt_hdr_lr_of(k + 1),
                            l.plateau, (const int32_t*)status, sc);
     }
     return hipGetLastError() == hipSuccess ? INR_OK : INR_ELAUNCH;

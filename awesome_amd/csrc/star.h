@@ -274,32 +274,44 @@ struct StarUpdArgs {
     const float* scal;   // loss, db2, doffset[2]
     float* grads_out;    // [P] or null: the assembled gradient (mode 1: no optimizer step)
     StarMap m;
-    float lr, beta1, beta2, eps, one_minus_b1, one_minus_b2;
-    double bc1, bc1_off;             // 1 - beta1^t for the network / for the centre (its own step count)
-    float bc2_sqrt, bc2_sqrt_off;
+    float lr;
+    OptConsts net, off;              // the network's / the centre's (its own step count; t = 0: it takes no step)
     int offset_on;                   // the centre takes this step
     int mode;                        // 0 = Adam + projection, 1 = gradients only
 };
 
-// torch.optim.Adam, single-tensor arithmetic in torch's operation order (as icnn_update_kernel), then W2_r.weight <- relu(W2_r.weight)
+// Where the gradient of parameter i < P comes from: -1 = `g` (a scalar of `scal`, an element of the h x h product), else the column
+// sum colq of hidden unit j - which each update kernel forms from what its backward pass left (chunk partials / the accumulated col).
+__device__ __forceinline__ int star_grad_source(const StarMap& m, const int i, const float* __restrict__ scal, const float* __restrict__ gW1,
+                                                float& g, int& j) {
+    int colq = -1;
+    if (i < m.p_w0()) g = scal[2 + i];
+    else if (i < m.p_b0()) { j = (i - m.p_w0()) >> 1; colq = 5 + ((i - m.p_w0()) & 1); }
+    else if (i < m.p_w1()) { j = i - m.p_b0(); colq = 4; }
+    else if (i < m.p_b1()) g = gW1[i - m.p_w1()];
+    else if (i < m.p_w2()) { j = i - m.p_b1(); colq = 0; }
+    else if (i < m.p_b2()) { j = i - m.p_w2(); colq = 2; }
+    else if (i < m.p_w1r()) g = scal[1];
+    else if (i < m.p_b1r()) { j = i - m.p_w1r(); colq = 1; }
+    else if (i < m.p_w2r()) { j = i - m.p_b1r(); colq = 0; }
+    else if (i < m.p_b2r()) { j = i - m.p_w2r(); colq = 3; }
+    else if (i < m.P) g = scal[1];
+    return colq;
+}
+// W2_r.weight <- relu(W2_r.weight) behind the step
+__device__ __forceinline__ float star_project(const StarMap& m, const int i, const float p) {
+    return (i >= m.p_w2r() && i < m.p_b2r()) ? fmaxf(p, 0.f) : p;
+}
+
+// torch.optim.Adam, single-tensor arithmetic in torch's operation order (optim.h), then W2_r.weight <- relu(W2_r.weight)
 __global__ __launch_bounds__(256) void star_update_kernel(const StarUpdArgs u) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const StarMap& m = u.m;
     if (i >= m.P) return;
     const int h = m.h;
-    float g;
-    int colq = -1, j = 0;
-    if (i < m.p_w0()) g = u.scal[2 + i];
-    else if (i < m.p_b0()) { j = (i - m.p_w0()) >> 1; colq = 5 + ((i - m.p_w0()) & 1); }
-    else if (i < m.p_w1()) { j = i - m.p_b0(); colq = 4; }
-    else if (i < m.p_b1()) g = u.gW1[i - m.p_w1()];
-    else if (i < m.p_w2()) { j = i - m.p_b1(); colq = 0; }
-    else if (i < m.p_b2()) { j = i - m.p_w2(); colq = 2; }
-    else if (i < m.p_w1r()) g = u.scal[1];
-    else if (i < m.p_b1r()) { j = i - m.p_w1r(); colq = 1; }
-    else if (i < m.p_w2r()) { j = i - m.p_b1r(); colq = 0; }
-    else if (i < m.p_b2r()) { j = i - m.p_w2r(); colq = 3; }
-    else g = u.scal[1];
+    float g = 0.f;
+    int j = 0;
+    const int colq = star_grad_source(m, i, u.scal, u.gW1, g, j);
     if (colq >= 0) {
         g = 0.f;
 #pragma unroll
@@ -310,12 +322,8 @@ __global__ __launch_bounds__(256) void star_update_kernel(const StarUpdArgs u) {
     const bool is_off = i < m.p_w0();
     if (is_off && !u.offset_on) return;     // requires_grad = False: torch's Adam skips a parameter without a gradient
     float p = u.prm[i], mm = u.opt[i], v = u.opt[m.P + i];
-    mm = __fadd_rn(mm, __fmul_rn(u.one_minus_b1, __fsub_rn(g, mm)));
-    v = __fadd_rn(__fmul_rn(v, u.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, g), g));
-    const float step_size = (float)((double)u.lr / (is_off ? u.bc1_off : u.bc1));
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), is_off ? u.bc2_sqrt_off : u.bc2_sqrt), u.eps);
-    p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, mm), denom));
-    if (i >= m.p_w2r() && i < m.p_b2r()) p = fmaxf(p, 0.f);
+    const OptConsts c = is_off ? u.off : u.net;
+    p = star_project(m, i, adam_step(c, opt_step_size(u.lr, c.bc1), 0.f, g, p, mm, v));
     u.prm[i] = p;
     u.opt[i] = mm;
     u.opt[m.P + i] = v;
@@ -447,18 +455,16 @@ struct StarDenseUpdArgs {
     int32_t* status;     // mode 0: this image's word
     StarMap m;
     InrOptDesc od;
-    float one_minus_b1, one_minus_b2;
-    double bc1, bc1_off;             // 1 - beta1^t for the network / for the centre (its own step count)
-    float bc2_sqrt, bc2_sqrt_off;
+    OptConsts net, off;              // the network's / the centre's (its own step count; t = 0: it takes no step)
     int offset_on;                   // the centre takes this step
     int t;                           // 1-based optimizer step index (selects the header's double-buffer slots)
     int mode;                        // 0 = optimizer step + projection + plateau, 1 = gradients and loss only
 };
 
 // Thread i < P: one parameter (torch's single-tensor Adam / Adamax in its operation order, then W2_r.weight <- relu(W2_r.weight));
-// thread P: the loss, the "frozen by a non-finite loss" flag and ReduceLROnPlateau in the header - the discipline of icnn_update_kernel:
-// this step's learning rate and the flag left by the previous step sit in slot [t & 1], the next step's are written to the other one,
-// and every thread derives "frozen" from the flag and from THIS step's loss, so which parameters move does not depend on block timing.
+// thread P: the loss, the "frozen by a non-finite loss" flag and ReduceLROnPlateau in the header (optim.h, shared with
+// icnn_update_kernel): every thread derives "frozen" from the flag the previous step left and from THIS step's loss, so which
+// parameters move does not depend on block timing.
 __global__ __launch_bounds__(256) void star_dense_update_kernel(const StarDenseUpdArgs u) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const StarMap& m = u.m;
@@ -466,18 +472,8 @@ __global__ __launch_bounds__(256) void star_dense_update_kernel(const StarDenseU
     const int h = m.h;
     const float loss = u.scal[0];
     float g = 0.f;
-    int colq = -1, j = 0;
-    if (i < m.p_w0()) g = u.scal[2 + i];
-    else if (i < m.p_b0()) { j = (i - m.p_w0()) >> 1; colq = 5 + ((i - m.p_w0()) & 1); }
-    else if (i < m.p_w1()) { j = i - m.p_b0(); colq = 4; }
-    else if (i < m.p_b1()) g = u.gW1[i - m.p_w1()];
-    else if (i < m.p_w2()) { j = i - m.p_b1(); colq = 0; }
-    else if (i < m.p_b2()) { j = i - m.p_w2(); colq = 2; }
-    else if (i < m.p_w1r()) g = u.scal[1];
-    else if (i < m.p_b1r()) { j = i - m.p_w1r(); colq = 1; }
-    else if (i < m.p_w2r()) { j = i - m.p_b1r(); colq = 0; }
-    else if (i < m.p_b2r()) { j = i - m.p_w2r(); colq = 3; }
-    else if (i < m.P) g = u.scal[1];
+    int j = 0;
+    const int colq = star_grad_source(m, i, u.scal, u.gW1, g, j);
     if (colq >= 0) g = u.col[colq * h + j];
     if (u.mode != 0) {
         if (i < m.P) u.grads_out[i] = g;
@@ -485,52 +481,19 @@ __global__ __launch_bounds__(256) void star_dense_update_kernel(const StarDenseU
         return;
     }
     float* __restrict__ hdr = u.opt + 2 * (size_t)m.P;
-    const bool bad_before = hdr[6 + (u.t & 1)] != 0.f;   // written by the PREVIOUS step's launch (double buffer like the lr: no race)
-    const float lr_now = hdr[u.t & 1];
+    const bool bad_before = hdr[opt_hdr_frozen_before(u.t)] != 0.f;
+    const float lr_now = hdr[opt_hdr_lr_of(u.t)];
     const bool frozen = bad_before || !isfinite(loss);
     if (i == m.P) {
-        if (u.loss_hist) u.loss_hist[0] = loss;
-        float lr = lr_now;
-        hdr[6 + ((u.t + 1) & 1)] = frozen ? 1.f : 0.f;
-        if (frozen) {
-            u.status[0] = INR_STATUS_NONFINITE;
-        } else if (u.od.plateau) {   // torch semantics, mode 'min', relative threshold
-            float best = hdr[3];
-            int num_bad = (int)hdr[4];
-            if (loss < best * (1.f - u.od.plateau_threshold)) {
-                best = loss;
-                num_bad = 0;
-            } else {
-                num_bad += 1;
-            }
-            if (num_bad > u.od.plateau_patience) {
-                const float nlr = fmaxf(lr * u.od.plateau_factor, u.od.plateau_min_lr);
-                if (lr - nlr > u.od.plateau_eps) lr = nlr;
-                num_bad = 0;
-            }
-            hdr[3] = best;
-            hdr[4] = (float)num_bad;
-        }
-        hdr[(u.t + 1) & 1] = lr;   // learning rate of the NEXT step (the scheduler steps after the optimizer)
-        hdr[2] = lr;
-        hdr[5] = loss;
+        opt_header_step(hdr, u.od, u.t, loss, frozen, lr_now, u.loss_hist, u.status);
         return;
     }
     if (frozen) return;
     const bool is_off = i < m.p_w0();
     if (is_off && !u.offset_on) return;     // requires_grad = False: torch's optimizers skip a parameter without a gradient
     float p = u.prm[i], mm = u.opt[i], v = u.opt[m.P + i];
-    const float step_size = (float)((double)lr_now / (is_off ? u.bc1_off : u.bc1));
-    mm = __fadd_rn(mm, __fmul_rn(u.one_minus_b1, __fsub_rn(g, mm)));
-    if (u.od.kind == INR_OPT_ADAM) {
-        v = __fadd_rn(__fmul_rn(v, u.od.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, g), g));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), is_off ? u.bc2_sqrt_off : u.bc2_sqrt), u.od.eps);
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, mm), denom));
-    } else {   // Adamax: exp_inf = max(beta2 exp_inf, |grad| + eps); p -= lr / bc1 * m / exp_inf
-        v = fmaxf(__fmul_rn(v, u.od.beta2), __fadd_rn(fabsf(g), u.od.eps));
-        p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, mm), v));
-    }
-    if (i >= m.p_w2r() && i < m.p_b2r()) p = fmaxf(p, 0.f);
+    const OptConsts c = is_off ? u.off : u.net;
+    p = star_project(m, i, opt_step(u.od.kind, c, opt_step_size(lr_now, c.bc1), 0.f, g, p, mm, v));
     u.prm[i] = p;
     u.opt[i] = mm;
     u.opt[m.P + i] = v;

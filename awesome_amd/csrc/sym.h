@@ -129,17 +129,17 @@ struct SymUpdArgs {
     float* opt;             // [n_images][6] exp_avg[3] | exp_avg_sq[3] (mode 0)
     float* grads_out;       // [n_images][3] (mode 1)
     const float* part;      // [n_images][blocks][3]
-    const float* lr_hdr;    // ICNN opt-state header of image 0: the lr of this step is hdr[t & 1], its "frozen" flag hdr[6 + ((t + 1) & 1)]
+    const float* lr_hdr;    // ICNN opt-state header of image 0: this step's lr and the "frozen" flag its update has written (optim.h)
     long long hdr_stride;
     const int32_t* status;  // per image, or null
     const float* gscale;    // [n_images] factor on the gradient (a joint step's detached clip factor), or null
     int blocks, t, mode;    // mode 0 = Adam step, 1 = gradients only
-    double bc1;
-    float bc2_sqrt, one_minus_b1, one_minus_b2, beta2, eps, wd;
+    OptConsts c;
+    float wd;
 };
 
 // One wave per image; thread k < 3 owns pose parameter k: its block partials added in block order, then torch.optim.Adam's
-// single-tensor step in torch's operation order (as flow.h's adam_apply).  An image the ICNN update of this step has frozen (a
+// single-tensor step in torch's operation order (optim.h's adam_step).  An image the ICNN update of this step has frozen (a
 // non-finite loss, now or earlier in the call) keeps its pose and its moments.
 __global__ __launch_bounds__(64) void sym_update_kernel(const SymUpdArgs u) {
     const int img = blockIdx.x, k = threadIdx.x;
@@ -152,20 +152,14 @@ __global__ __launch_bounds__(64) void sym_update_kernel(const SymUpdArgs u) {
         return;
     }
     const float gmul = u.gscale != nullptr ? u.gscale[img] : 1.f;
-    const float* hdr = u.lr_hdr + (size_t)img * u.hdr_stride;
-    if (!isfinite(gmul) || hdr[6 + ((u.t + 1) & 1)] != 0.f || (u.status != nullptr && u.status[img] != INR_STATUS_OK)) return;
-    const float lr = hdr[u.t & 1];
+    __builtin_assume(u.lr_hdr != nullptr);   // a pose never steps without the ICNN header: no null tests between the loads below
+    if (deformation_frozen(gmul, nullptr, 0, 0, u.lr_hdr, u.hdr_stride, u.status, u.t, img, k)) return;   // (the ICNN update ran one launch earlier)
+    const float lr = opt_hdr_lr(u.lr_hdr, u.hdr_stride, img, u.t, 0.f);
     float* pp = u.pose + (size_t)img * SYM_POSE + k;
     float* mp = u.opt + (size_t)img * 2 * SYM_POSE + k;
     float* vp = mp + SYM_POSE;
-    float p = *pp, m = *mp, v = *vp;
-    g = g * gmul;   // (x 1.0 is exact)
-    if (u.wd != 0.f) g = __fadd_rn(g, __fmul_rn(u.wd, p));
-    m = __fadd_rn(m, __fmul_rn(u.one_minus_b1, __fsub_rn(g, m)));
-    v = __fadd_rn(__fmul_rn(v, u.beta2), __fmul_rn(__fmul_rn(u.one_minus_b2, g), g));
-    const float step_size = (float)((double)lr / u.bc1);
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), u.bc2_sqrt), u.eps);
-    *pp = __fadd_rn(p, __fdiv_rn(__fmul_rn(-step_size, m), denom));
+    float m = *mp, v = *vp;
+    *pp = adam_step(u.c, opt_step_size(lr, u.c.bc1), u.wd, g * gmul, *pp, m, v);   // (x 1.0 is exact)
     *mp = m;
     *vp = v;
 }

@@ -4,7 +4,7 @@ fit_run, joint_step_run, joint_prior_step_run), on small shapes with fixed seeds
 hidden layers; layer by layer: h = 136 x 1 and h = 64 x 3), without a deformation, behind the RealNVP and - fused only - behind the
 coupling flow; a 24 x 20 and a ragged 23 x 19 separable grid and the latter as explicit coordinates, one and two images.  Behind
 them the wrappers with loops of their own (`extras`): the pixel-minibatch fits, the pose fits (h = 130 and the layer-by-layer 150),
-the star prior, the flow's identity pre-fit and the two sequence fits, on a 96-point pool with batches of 32 and 17.  Two builds of the
+the star prior (minibatch and dense, Adam and Adamax), the flow's identity pre-fit and the two sequence fits, on a 96-point pool with batches of 32 and 17.  Two builds of the
 library - or two versions of the Python binding over one build - that print the same lines compute the same bits:
 
     INRFIT_LIB=old/libinrfit.so INRFIT_ABI_ANY=1 python tools/driver_hashes.py > old.txt
@@ -131,6 +131,15 @@ def extras(dev, pl):
     for index, _ in tables(13):
         r = ST.star_fit(sspec, sp.clone(), coords, labels, index, step0=0, offset_first_step=3)
         show(f"star fit b{index.shape[1]}", params=r.params, opt=r.opt_state, hist=r.loss_hist)
+    # ---- ... and its dense many-image form on the whole pool (the centre steps from step 3 on)
+    gs = torch.Generator().manual_seed(12)
+    for n in (1, 2):
+        dp, dt = (0.3 * torch.randn(n, sspec.n_params, generator=gs)).to(dev), targets(n, POOL, 20 + n, dev)
+        lo, gr = ST.star_loss_grad_dense(sspec, dp, coords, dt)
+        show(f"star n{n} loss_grad_dense", loss=lo, grads=gr)
+        for optimizer in ("adam", "adamax"):
+            r = ST.star_fit_dense(sspec, dp.clone(), coords, dt, 5, optimizer=optimizer, plateau=pl, offset_first_step=3)
+            show(f"star n{n} fit_dense {optimizer}", params=r.params, opt=r.opt_state, hist=r.loss_hist, logits=r.logits, status=r.status)
     # ---- the flow's identity pre-fit and the sequence fits (T = 5 frames of the pool, batches of 2: the last one short)
     for n in (1, 2):
         fp = rnvp_params(rspec, grid, n, 9000 + n, dev)
