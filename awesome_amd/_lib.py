@@ -183,6 +183,11 @@ EXPORTS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_int64,
                                            C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_cdn_wide_minibatch_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrFlowDesc), C.c_int64, C.c_int]),
+    "inrfit_cdn_wide_fit_minibatch": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrFlowDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32),
+                                                C.c_int64, C.POINTER(InrLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_sym_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrGridDesc), C.c_int]),
     "inrfit_sym_minibatch_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.c_int64, C.c_int]),
     "inrfit_sym_forward": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrSymDesc), C.c_void_p, C.c_void_p, C.POINTER(InrGridDesc),
@@ -228,6 +233,12 @@ EXPORTS = {
                                                C.c_void_p, C.POINTER(InrJointPriorDesc), C.c_void_p, C.POINTER(InrOptDesc), C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "inrfit_pcn_wide_joint_step": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrRnvpDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p, C.c_void_p,
+                                             C.POINTER(InrJointLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "inrfit_cdn_wide_joint_step_workspace_bytes": (C.c_int64, [C.POINTER(InrModelDesc), C.POINTER(InrFlowDesc),
+                                                               C.POINTER(InrGridDesc)]),
+    "inrfit_cdn_wide_joint_step": (C.c_int, [C.POINTER(InrModelDesc), C.POINTER(InrFlowDesc), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.POINTER(InrGridDesc), C.c_void_p, C.c_void_p,
                                              C.POINTER(InrJointLossDesc), C.POINTER(InrOptDesc), C.c_float, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -135,7 +135,7 @@ def _layer_by_layer_joint(ispec) -> bool:
     return ispec.supported() and not ispec.fused() and not ispec.general and ispec.act0 == "relu"
 
 
-def _fused_prior_family(prior, kind: str, fused_layer_by_layer: bool):
+def _fused_prior_family(prior, kind: str, fused_layer_by_layer: bool, fused_cdn_layer_by_layer: bool = False):
     """Which fused joint step serves `prior` under optimizer `kind`: (family, ispec, dspec, wide), or None = the autograd step.
     Host logic only (no device), so the routing of a model class can be checked anywhere."""
     from .model.star_net import StarShapedNet
@@ -150,9 +150,11 @@ def _fused_prior_family(prior, kind: str, fused_layer_by_layer: bool):
             return None
         family = "pcn" if type(dspec).__name__ == "RnvpSpec" else "cdn"
         wide = not ispec.fused()
-        # its ICNN runs layer by layer: the composite's autograd bridges - unless asked for (fused_layer_by_layer) and the
-        # composite is a PathConnectedNet (inrfit_pcn_wide_joint_step; ConvexDiffeomorphismNet has no such step)
-        if wide and not (fused_layer_by_layer and family == "pcn" and _layer_by_layer_joint(ispec)):
+        # its ICNN runs layer by layer: the composite's autograd step - unless asked for: fused_layer_by_layer for a
+        # PathConnectedNet (inrfit_pcn_wide_joint_step), fused_cdn_layer_by_layer on top of it for a ConvexDiffeomorphismNet
+        # (inrfit_cdn_wide_joint_step; a switch of its own, so that the first one alone keeps routing as it did)
+        asked = fused_layer_by_layer and (family == "pcn" or fused_cdn_layer_by_layer)
+        if wide and not (asked and _layer_by_layer_joint(ispec)):
             return None
         if kind != "adam" and family == "cdn":
             return None
@@ -258,7 +260,9 @@ class JointTrainer:
                       (awesome_amd.joint); seg.backward(dseg)
                       (an ICNN of the layer-by-layer path - n_hidden > 130 or more than two hidden layers - alone or behind a
                       PathConnectedNet's RealNVP: only under `fused_layer_by_layer`, then inrfit_wide_joint_step /
-                      inrfit_pcn_wide_joint_step, and inrfit_wide_joint_prior_step on the `convexity` route; else `autograd`)
+                      inrfit_pcn_wide_joint_step, and inrfit_wide_joint_prior_step on the `convexity` route; behind a
+                      ConvexDiffeomorphismNet's coupling flow only with `fused_cdn_layer_by_layer` as well, then
+                      inrfit_cdn_wide_joint_step; else `autograd`)
                else   `convexity` where that applies and the criterion has no such desc; `autograd` for everything else it
                       refuses: batch > 1, the step that initialises ActNorm
     convexity  takes  (`fused_convexity_losses`) AwesomeImageLoss, AwesomeImageLossJoint, AwesomeLoss, AwesomeLossJoint on an ICNN
@@ -292,9 +296,12 @@ class JointTrainer:
     def __init__(self, wrapper: torch.nn.Module, bank: PriorBank, criterion: Callable, optimizer: torch.optim.Optimizer,
                  fused: Optional[bool] = None, shared_prior_moments: bool = True, check_finite: str = "epoch",
                  fused_extra_penalty: bool = False, fused_convexity_losses: bool = False, fused_segmentation: bool = False,
-                 fused_layer_by_layer: bool = False):
+                 fused_layer_by_layer: bool = False, fused_cdn_layer_by_layer: bool = False):
         if fused_segmentation and not fused_convexity_losses:
             raise ValueError("fused_segmentation runs inside the convexity losses' fused step: it needs fused_convexity_losses=True")
+        if fused_cdn_layer_by_layer and not fused_layer_by_layer:
+            raise ValueError("fused_cdn_layer_by_layer extends the layer-by-layer fused steps to ConvexDiffeomorphismNet: it needs "
+                             "fused_layer_by_layer=True")
         if check_finite not in ("step", "epoch"):
             raise ValueError("check_finite: 'step' (raise before backward like the reference, one host sync per step) or 'epoch' "
                              "(device flag, the caller polls raise_if_failed())")
@@ -306,6 +313,7 @@ class JointTrainer:
         self.fused_convexity_losses = bool(fused_convexity_losses)
         self.fused_segmentation = bool(fused_segmentation)
         self.fused_layer_by_layer = bool(fused_layer_by_layer)
+        self.fused_cdn_layer_by_layer = bool(fused_cdn_layer_by_layer)
         # (both names date from the CNNNet share; they serve the FCNet share, inrfit_fcseg_step, as well)
         self._cnn_grads: Optional[torch.Tensor] = None     # the segmentation network's flat gradient (fused_segmentation)
         self.cnnseg_status: Optional[torch.Tensor] = None   # status word of the last inrfit_cnnseg_step / inrfit_fcseg_step
@@ -396,7 +404,7 @@ class JointTrainer:
             return None
         if not pids <= {id(p) for p in groups[0]["params"]}:
             return None
-        fam = _fused_prior_family(prior, kind, self.fused_layer_by_layer)
+        fam = _fused_prior_family(prior, kind, self.fused_layer_by_layer, getattr(self, "fused_cdn_layer_by_layer", False))
         if fam is None:
             return None
         family, ispec, dspec, wide = fam
@@ -492,8 +500,9 @@ class JointTrainer:
                 res = step_fn(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
                               step=t, optimizer=plan["kind"], flow_weight_decay=0.0, **hp)
             else:
-                res = J.cdn_joint_step(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
-                                       step=t, weight_decay_on_weight_g=0.0, **hp)
+                step_fn = J.cdn_wide_joint_step if plan["wide"] else J.cdn_joint_step
+                res = step_fn(plan["ispec"], plan["dspec"], row[:P], row[P:], iopt, fopt, grid, segd, tgt, desc,
+                              step=t, weight_decay_on_weight_g=0.0, **hp)
         self._latch(res)
         self._check_finite()
         if seg.requires_grad:

@@ -1168,6 +1168,9 @@ static bool use_wide(const InrModelDesc* m) { return find_entry(m) == nullptr &&
 // steps accept (the encode shapes stay refused there).
 static bool pcn_wide_shape(const InrModelDesc* m) { return use_wide(m) && m->act0 == INR_ACT_RELU && !wide_desc_general(m); }
 
+// ... and behind the coupling flow, which is 2-D only: every other shape keeps the answers of the fused route's checks
+static bool cdn_wide_shape(const InrModelDesc* m) { return m && pcn_wide_shape(m) && m->in_features == 2; }
+
 long long align256(long long b) { return (b + 255) / 256 * 256; }
 
 // the layer-by-layer workspace behind a deformation's buffers (an ICNN-form shape): logits [N] | dL/dlogits [N] | ONE image's
@@ -1478,8 +1481,12 @@ int64_t inrfit_cdn_workspace_bytes(const InrModelDesc* model, const InrFlowDesc*
     if (!flow_ok(flow)) return INR_EUNSUPPORTED;
     if (!grid || grid->n_points <= 0 || n_images <= 0) return INR_EINVAL;
     const KernelEntry* e = model ? find_entry(model) : nullptr;
-    if (model && !e) return INR_EUNSUPPORTED;
-    return carve_cdn(flow, grid, n_images, nullptr).bytes + (e ? align256(carve(e, grid->n_points, n_images, nullptr).bytes) : 0);
+    const long long own = carve_cdn(flow, grid, n_images, nullptr).bytes;
+    if (model && !e) {   // the layer-by-layer ICNN behind the flow
+        if (!cdn_wide_shape(model)) return INR_EUNSUPPORTED;
+        return own + carve_wide_behind(make_wide_map(model), grid->n_points, n_images, nullptr).bytes;
+    }
+    return own + (e ? align256(carve(e, grid->n_points, n_images, nullptr).bytes) : 0);
 }
 
 int inrfit_flow_forward(const InrFlowDesc* flow, const float* flow_params, const InrGridDesc* grid, int n_images,
@@ -2220,8 +2227,7 @@ int64_t inrfit_joint_step_workspace_bytes(const InrModelDesc* model, const InrGr
 //   train(k, params, pass, s)     the training pass of unit k -> gradients and loss in the unit's buffer (loss_column())
 //   grads_out(k, grads, loss, s)  ... out to the caller
 //   update(k, s)                  ... into the optimizer step.  Layer by layer it sits inside the unit loop: the buffer is one image's.
-// A DEFORMATION F is what runs in front of the backbone: NoDeform, FlowDeform (the coupling flow; fused backbone only) or
-// RnvpDeform.  It gives
+// A DEFORMATION F is what runs in front of the backbone: NoDeform, FlowDeform (the coupling flow) or RnvpDeform.  It gives
 //   none, dxd, bytes              whether it is NoDeform; where the pass writes dL/dcoords (null: none); bytes of the whole workspace
 //   check(b, ...), device()       every argument check and both carves (check_deformed); its set_lds
 //   begin(s)                      once per call, in front of the first forward
@@ -2497,7 +2503,6 @@ struct FlowDeform : CdnWs {   // ConvexDiffeomorphismNet: the ICNN behind the we
     }
     template <class B>
     int check(B& b, const InrModelDesc* model, const InrGridDesc* g, int n, void* ws, int64_t ws_bytes, bool) {
-        static_assert(B::fused, "the coupling flow runs over the fused backbone only");
         return check_deformed(*this, b, model, g, n, ws, ws_bytes);
     }
     int in_channels(const InrModelDesc* model) const { return model->in_features; }
@@ -2510,19 +2515,23 @@ struct FlowDeform : CdnWs {   // ConvexDiffeomorphismNet: the ICNN behind the we
         launch_flow_bwd(*this, flow, grid, n_images, s);
         launch_flow_update(*this, flow, n_images, 1, params, grads, s);
     }
-    void update(FusedIcnn& b, bool, hipStream_t s) {
+    template <class B>
+    void update(B& b, bool, hipStream_t s) {
         // the learning rate of THIS step sits in the ICNN header's [t & 1] (the plateau thread writes the next one into the other slot)
         const UpdArgs& u = b.u;
         const FlowUpdArgs uf = make_flow_upd_args(*this, 0, params, opt_state, nullptr, &u.opt, wd_g, u.t, b.hdr(), b.opt_stride(),
                                                   b.status(), u.gscale);
-        if (upd_union_ok(b.e->img.sl_cols, 2 * flow->num_coupling + 1)) {
-            launch_flow_bwd(*this, flow, grid, n_images, s);
-            launch_cdn_update(b.e, u, uf, flow, n_images, s);   // (the ICNN half writes `status`: the flow half gets none)
-        } else {
+        if constexpr (B::fused) {
+            if (upd_union_ok(b.e->img.sl_cols, 2 * flow->num_coupling + 1)) {
+                launch_flow_bwd(*this, flow, grid, n_images, s);
+                launch_cdn_update(b.e, u, uf, flow, n_images, s);   // (the ICNN half writes `status`: the flow half gets none)
+                return;
+            }
             launch_icnn_update(b.e, u, s);
-            launch_flow_bwd(*this, flow, grid, n_images, s);
-            launch_flow_update_args(flow, n_images, uf, s);
         }
+        // (layer by layer the unit loop has stepped every image's ICNN: its header holds the frozen flag of this step)
+        launch_flow_bwd(*this, flow, grid, n_images, s);
+        launch_flow_update_args(flow, n_images, uf, s);
     }
 };
 
@@ -2963,6 +2972,12 @@ int64_t inrfit_pcn_wide_joint_step_workspace_bytes(const InrModelDesc* model, co
     return align256(inrfit_pcn_workspace_bytes(model, rnvp, grid, 1)) + joint_ws_bytes(grid->n_points);
 }
 
+int64_t inrfit_cdn_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrFlowDesc* flow, const InrGridDesc* grid) {
+    if (!flow_ok(flow) || !cdn_wide_shape(model)) return INR_EUNSUPPORTED;
+    if (!grid || grid->n_points <= 0) return INR_EINVAL;
+    return align256(inrfit_cdn_workspace_bytes(model, flow, grid, 1)) + joint_ws_bytes(grid->n_points);
+}
+
 int inrfit_wide_joint_step(const InrModelDesc* model, float* params, float* opt_state, const InrGridDesc* grid, const float* seg,
                            const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, int step, float* loss_out,
                            float* dseg, float* prior_logits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
@@ -2982,6 +2997,18 @@ int inrfit_pcn_wide_joint_step(const InrModelDesc* model, const InrRnvpDesc* rnv
                           workspace_bytes, (hipStream_t)stream);
 }
 
+int inrfit_cdn_wide_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
+                               float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* seg,
+                               const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, float wd_on_weight_g,
+                               int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !seg || !target || !dseg) return INR_EINVAL;
+    if (!opt || opt->kind != INR_OPT_ADAM) return INR_EINVAL;   // the flow's optimizer step is Adam's only (checked before the model)
+    return joint_step_run(WideIcnn(), FlowDeform(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params,
+                          icnn_opt_state, grid, seg, target, desc, opt, step, loss_out, dseg, prior_logits, status, workspace,
+                          workspace_bytes, (hipStream_t)stream);
+}
+
 int inrfit_forward(const InrModelDesc* model, const float* params, const InrGridDesc* grid, int n_images, float* logits,
                    void* workspace, int64_t workspace_bytes, void* stream) {
     if (!params || !logits) return INR_EINVAL;
@@ -2994,6 +3021,9 @@ int inrfit_cdn_forward(const InrModelDesc* model, const InrFlowDesc* flow, const
                        const InrGridDesc* grid, int n_images, float* logits, void* workspace, int64_t workspace_bytes,
                        void* stream) {
     if (!icnn_params || !flow_params || !logits) return INR_EINVAL;
+    if (cdn_wide_shape(model))
+        return forward_run(WideIcnn(), FlowDeform(flow, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
+                           (hipStream_t)stream);
     return forward_run(FusedIcnn(), FlowDeform(flow, flow_params), model, icnn_params, grid, n_images, logits, workspace, workspace_bytes,
                        (hipStream_t)stream);
 }
@@ -3046,8 +3076,12 @@ int inrfit_cdn_loss_grad(const InrModelDesc* model, const InrFlowDesc* flow, con
                          int64_t workspace_bytes, void* stream) {
     if (!icnn_params || !flow_params || !targets || !loss_out || !icnn_grads || !flow_grads) return INR_EINVAL;
     if (const int rc = check_loss(loss)) return rc;
-    return loss_grad_run(FusedIcnn(), FlowDeform(flow, flow_params, nullptr, flow_grads), model, icnn_params, grid, targets, loss, n_images,
-                         loss_out, icnn_grads, workspace, workspace_bytes, (hipStream_t)stream);
+    const FlowDeform f(flow, flow_params, nullptr, flow_grads);
+    if (cdn_wide_shape(model))
+        return loss_grad_run(WideIcnn(), f, model, icnn_params, grid, targets, loss, n_images, loss_out, icnn_grads, workspace,
+                             workspace_bytes, (hipStream_t)stream);
+    return loss_grad_run(FusedIcnn(), f, model, icnn_params, grid, targets, loss, n_images, loss_out, icnn_grads, workspace,
+                         workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_pcn_loss_grad(const InrModelDesc* model, const InrRnvpDesc* rnvp, const float* icnn_params,
@@ -3084,9 +3118,12 @@ int inrfit_cdn_fit(const InrModelDesc* model, const InrFlowDesc* flow, float* ic
     if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state || !targets || !opt || steps < 0 || step0 < 0)
         return INR_EINVAL;
     if (const int rc = check_fit(opt, loss, true)) return rc;   // the flow's optimizer step is Adam's only
-    return fit_run(FusedIcnn(), FlowDeform(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g), model, icnn_params, icnn_opt_state,
-                   grid, targets, loss, opt, n_images, steps, step0, loss_hist, final_logits, status, workspace, workspace_bytes,
-                   (hipStream_t)stream);
+    const FlowDeform f(flow, flow_params, flow_opt_state, nullptr, wd_on_weight_g);
+    if (cdn_wide_shape(model))
+        return fit_run(WideIcnn(), f, model, icnn_params, icnn_opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist,
+                       final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
+    return fit_run(FusedIcnn(), f, model, icnn_params, icnn_opt_state, grid, targets, loss, opt, n_images, steps, step0, loss_hist,
+                   final_logits, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int inrfit_pcn_fit(const InrModelDesc* model, const InrRnvpDesc* rnvp, float* icnn_params, float* flow_params,

@@ -1,9 +1,11 @@
-// Pixel-minibatch fits on the device (include/inrfit.h: inrfit_fit_minibatch, inrfit_cdn_fit_minibatch): the teaser notebooks' loops
+// Pixel-minibatch fits on the device (include/inrfit.h: inrfit_fit_minibatch, inrfit_cdn_fit_minibatch, inrfit_cdn_wide_fit_minibatch): the teaser notebooks' loops
 // that train a coordinate net on a fresh random subset of the pixels at every optimizer step (convex.ipynb cell 3, repeating.ipynb
 // cell 4, diffeo_convex.ipynb cells 9-11, the DataLoader loop of imageRepresentationTest.ipynb cell 6) as ONE enqueue of plain stream
 // launches.  Step k is the pool gathered by row k of a device index table into a staging grid, the loss coefficients on the staging
 // targets, and then fit_step - what inrfit_fit / inrfit_cdn_fit(steps = 1, step0 = step0 + k) launch for that explicit grid, on the
 // same numbers - so a finite run ends bit for bit where the per-step host loop ends.  One kernel is new: the gather.
+// inrfit_cdn_fit_minibatch keeps to the ICNN shapes with a fused kernel (it answers the others with INR_EUNSUPPORTED, as
+// inrfit_cdn_joint_step does); inrfit_cdn_wide_fit_minibatch is the same call for the flow over a layer-by-layer ICNN (cdn_wide_shape).
 //
 // Included by inrfit.hip behind its fit skeletons (FusedIcnn, WideIcnn, NoDeform, FlowDeform, fit_step) and sequence.h (seq_grid).
 #pragma once
@@ -170,6 +172,20 @@ int64_t inrfit_minibatch_workspace_bytes(const InrModelDesc* model, const InrFlo
     return mb_layout(model->in_features, wide_desc_O(model), batch, n_images, nullptr).head_bytes + align256(own);
 }
 
+int64_t inrfit_cdn_wide_minibatch_workspace_bytes(const InrModelDesc* model, const InrFlowDesc* flow, int64_t batch, int n_images) {
+    if (!flow_ok(flow) || !cdn_wide_shape(model)) return INR_EUNSUPPORTED;
+    if (!mb_sizes_ok(model, 1, batch, n_images, 0, 0)) return INR_EINVAL;
+    long long own = 0;   // (as above: the largest carve over 1..batch)
+    InrGridDesc g = seq_grid(nullptr, 1);
+    for (long long c = 1; c <= batch; ++c) {
+        g.n_points = c;
+        const long long o = inrfit_cdn_workspace_bytes(model, flow, &g, n_images);
+        if (o < 0) return o;
+        if (o > own) own = o;
+    }
+    return mb_layout(model->in_features, wide_desc_O(model), batch, n_images, nullptr).head_bytes + align256(own);
+}
+
 int inrfit_fit_minibatch(const InrModelDesc* model, float* params, float* opt_state, const float* pool_coords,
                          const float* pool_targets, int64_t n_pool, const int32_t* index, const int32_t* counts, int64_t batch,
                          const InrLossDesc* loss, const InrOptDesc* opt, int n_images, int steps, int step0, float* loss_hist,
@@ -198,6 +214,21 @@ int inrfit_cdn_fit_minibatch(const InrModelDesc* model, const InrFlowDesc* flow,
     return mb_run<FusedIcnn>(FlowDeform(flow, flow_params, flow_opt_state, nullptr, weight_decay_on_weight_g), model, icnn_params,
                              icnn_opt_state, pool_coords, pool_targets, n_pool, index, counts, batch, loss, opt, n_images, steps, step0,
                              loss_hist, status, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int inrfit_cdn_wide_fit_minibatch(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
+                                  float* icnn_opt_state, float* flow_opt_state, const float* pool_coords, const float* pool_targets,
+                                  int64_t n_pool, const int32_t* index, const int32_t* counts, int64_t batch, const InrLossDesc* loss,
+                                  const InrOptDesc* opt, float weight_decay_on_weight_g, int n_images, int steps, int step0,
+                                  float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!icnn_params || !flow_params || !icnn_opt_state || !flow_opt_state) return INR_EINVAL;
+    if (const int rc = mb_check_args(model, pool_coords, pool_targets, n_pool, index, counts, batch, loss, opt, n_images, steps, step0,
+                                     true))   // the flow's optimizer step is Adam's only
+        return rc;
+    if (!flow_ok(flow) || !cdn_wide_shape(model)) return INR_EUNSUPPORTED;
+    return mb_run<WideIcnn>(FlowDeform(flow, flow_params, flow_opt_state, nullptr, weight_decay_on_weight_g), model, icnn_params,
+                            icnn_opt_state, pool_coords, pool_targets, n_pool, index, counts, batch, loss, opt, n_images, steps, step0,
+                            loss_hist, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -4,6 +4,10 @@
   cdn_forward   <- ConvexDiffeomorphismNet.forward                    (:173-178)
   cdn_loss_grad <- criterion(sigmoid(model(grid)), unaries).backward()  w.r.t. every parameter
   cdn_fit       <- the inner loop of ConvexDiffeomorphismNet.pretrain (:405-430)
+
+The ICNN may be a fused shape or one of the layer-by-layer path (n_hidden > 130 or more than two hidden layers): the same calls take
+both, and inrfit_cdn_workspace_bytes sizes the workspace of either.  `cdn_wide_joint_step` is the fused joint step of the second kind
+(inrfit_cdn_wide_joint_step; the fused shapes' is `awesome_amd.joint.cdn_joint_step`).
 """
 from __future__ import annotations
 
@@ -182,3 +186,13 @@ def cdn_fit(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_params: Tensor, flow_params
            X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), od, float(weight_decay_on_weight_g), n, int(steps), int(step0), hist, logits,
            status, ws=_ws(ispec, fspec, grid, n), device=dev)
     return CdnFitResult(ip, fp, icnn_opt_state, flow_opt_state, X.trim(hist, steps), logits, status)
+
+
+def cdn_wide_joint_step(ispec: K.IcnnSpec, fspec: FlowSpec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
+                        flow_opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor, desc, step: int, lr: float,
+                        betas=(0.9, 0.999), eps: float = 1e-8, weight_decay_on_weight_g: float = 0.0):
+    """One fused joint-training step of ICNN(flow(Ax + b)) over an ICNN of the layer-by-layer path, one image, every row updated in
+    place (inrfit_cdn_wide_joint_step through awesome_amd.joint's call path) -> JointStepResult."""
+    from . import joint as J
+    return J.cdn_wide_joint_step(ispec, fspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc, step,
+                                 lr, betas=betas, eps=eps, weight_decay_on_weight_g=weight_decay_on_weight_g)

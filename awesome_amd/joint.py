@@ -14,8 +14,9 @@ the segmentation share in torch (any criterion, second-order autograd included) 
 the prior's masked data term and the hard / soft align term, steps the row and returns d(prior's share) / d seg.
 
 `wide_joint_step`, `pcn_wide_joint_step` and `wide_joint_prior_step` are the same three steps for ICNN shapes of the layer-by-layer
-path (n_hidden > 130 or more than two hidden layers: inrfit_wide_joint_step / _pcn_wide_joint_step / _wide_joint_prior_step); the
-entry points above refuse those shapes, these refuse the shapes with a fused kernel."""
+path (n_hidden > 130 or more than two hidden layers: inrfit_wide_joint_step / _pcn_wide_joint_step / _wide_joint_prior_step), and
+`cdn_wide_joint_step` is `cdn_joint_step` for them (inrfit_cdn_wide_joint_step); the entry points above refuse those shapes, these
+refuse the shapes with a fused kernel."""
 from __future__ import annotations
 
 import ctypes as C
@@ -87,8 +88,8 @@ def _icnn_joint(entry: str, spec: K.IcnnSpec, params: Tensor, opt_state: Tensor,
 def _flow_joint(family: str, ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
                 flow_opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, od: L.InrOptDesc,
                 flow_weight_decay: float, step: int) -> JointStepResult:
-    """inrfit_pcn_joint_step / inrfit_cdn_joint_step: `fspec` is the family's flow (RnvpSpec / FlowSpec); family 'pcn_wide':
-    inrfit_pcn_wide_joint_step with its own workspace call."""
+    """inrfit_pcn_joint_step / inrfit_cdn_joint_step: `fspec` is the family's flow (RnvpSpec / FlowSpec); families 'pcn_wide' and
+    'cdn_wide': inrfit_pcn_wide_joint_step / inrfit_cdn_wide_joint_step, each with its own workspace call."""
     K._check_spec(ispec)
     dev, n = icnn_params.device, grid.n_points
     icnn_params, flow_params = X.flat(icnn_params, "icnn_params", ispec.n_params), X.flat(flow_params, "flow_params", fspec.n_params)
@@ -99,9 +100,9 @@ def _flow_joint(family: str, ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow
              target=target)
     md, fd, gd = ispec._desc, fspec._desc, grid._desc
     lib = L.load()
-    if family == "pcn_wide":
-        ws = _workspace((family, ispec, fspec, n),
-                        lambda: lib.inrfit_pcn_wide_joint_step_workspace_bytes(C.byref(md), C.byref(fd), C.byref(gd)), dev)
+    if family in ("pcn_wide", "cdn_wide"):
+        ws_bytes = getattr(lib, f"inrfit_{family}_joint_step_workspace_bytes")
+        ws = _workspace((family, ispec, fspec, n), lambda: ws_bytes(C.byref(md), C.byref(fd), C.byref(gd)), dev)
     else:
         ws_bytes = getattr(lib, f"inrfit_{family}_workspace_bytes")
         ws = _workspace((family, ispec, fspec, n),
@@ -134,6 +135,14 @@ def cdn_joint_step(ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: T
                    betas=(0.9, 0.999), eps: float = 1e-8, weight_decay_on_weight_g: float = 0.0) -> JointStepResult:
     """ConvexDiffeomorphismNet prior (ICNN behind the weight-normed coupling flow); Adam only, like its pretrain loop."""
     return _flow_joint("cdn", ispec, fspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
+                       X.opt_desc("adam", lr, betas, eps, clamp=True), weight_decay_on_weight_g, step)
+
+
+def cdn_wide_joint_step(ispec: K.IcnnSpec, fspec, icnn_params: Tensor, flow_params: Tensor, icnn_opt_state: Tensor,
+                        flow_opt_state: Tensor, grid: K.Grid, seg: Tensor, target: Tensor, desc: L.InrJointLossDesc, step: int,
+                        lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay_on_weight_g: float = 0.0) -> JointStepResult:
+    """`cdn_joint_step` over an ICNN of the layer-by-layer path (inrfit_cdn_wide_joint_step)."""
+    return _flow_joint("cdn_wide", ispec, fspec, icnn_params, flow_params, icnn_opt_state, flow_opt_state, grid, seg, target, desc,
                        X.opt_desc("adam", lr, betas, eps, clamp=True), weight_decay_on_weight_g, step)
 
 

@@ -98,6 +98,8 @@ def _table(index: Tensor, counts, device) -> Tuple[Tensor, Optional[C.Array], in
 
 
 def _workspace(spec: K.IcnnSpec, fspec: Optional[FL.FlowSpec], batch: int, n_images: int, device) -> Tensor:
+    if fspec is not None and not spec.fused():   # the flow over a layer-by-layer ICNN: its own entry pair
+        return X.workspace("inrfit_cdn_wide_minibatch_workspace_bytes", spec._desc, fspec._desc, batch, n_images, device=device)
     return X.workspace("inrfit_minibatch_workspace_bytes", spec._desc, fspec._desc if fspec is not None else None, batch, n_images,
                        device=device)
 
@@ -136,7 +138,8 @@ def cdn_fit_minibatch(ispec: K.IcnnSpec, fspec: FL.FlowSpec, icnn_params: Tensor
                       plateau: Optional[dict] = None, icnn_opt_state: Optional[Tensor] = None,
                       flow_opt_state: Optional[Tensor] = None, step0: int = 0, record_loss: bool = True) -> FL.CdnFitResult:
     """`fit_minibatch` for ICNN(flow(Ax + b)): `flow.cdn_fit`'s step (Adam over everything, weight decay on the weight_g group) on
-    the pixels index[k, :counts[k]] of the pool at step k.  No final logits (`flow.cdn_forward`)."""
+    the pixels index[k, :counts[k]] of the pool at step k.  No final logits (`flow.cdn_forward`).  An ICNN of the layer-by-layer path
+    (n_hidden > 130 or more than two hidden layers) goes through inrfit_cdn_wide_fit_minibatch, the same call for those shapes."""
     ip, fp, n = FL._params(ispec, fspec, icnn_params, flow_params)
     dev = ip.device
     pool_coords, pool_targets, n_pool = _pool(ispec, n, pool_coords, pool_targets)
@@ -147,7 +150,7 @@ def cdn_fit_minibatch(ispec: K.IcnnSpec, fspec: FL.FlowSpec, icnn_params: Tensor
     ws = _workspace(ispec, fspec, batch, n, dev)
     hist, _, status = X.fit_outputs(n, steps, None, record_loss, False, dev)
     od = X.opt_desc("adam", lr, betas, eps, clamp=clamp, plateau=plateau)
-    X.call("inrfit_cdn_fit_minibatch", ispec._desc, fspec._desc, ip, fp, icnn_opt_state, flow_opt_state, pool_coords, pool_targets,
+    X.call("inrfit_cdn_fit_minibatch" if ispec.fused() else "inrfit_cdn_wide_fit_minibatch", ispec._desc, fspec._desc, ip, fp, icnn_opt_state, flow_opt_state, pool_coords, pool_targets,
            n_pool, index, carr, batch, X.loss_desc(loss, weight_mode, ratio, c_fg, c_bg), od, float(weight_decay_on_weight_g), n, steps,
            int(step0), hist, status, ws=ws, device=dev)
     return FL.CdnFitResult(ip, fp, icnn_opt_state, flow_opt_state, X.trim(hist, steps), None, status)

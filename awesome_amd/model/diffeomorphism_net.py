@@ -6,7 +6,8 @@ Same constructor kwargs and state_dict keys (torch's legacy weight_norm parametr
 creation order of the leaves (seeded construction = reference init).
 
 `ConvexDiffeomorphismNet.forward` and its autograd backward run entirely on the HIP path (flow kernels + ICNN kernels,
-`inrfit_cdn_forward` / `inrfit_cdn_loss_grad` with an external dL/dlogits); `fit_images` is the fused device-resident
+`inrfit_cdn_forward` / `inrfit_cdn_loss_grad` with an external dL/dlogits) - one composite call, whether the ICNN has a fused
+kernel or runs layer by layer (n_hidden > 130 or more than two hidden layers); `fit_images` is the fused device-resident
 form of `ConvexDiffeomorphismNet.pretrain`'s inner loop (`inrfit_cdn_fit`).  `NormalizingFlow1D.forward` (with autograd)
 and `ConvexDiffeomorphismNet.get_deformation` run on `inrfit_flow_forward` / `inrfit_flow_backward`.  The leaf modules
 (`WNLinear`, `NormalBlock`, `SimpleBackbone`, `WNScale`) are the containers of the parameters; called on their own they are
@@ -351,10 +352,23 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
 
     # -- the 'resnet' flow backbone: no fused fit; the reference's loop (:376-421) as device-side autograd ---------------------------
     def _generic(self) -> bool:
-        """No fused composite for this module: a whole-image flow backbone, or an ICNN shape without a fused kernel (n_hidden > 130 or more
-        than two hidden layers: the layer-by-layer path) - forward / backward compose the flow and ICNN kernels through autograd (the
-        ICNN's dL/dcoords feeds the flow's backward), `pretrain` runs the reference's loop on that."""
-        return self.diffeo_net.backbone == "resnet" or not self.convex_net.spec.fused()
+        """No device composite for this module: a whole-image flow backbone - forward / backward compose the flow in torch and the ICNN
+        kernels through autograd (the ICNN's dL/dcoords feeds the flow's backward), `pretrain` runs the reference's loop on that."""
+        return self.diffeo_net.backbone == "resnet"
+
+    def _generic_pretrain(self) -> bool:
+        """Whether `pretrain` runs `_generic_fit`: a module without a composite, and - the default so far - one whose ICNN runs layer by
+        layer (n_hidden > 130 or more than two hidden layers).  pretrain(device_fit_layer_by_layer=True) sends the second kind through
+        the batched device engine (inrfit_cdn_fit) like the fused shapes."""
+        return self._generic() or (not self.convex_net.spec.fused() and not getattr(self, "_device_fit_layer_by_layer", False))
+
+    def pretrain(self, *args, device_fit_layer_by_layer: bool = False, **kwargs):
+        # (the rows' layout follows the engine: _engine_pack / _engine_unpack / _engine_warm_start ask _generic_pretrain)
+        self._device_fit_layer_by_layer = bool(device_fit_layer_by_layer)
+        return super().pretrain(*args, **kwargs)
+
+    def _engine_name(self) -> str:
+        return "generic" if self._generic_pretrain() else "device"
 
     def _generic_fit(self, grid, unaries, flat, epochs, opts):
         """Adam (weight decay on the weight_g group only) + ReduceLROnPlateau(patience 200, factor 0.5) + enforce_convexity per step,
@@ -405,14 +419,14 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
         return torch.stack(out_flat), torch.stack(out_logits), torch.tensor(status, dtype=torch.int32, device=flat.device)
 
     def _engine_pack(self, sd):
-        if self._generic():
+        if self._generic_pretrain():
             return torch.cat([sd[k].detach().reshape(-1).to(torch.float32).cpu() for k, _ in self.named_parameters()])
         ispec, fspec = self._specs()
         i, f = FL.split_cdn_state_dict(ispec, fspec, sd)
         return torch.cat([i.cpu(), f.cpu()])
 
     def _engine_unpack(self, flat):
-        if self._generic():
+        if self._generic_pretrain():
             out, off = {}, 0
             for k, p_ in self.named_parameters():
                 out[k] = flat[off:off + p_.numel()].reshape(p_.shape).clone()
@@ -425,7 +439,7 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
         from ..measures import criterion_to_desc
         if opts.get("weight_decay_on_convex_weight", False):
             raise NotImplementedError("weight_decay_on_convex_weight=True (no reference config sets it) has no fused form")
-        if self._generic():
+        if self._generic_pretrain():
             return self._generic_fit(grid, unaries, flat, epochs, opts)
         ispec, fspec = self._specs()
         P = ispec.n_params
@@ -441,7 +455,7 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
     def _engine_warm_start(self, flat, ctx, image, opts):
         """:337-348: shift the previous frame's prior to this frame's centre of mass before the short refit."""
         com = center_of_mass(image.unaries)
-        if ctx is not None and self._generic():   # the same translate on this layout's `linear.weight` / `linear.bias` slices
+        if ctx is not None and self._generic_pretrain():   # the same translate on this layout's `linear.weight` / `linear.bias` slices
             off, where = 0, {}
             for k, p_ in self.named_parameters():
                 where[k] = (off, p_.numel())
@@ -531,11 +545,8 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
                 return torch.stack([self.convex_net(self.diffeo_net(self.linear(rows[i]))).reshape(1, h, w) for i in range(b)], 0)
             return self.convex_net(self.diffeo_net(self.linear(x)))
         ispec, fspec, icnn, flow = self._ordered_params()
-        if not ispec.fused():   # flow kernels, then the layer-by-layer ICNN: two autograd bridges instead of the fused composite
-            from .convex_net import _IcnnFunction
-            run = lambda coords: _IcnnFunction.apply(_FlowFunction.apply(coords, fspec, *flow), ispec, *icnn)  # noqa: E731
-        else:
-            run = lambda coords: _CdnFunction.apply(coords, ispec, fspec, len(icnn), *icnn, *flow)  # noqa: E731
+        # one composite call, over a fused ICNN shape and over one of the layer-by-layer path alike
+        run = lambda coords: _CdnFunction.apply(coords, ispec, fspec, len(icnn), *icnn, *flow)  # noqa: E731
         if x.dim() == 4:
             b, c, h, w = x.shape
             return torch.stack([run(x[i].reshape(c, h * w)).reshape(1, h, w) for i in range(b)], 0)
@@ -552,11 +563,10 @@ class ConvexDiffeomorphismNet(nn.Module, PriorFitMixin):
         (label < 0.5) + `number` random foreground pixels of pixel_info (N, 2) / labels (N,), loss w_bg BCE(bg) + w_fg BCE(fg) with
         class_weights = (w_bg, w_fg), Adam(lr) over every parameter, no projection unless `clamp`.  `batch_size`, `batch_index` /
         `counts` and `state` (opt_state, flow_opt_state, epoch) as on the ICNN modules.  The parameters are updated in place; returns
-        the CdnFitResult (loss_hist [1, steps]).  The fused composite only (a coupling-flow backbone over a fused ICNN shape)."""
+        the CdnFitResult (loss_hist [1, steps]).  The device composite only (a coupling-flow backbone; any ICNN shape the library runs)."""
         from .. import minibatch as MB
         if self._generic():
-            raise NotImplementedError("fit_minibatch runs the fused composite: a 'resnet' flow backbone or an ICNN shape without a fused "
-                                      "kernel has none")
+            raise NotImplementedError("fit_minibatch runs the device composite: a 'resnet' flow backbone has none")
         ispec, fspec, icnn, flow = self._ordered_params()
         dev = self.linear.weight.device
         pixel_info = pixel_info.to(device=dev, dtype=torch.float32)

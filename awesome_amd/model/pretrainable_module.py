@@ -196,7 +196,8 @@ class PriorFitMixin(PretrainableModule):
                     if do_pretrain_checkpoints and not im.from_checkpoint and im.status == 0:
                         save_pretrain_checkpoint(im.fitted, ckpt(im))
             self.pretrain_report = [dict(index=im.pos, key=im.key, skipped=im.skip, iou=im.iou, retries=im.retries,
-                                         from_checkpoint=im.from_checkpoint, status=im.status) for im in images]
+                                         from_checkpoint=im.from_checkpoint, status=im.status, engine=self._engine_name())
+                                    for im in images]
             if bad:
                 raise ValueError(f"Loss is nan or inf! (images {bad})")
             return cache.get_state()
@@ -340,3 +341,7 @@ class PriorFitMixin(PretrainableModule):
 
     def _engine_chain_context(self, ctx: Any, image: "_Image") -> Any:
         return ctx
+
+    def _engine_name(self) -> str:
+        """What `pretrain_report` calls the engine of this run: 'device' (the batched fits), or a module's own name for another one."""
+        return "device"

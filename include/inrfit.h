@@ -221,7 +221,12 @@ int inrfit_pack_masks(const float* values, int n_images, int64_t n_points, float
  *     linear.weight [2][2] | linear.bias [2] |
  *     for i in 0..K-1, for net in (s, t):  in_linear weight_v [W] | weight_g | bias [W] | out_linear weight_v [W] | weight_g | bias
  *     for i in 0..K-1 (WNScale):  weight | scale.bias | scale.weight_g | scale.weight_v
- *   FP = 6 + 2K(3W + 3) + 4K.   flow_opt_state = n_images * 2 * FP floats (exp_avg | exp_avg_sq), zero for a cold fit. */
+ *   FP = 6 + 2K(3W + 3) + 4K.   flow_opt_state = n_images * 2 * FP floats (exp_avg | exp_avg_sq), zero for a cold fit.
+ * The ICNN behind the flow: a shape with a fused kernel, or an ICNN-form shape of the layer-by-layer path (relu layer 0, one output,
+ * n_features = n_hidden, n_hidden <= 1024, n_layers <= 8) with in_features = 2 - inrfit_cdn_workspace_bytes / _forward / _loss_grad /
+ * _fit take both under the same names and semantics (the flow's kernels run all images in one launch, a layer-by-layer ICNN one image
+ * after the other in one image's workspace).  inrfit_cdn_joint_step and inrfit_cdn_fit_minibatch take the fused shapes only; the
+ * others go to inrfit_cdn_wide_joint_step and inrfit_cdn_wide_fit_minibatch. */
 enum { INR_FLOW_NORMAL_BLOCK = 0, /* NormalBlock: tanh(WN2 leaky_relu(WN1 u)), keys in_linear / out_linear (diffeomorphism_net.py:169-192;
                                      backbone 'normal_block' / 'residual_block' - every reference config) */
        INR_FLOW_SIMPLE = 1        /* SimpleBackbone: tanh(WN2 relu(WN1 u)), keys linear1 / linear2 (:83-104; NormalizingFlow1D's
@@ -395,6 +400,15 @@ int inrfit_cdn_fit_minibatch(const InrModelDesc* model, const InrFlowDesc* flow,
                              int64_t n_pool, const int32_t* index, const int32_t* counts, int64_t batch, const InrLossDesc* loss,
                              const InrOptDesc* opt, float weight_decay_on_weight_g, int n_images, int steps, int step0,
                              float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* inrfit_cdn_fit_minibatch takes the ICNN shapes with a fused kernel.  The pair below is the same call, with the same checks in the
+ * same order, for the flow over an ICNN of the layer-by-layer path (ICNN-form, no fused kernel, in_features = 2: the shapes
+ * inrfit_cdn_fit takes beyond the fused ones); every other shape: INR_EUNSUPPORTED. */
+int64_t inrfit_cdn_wide_minibatch_workspace_bytes(const InrModelDesc* model, const InrFlowDesc* flow, int64_t batch, int n_images);
+int inrfit_cdn_wide_fit_minibatch(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
+                                  float* icnn_opt_state, float* flow_opt_state, const float* pool_coords, const float* pool_targets,
+                                  int64_t n_pool, const int32_t* index, const int32_t* counts, int64_t batch, const InrLossDesc* loss,
+                                  const InrOptDesc* opt, float weight_decay_on_weight_g, int n_images, int steps, int step0,
+                                  float* loss_hist, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- rotation / mirror-symmetry prior of the teaser: pose and network trained together (csrc/sym.h) --------------------------------
  * Replaces: `myNet` of notebooks/icml_teaser_code/rotation_symmetric/rotation_symmetric.ipynb cell 2 and the loop of cell 3 (one Adam
@@ -594,6 +608,21 @@ int inrfit_wide_joint_prior_step(const InrModelDesc* model, float* params, float
                                  const float* target, const InrJointPriorDesc* desc, const float* seg_term, const InrOptDesc* opt,
                                  int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
                                  int64_t workspace_bytes, void* stream);
+
+/* The same step for ConvexDiffeomorphismNet over such an ICNN: the twin of inrfit_pcn_wide_joint_step behind the weight-normed coupling
+ * flow, with the argument list and semantics of inrfit_cdn_joint_step (Adam only: any other optimizer is INR_EINVAL, answered before
+ * the model is looked at; wd_on_weight_g as in inrfit_cdn_fit).  It takes exactly the shapes inrfit_cdn_joint_step refuses -
+ * ICNN-form, no fused kernel, in_features = 2 - and refuses the others (fused shapes, encode shapes: INR_EUNSUPPORTED).  One step =
+ * the flow's forward | the layer-by-layer forward and backward, whose dL/dcoords lands planar [2][n_points] in the flow's buffer | the
+ * finish kernel | the ICNN's optimizer step | the flow's backward and its Adam step with the same gradient scale, this step's
+ * learning rate and the frozen flag from the ICNN's header | d loss / d seg (all zeros when *status = 1).
+ * The other inrfit_cdn_* calls (workspace_bytes, forward, loss_grad, fit, fit_minibatch) take these shapes under their own names. */
+int64_t inrfit_cdn_wide_joint_step_workspace_bytes(const InrModelDesc* model, const InrFlowDesc* flow, const InrGridDesc* grid);
+int inrfit_cdn_wide_joint_step(const InrModelDesc* model, const InrFlowDesc* flow, float* icnn_params, float* flow_params,
+                               float* icnn_opt_state, float* flow_opt_state, const InrGridDesc* grid, const float* seg,
+                               const float* target, const InrJointLossDesc* desc, const InrOptDesc* opt, float wd_on_weight_g,
+                               int step, float* loss_out, float* dseg, float* prior_logits, int32_t* status, void* workspace,
+                               int64_t workspace_bytes, void* stream);
 
 /* Measurement hook (bench.py, rocprof): launch ONLY the fused forward+loss+backward step kernel `iters` times
  * back-to-back on `stream` (no optimizer step), so its average duration can be bracketed with events. */

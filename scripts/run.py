@@ -330,10 +330,13 @@ def _fit_shard(cfg, ds, mine, agent, wrapper, criterion, model_type, model_args,
         # agent_args.fused_segmentation (opt-in, with fused_convexity_losses): a supported CNNNet takes its step in HIP too
         # agent_args.fused_layer_by_layer (opt-in): an ICNN of the layer-by-layer path (n_hidden > 130 or more than two hidden layers),
         # alone or inside a PathConnectedNet, takes the fused joint step too (inrfit_wide_joint_step and its kin)
+        # agent_args.fused_cdn_layer_by_layer (opt-in, with fused_layer_by_layer): ... and inside a ConvexDiffeomorphismNet
+        # (inrfit_cdn_wide_joint_step); its pretrain fits take the device engine under pretrain_args.device_fit_layer_by_layer
         trainer = JointTrainer(jw, bank, criterion, opt, fused_extra_penalty=bool(aa.get("fused_extra_penalty", False)),
                                fused_convexity_losses=bool(aa.get("fused_convexity_losses", False)),
                                fused_segmentation=bool(aa.get("fused_segmentation", False)),
-                               fused_layer_by_layer=bool(aa.get("fused_layer_by_layer", False)))
+                               fused_layer_by_layer=bool(aa.get("fused_layer_by_layer", False)),
+                               fused_cdn_layer_by_layer=bool(aa.get("fused_cdn_layer_by_layer", False)))
         for epoch in range(joint_epochs):
             # the runner's extra-penalty hook (awesome/run/awesome_runner.py:351-371; config fields awesome_config.py:164-173): from
             # epoch N on the loss adds its penalty term, optionally with the learning rate scaled once
